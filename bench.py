@@ -2,18 +2,23 @@
 """Headline benchmark: point-clouds/sec (fwd+bwd+optimizer) of the PointMamba classifier at
 B=64 per GPU, 1024 points -> 128 patches, d=384, 12 blocks (Mamba L = 1024), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports the headline (metric,
+value, unit, ms_per_step, dtype, config).  Each step (fwd, bwd, grad clip, AdamW update) starts from the seeded initial
+parameters and a fresh optimizer state.  ``--dump-outputs DIR`` writes what the last timed step computed (logits, loss,
+gradients) as .npy files; the inputs depend on the arguments only, so two builds can be compared (dump_outputs()).
+``--full`` adds everything else the benchmark measures (each piece can be dropped with its --no-* switch):
   roofline      selective-scan forward kernel inside the timed region: algorithmic bytes per launch /
                 mean launch duration from events recorded on the launch stream, vs 8 TB/s HBM.
   cpu_baseline  the oracle (CPU restatement) running the same step on a bounded sample (two steps of 4 clouds after a
                 warm-up step) on the host cores.
 plus "headline_scan" (the north-star micro-shape B=256, L=128, D=768, N=16, measured after the timed region, fp32 and
-bf16 I/O), "kernels" (mean ms per launch of the two scan kernels, event-bracketed inside the timed region) and
-"kernels_outside_timed_region" (the other HIP kernels, from two more steps after it).
+bf16 I/O), "kernels" (mean ms per launch of the two scan kernels, event-bracketed inside the timed region),
+"kernels_outside_timed_region" (the other HIP kernels, from two more steps after it) and "bf16_step" (the same step
+under bf16 autocast, after the timed region).
 """
 from __future__ import annotations
 
@@ -244,6 +249,32 @@ def headline_scan(device, iters=30):
     return res
 
 
+GRAD_CAP = 12 << 20      # gradient values kept in full up to this count (48 MiB of fp32)
+
+
+def dump_outputs(path, model, logits, loss):
+    """What the last timed step computed, as float32 .npy files under ``path``: ``logits`` (B, classes), ``loss`` (0-d)
+    and ``grads`` (every parameter's gradient after clipping, flattened in named_parameters() order; 49 MB at the
+    default configuration).  Past GRAD_CAP values the gradients are replaced by the values at a fixed seeded set of
+    indices, the same set in every run.
+
+    Every step starts from the same initial state (main(): reset()), so with the same arguments the last step sees
+    the same inputs in every run: loss and logits repeat bit for bit, gradients to rounding (the scan backward adds
+    into dB / dC with float atomics, in no fixed order).  Under --dtype bf16 loss and logits repeat bit for bit as well;
+    the gradients differ more (measured: 2-4 % of their largest value), as those last-bit differences pass through
+    bf16 roundings in the backward."""
+    import numpy as np
+
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                       for p in model.parameters()])
+    if grads.numel() > GRAD_CAP:
+        idx = torch.randperm(grads.numel(), generator=torch.Generator().manual_seed(0))[:GRAD_CAP].sort().values
+        grads = grads[idx.to(grads.device)]
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("logits", logits), ("loss", loss), ("grads", grads)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -256,6 +287,12 @@ def main():
     ap.add_argument("--scan-variant", type=int, default=0,
                     help="A/B tool: force one forward-scan kernel (include/simamba.h SIMAMBA_SCAN_*; 0 = the library's "
                          "choice, which is what every reported line uses)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: scan kernel times and roofline (events "
+                         "around the scan launches inside the timed region), the other kernels' times, the bf16 "
+                         "step, headline_scan and the CPU baseline; the --no-* switches drop single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-headline", action="store_true")
     ap.add_argument("--no-bf16-step", action="store_true",
@@ -264,6 +301,9 @@ def main():
     ap.add_argument("--no-tuned-gemm", action="store_true",
                     help="library-default GEMM solutions instead of si_mamba_amd/tuned/gemm_gfx950.csv")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    kernel_timing = args.full and not args.no_kernel_timing
 
     from si_mamba_amd import _lib
     from si_mamba_amd import dist as sdist
@@ -299,8 +339,26 @@ def main():
     pts = make_clouds(args.batch, args.npoints, seed=rank, device=device)
     gt = torch.randint(0, cfg.cls_dim, (args.batch,), generator=torch.Generator().manual_seed(rank)).to(device)
     amp = torch.autocast("cuda", dtype=torch.bfloat16, enabled=(args.dtype == "bf16"))
+    # Every step starts from the same state: the initial parameters and a fresh AdamW state (all zero).  The backward
+    # adds with float atomics in no fixed order, so gradients differ in their last bits from run to run, and an AdamW
+    # update turns such a difference on a near-zero gradient into a step of up to lr: carried from step to step, two
+    # runs on the same inputs would drift apart.  Reset, each step computes the same thing from the same inputs, with
+    # the same work (forward, backward, clip, AdamW update).  Parameters and optimizer state are all fp32, so the reset
+    # is a few multi-tensor launches (~150 MB); the BatchNorm running statistics are not read by a training step.
+    params = list(model.parameters())
+    init = [p.detach().clone() for p in params]
+    opt_state = []          # AdamW creates its state at the first step and updates it in place from then on
+
+    def reset():
+        with torch.no_grad():
+            torch._foreach_copy_(params, init)
+            if not opt_state:
+                opt_state.extend(v for s in opt.state.values() for v in s.values() if torch.is_tensor(v))
+            if opt_state:
+                torch._foreach_zero_(opt_state)
 
     def step(amp=amp):
+        reset()
         opt.zero_grad(set_to_none=True)
         with amp:
             logits = ddp(pts)
@@ -308,7 +366,7 @@ def main():
         loss.backward()
         torch.nn.utils.clip_grad_norm_(model.parameters(), 10.0)     # grad_norm_clip: 10
         opt.step()
-        return loss
+        return loss, logits
 
     def sync():
         if world > 1:
@@ -317,24 +375,26 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # events around the scan launches only (the roofline kernels): a pair of event records around every launch of the
-    # step costs 0.5 ms (fp32) to 7 ms (bf16, CPU-bound then) of the step it measures
-    _lib.enable_kernel_timing(not args.no_kernel_timing, only=("scan_fwd", "scan_bwd"))
+    # --full: events around the scan launches only (the roofline kernels): a pair of event records around every launch
+    # of the step costs 0.5 ms (fp32) to 7 ms (bf16, CPU-bound then) of the step it measures
+    _lib.enable_kernel_timing(kernel_timing, only=("scan_fwd", "scan_bwd"))
     _lib._scan_variant[0] = args.scan_variant
     gc.collect()        # a full collection of the interpreter (~80 ms with this many live tensors) now, not inside the region
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
         te = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = te.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, logits, loss)
     ktimes = _lib.kernel_times()
     other = {}
-    if not args.no_kernel_timing:
+    if kernel_timing:
         # the other HIP kernels' mean durations, for the record: two more steps with every launch bracketed, untimed
         _lib.enable_kernel_timing(True)
         for _ in range(2):
@@ -346,9 +406,9 @@ def main():
 
     # The same step under bf16 autocast (what the reference's pre-training and segmentation runners use,
     # tools/runner_pretrain.py:243), measured AFTER the timed region so that the driver's record carries it: not the
-    # headline, same model / data / optimizer state continued, 3 warm-up + 10 timed steps, max over ranks.
+    # headline, same model / data, each step from the initial state, 3 warm-up + 10 timed steps, max over ranks.
     bf16_step = None
-    if args.dtype == "f32" and not args.no_bf16_step:
+    if args.full and args.dtype == "f32" and not args.no_bf16_step:
         amp16 = torch.autocast("cuda", dtype=torch.bfloat16)
         for _ in range(3):
             step(amp16)
@@ -356,7 +416,7 @@ def main():
         sync()
         t1 = time.perf_counter()
         for _ in range(10):
-            loss16 = step(amp16)
+            loss16, _ = step(amp16)
         sync()
         el16 = time.perf_counter() - t1
         if world > 1:
@@ -368,7 +428,7 @@ def main():
                      "dtype": "bf16 autocast (parameters, optimizer, reductions, scan state fp32)",
                      "finite_loss": bool(torch.isfinite(loss16).item()),
                      "note": "measured after the timed fp32 region on the same model and data; not the headline"}
-        if not args.no_kernel_timing:
+        if kernel_timing:
             # two more bf16 steps with every HIP launch event-bracketed (untimed), and which routes the mixer took:
             # delta formed inside the scans (scan_dt_fwd) and out_proj + add + LayerNorm as one kernel (out_proj_add_ln)
             _lib.counters.clear()
@@ -453,11 +513,11 @@ def main():
                              "waves/SIMD); DESIGN.md 4.2")}
         if bf16_step is not None:
             out["bf16_step"] = bf16_step
-        if world == 1 and not args.no_headline:
+        if args.full and world == 1 and not args.no_headline:
             del opt
             torch.cuda.empty_cache()
             out["headline_scan"] = headline_scan(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.npoints, args.groups)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -177,9 +177,29 @@ def param_table():
     print("param table:", len(rows), "tensors,", total, "parameters")
 
 
+def cpu_platform():
+    """The kind of CPU a float fixture is generated on: vendor, model name and the vector ISA torch dispatches to.  The
+    CPU restatements reproduce a fixture bit for bit on this kind only: on other CPUs MKL and the vectorised torch
+    kernels round a few last bits differently."""
+    info = {}
+    with open("/proc/cpuinfo") as fh:
+        for line in fh:
+            key, _, val = line.partition(":")
+            info.setdefault(key.strip(), val.strip())
+    return f"{info.get('vendor_id')} | {info.get('model name')} | {torch.backends.cpu.get_cpu_capability()}"
+
+
+def record_cpu_platform():
+    """tests/golden/cpu_platform.json: where the float fixtures were written (tests/conftest.py reads it)."""
+    with open(os.path.join(OUT, "cpu_platform.json"), "w") as fh:
+        json.dump({"cpu": cpu_platform()}, fh)
+        fh.write("\n")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(4)
+    record_cpu_platform()
     scan_case("scan_cfg1", batch=2, dim=64, L=64, N=16, seed=0)
     scan_case("scan_l128", batch=2, dim=48, L=128, N=16, seed=1)
     scan_case("scan_multichunk_ragged", batch=1, dim=32, L=300, N=16, seed=2)

@@ -2,7 +2,7 @@
 
     python -m oracle.pin_from_reference          # from the repo root, in the build container (needs /root/reference)
 
-TEST INFRASTRUCTURE.  Writes tests/golden/ref_*.npz; nothing of the reference's source is copied into the repository
+TEST INFRASTRUCTURE.  Writes tests/golden/ref_*; nothing of the reference's source is copied into the repository
 -- the functions are read from /root/reference at run time, executed, and only their inputs and outputs are kept.
 
 Why not ``import models.point_mamba``: its module-level imports need timm, pytorch3d, mamba_ssm and easydict, none of
@@ -291,17 +291,57 @@ def stack_fixture(scope):
     return rec
 
 
+def create_block_fixture():
+    """The reference's own create_block / Block / _init_weights building THIS package's Mamba through the import shim
+    -> ref_create_block.json: the call create_block makes to Mamba, the block's state-dict names and shapes in order,
+    and which parameters _init_weights re-draws."""
+    import json
+    import si_mamba_amd
+    si_mamba_amd.install_shim()
+    from mamba_ssm.modules.mamba_simple import Mamba          # the reference's import line, models/point_mamba.py:25
+    calls = []
+
+    def recording_mamba(*args, **kwargs):
+        calls.append({"args": list(args), "kwargs": kwargs})
+        return Mamba(*args, **kwargs)
+
+    scope = {"torch": torch, "nn": nn, "F": F, "math": math, "partial": partial, "Tensor": Tensor,
+             "Optional": Optional, "Mamba": recording_mamba, "DropPath": _DropPath, "RMSNorm": None,
+             "layer_norm_fn": None, "rms_norm_fn": None}
+    _exec_defs([_find(_parse(REF_BLOCK).body, ast.ClassDef, "Block")], scope, REF_BLOCK)
+    tree = _parse(REF_MODEL)
+    _exec_defs([_find(tree.body, ast.FunctionDef, "_init_weights"),
+                _find(tree.body, ast.FunctionDef, "create_block")], scope, REF_MODEL)
+    torch.manual_seed(0)
+    blk = scope["create_block"](384, layer_idx=0, drop_path=0.0)
+    before = {k: v.clone() for k, v in blk.state_dict().items()}
+    blk.apply(partial(scope["_init_weights"], n_layer=12))
+    rec = {"source": "reference models/point_mamba.py create_block, _init_weights; models/block.py Block",
+           "create_block": {"d_model": 384, "layer_idx": 0, "drop_path": 0.0}, "init_n_layer": 12,
+           "mamba_calls": calls, "block_layer_idx": blk.layer_idx,
+           "state_dict": [[k, list(v.shape)] for k, v in blk.state_dict().items()],
+           "reinitialised": [k for k, v in blk.state_dict().items() if not torch.equal(v, before[k])]}
+    with open(os.path.join(OUT, "ref_create_block.json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
+    return rec
+
+
 def main():
     if not reference_present():
-        print("reference not present: keeping the committed ref_*.npz", file=sys.stderr)
+        print("reference not present: keeping the committed ref_* fixtures", file=sys.stderr)
         return 1
+    from oracle.gen_golden import record_cpu_platform
     torch.set_num_threads(4)
+    record_cpu_platform()
     methods, sast, hlt_fn, scope = load_reference()
     for name in ("spectral_g64", "spectral_g128", "spectral_g128_surface"):
         rec = spectral_fixture(name, methods, sast, hlt_fn)
         print(f"ref_{name}.npz: {len(rec)} arrays")
     rec = stack_fixture(scope)
     print(f"ref_stack.npz: {len(rec)} arrays")
+    rec = create_block_fixture()
+    print(f"ref_create_block.json: {len(rec['state_dict'])} parameters")
     return 0
 
 

@@ -11,21 +11,24 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
-from oracle import pin_from_reference as pin
+from conftest import assert_fixture_floats, load_golden, on_fixture_cpu
 from oracle import scan_ref
 from oracle import spectral_ref as sr
 from oracle.gen_golden import SPECTRAL_COMBOS
 
 NAMES = ["spectral_g64", "spectral_g128", "spectral_g128_surface"]
+ADJ_TOL = dict(rtol=0, atol=1e-6)          # adjacency entries lie in [0, 1]
+STACK_TOL = dict(rtol=1e-5, atol=1e-6)     # block-stack activations and input gradients
 
 
 @pytest.fixture
 def lapack_as_recorded():
-    """eigh's last bits depend on the LAPACK thread count: run with the count the fixtures were generated with."""
+    """eigh's last bits depend on the LAPACK thread count and the kind of CPU: run with the count the fixtures were
+    generated with; setup() tells whether the whole configuration (torch, threads, CPU) is the recorded one."""
     def setup(g):
         torch.set_num_threads(int(g["lapack_threads"]))
-        return str(g["torch_version"]) == torch.__version__ and torch.get_num_threads() == int(g["lapack_threads"])
+        return (str(g["torch_version"]) == torch.__version__ and torch.get_num_threads() == int(g["lapack_threads"])
+                and on_fixture_cpu())
     before = torch.get_num_threads()
     yield setup
     torch.set_num_threads(before)
@@ -41,7 +44,7 @@ def test_oracle_graph_eigen_orders_equal_reference_outputs(name, lapack_as_recor
         t = cb["tag"]
         adj = sr.create_graph_from_feature_space(centers, cb["knn"], cb["alpha"], cb["symmetric"], cb["self_loop"],
                                                  cb["binary"])
-        np.testing.assert_array_equal(adj.numpy(), g[f"{t}.adj"])                      # bit for bit
+        assert_fixture_floats(adj.numpy(), g[f"{t}.adj"], **ADJ_TOL)                  # bit for bit on its CPU
         vals, vecs, all_vals, _ = sr.calc_top_k_eigenvalues_eigenvectors(adj, 4, True)
         np.testing.assert_allclose(vals.numpy(), g[f"{t}.vals"], rtol=0, atol=3e-6)
         np.testing.assert_allclose(all_vals.numpy(), g[f"{t}.all_vals"], rtol=0, atol=3e-6)
@@ -70,10 +73,10 @@ def test_oracle_graph_eigen_orders_equal_reference_outputs(name, lapack_as_recor
     np.testing.assert_allclose(e.numpy(), g["hardest.largest.vecs"], rtol=0, atol=1e-4)
     if same_lapack:
         np.testing.assert_array_equal(e.numpy(), g["hardest.largest.vecs"])
-    np.testing.assert_array_equal(sr.create_graph_from_centers(centers, 10, 0.0, True, True, False).numpy(),
-                                  g["sigma_mean.adj"])
-    np.testing.assert_array_equal(sr.create_graph_from_centers(centers, 10, 10.0, True, True, False).numpy(),
-                                  g["centers_graph.adj"])
+    assert_fixture_floats(sr.create_graph_from_centers(centers, 10, 0.0, True, True, False).numpy(),
+                          g["sigma_mean.adj"], **ADJ_TOL)
+    assert_fixture_floats(sr.create_graph_from_centers(centers, 10, 10.0, True, True, False).numpy(),
+                          g["centers_graph.adj"], **ADJ_TOL)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -133,20 +136,22 @@ def test_oracle_block_stack_equals_reference_block_and_mixermodel():
     pos = torch.from_numpy(g["pos"]).requires_grad_(True)
     out = run(x, pos)
     out.backward(torch.from_numpy(g["dout"]))
-    # same torch ops in the same order as models/block.py:56-72 and models/point_mamba.py:247-258: exact
-    np.testing.assert_array_equal(out.detach().numpy(), g["out"])
-    np.testing.assert_array_equal(x.grad.numpy(), g["grad_x"])
-    np.testing.assert_array_equal(pos.grad.numpy(), g["grad_pos"])
+    # same torch ops in the same order as models/block.py:56-72 and models/point_mamba.py:247-258: exact on the CPU
+    # the fixture was written on
+    assert_fixture_floats(out.detach().numpy(), g["out"], **STACK_TOL)
+    assert_fixture_floats(x.grad.numpy(), g["grad_x"], **STACK_TOL)
+    assert_fixture_floats(pos.grad.numpy(), g["grad_pos"], **STACK_TOL)
+    grad_tol = dict(rtol=1e-6, atol=1e-7) if on_fixture_cpu() else STACK_TOL
     for i, m in enumerate(mixers):
         for k, p in m.named_parameters():
-            np.testing.assert_allclose(p.grad.numpy(), g[f"grad.layers.{i}.mixer.{k}"], rtol=1e-6, atol=1e-7)
+            np.testing.assert_allclose(p.grad.numpy(), g[f"grad.layers.{i}.mixer.{k}"], **grad_tol)
     # one Block, both call forms: (mixer(LN(h)), h) and (mixer(LN(h + r)), h + r)
     h, r = torch.from_numpy(g["block.h"]), torch.from_numpy(g["block.r"])
     ln = torch.nn.functional.layer_norm
     w, b = sd["layers.0.norm.weight"], sd["layers.0.norm.bias"]
-    np.testing.assert_array_equal(mixers[0](ln(h, (d,), w, b, 1e-5)).detach().numpy(), g["block.first.h"])
+    assert_fixture_floats(mixers[0](ln(h, (d,), w, b, 1e-5)).detach().numpy(), g["block.first.h"], **STACK_TOL)
     np.testing.assert_array_equal(h.numpy(), g["block.first.r"])
-    np.testing.assert_array_equal(mixers[0](ln(h + r, (d,), w, b, 1e-5)).detach().numpy(), g["block.next.h"])
+    assert_fixture_floats(mixers[0](ln(h + r, (d,), w, b, 1e-5)).detach().numpy(), g["block.next.h"], **STACK_TOL)
     np.testing.assert_array_equal((h + r).numpy(), g["block.next.r"])
 
 
@@ -177,56 +182,37 @@ def test_reference_init_contract_and_state_dict_names():
         assert 0.9 * bound < w <= bound * (1 + 1e-6)
 
 
-@pytest.mark.skipif(not pin.reference_present(), reason="/root/reference is not on this machine")
-def test_committed_fixtures_are_what_the_reference_returns_today():
-    """Regenerates one fixture from the reference's files and compares it with the committed one."""
-    methods, sast, hlt_fn, scope = pin.load_reference()
-    import os
-    import tempfile
-    torch.set_num_threads(int(load_golden("ref_spectral_g64")["lapack_threads"]))
-    old = pin.OUT
-    with tempfile.TemporaryDirectory() as tmp:
-        # the generator reads the centres from the committed spectral_g64.npz and writes ref_spectral_g64.npz
-        os.symlink(os.path.join(old, "spectral_g64.npz"), os.path.join(tmp, "spectral_g64.npz"))
-        pin.OUT = tmp
-        try:
-            rec = pin.spectral_fixture("spectral_g64", methods, sast, hlt_fn)
-        finally:
-            pin.OUT = old
-    g = load_golden("ref_spectral_g64")
-    assert set(rec) == set(g)
-    for k in g:
-        np.testing.assert_array_equal(np.asarray(rec[k]), g[k], err_msg=k)
-
-
-@pytest.mark.skipif(not pin.reference_present(), reason="/root/reference is not on this machine")
 def test_reference_create_block_over_the_shim_has_the_contract_names():
-    """The reference's own create_block (models/point_mamba.py:147-175) and Block (models/block.py:17-45), compiled
-    from its files, building THIS package's Mamba through the import shim: constructs without a GPU, and its
-    state_dict() carries the names and shapes of the reference's training log (tests/golden/param_table_*.json)."""
-    import ast
+    """The reference's own create_block (models/point_mamba.py:147-175), Block (models/block.py:17-45) and
+    _init_weights, run over the import shim by oracle/pin_from_reference.py, are recorded in ref_create_block.json:
+    the call they make to Mamba, the block's state-dict names and shapes, the parameters _init_weights re-draws.  The
+    recorded call resolves through the shim to THIS package's Mamba, the names and shapes are those of the reference's
+    training log (tests/golden/param_table_*.json), and this package's create_block / _init_weights give the same."""
     import json
-    import math
     import os
     from functools import partial
-    from typing import Optional
     import si_mamba_amd
+    from si_mamba_amd.block import _init_weights, create_block
     si_mamba_amd.install_shim()
     from mamba_ssm.modules.mamba_simple import Mamba          # the reference's import line, models/point_mamba.py:25
-    scope = {"torch": torch, "nn": torch.nn, "F": torch.nn.functional, "math": math, "partial": partial,
-             "Tensor": torch.Tensor, "Optional": Optional, "Mamba": Mamba, "DropPath": pin._DropPath, "RMSNorm": None,
-             "layer_norm_fn": None, "rms_norm_fn": None}
-    pin._exec_defs([pin._find(pin._parse(pin.REF_BLOCK).body, ast.ClassDef, "Block")], scope, pin.REF_BLOCK)
-    tree = pin._parse(pin.REF_MODEL)
-    pin._exec_defs([pin._find(tree.body, ast.FunctionDef, "_init_weights"),
-                    pin._find(tree.body, ast.FunctionDef, "create_block")], scope, pin.REF_MODEL)
-    blk = scope["create_block"](384, layer_idx=0, drop_path=0.0)
-    blk.apply(partial(scope["_init_weights"], n_layer=12))
-    assert type(blk.mixer) is Mamba and blk.layer_idx == 0 and blk.mixer.layer_idx == 0
-    table = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "param_table_finetune_hardest.json")))
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    rec = json.load(open(os.path.join(golden, "ref_create_block.json")))
+    (call,) = rec["mamba_calls"]
+    mixer = Mamba(*call["args"], **call["kwargs"])
+    assert type(mixer) is si_mamba_amd.Mamba and mixer.layer_idx == rec["create_block"]["layer_idx"]
+    table = json.load(open(os.path.join(golden, "param_table_finetune_hardest.json")))
     want = {r["name"][len("blocks.layers.0."):]: tuple(r["shape"]) for r in table["params"]
             if r["name"].startswith("blocks.layers.0.")}
-    got = {k: tuple(v.shape) for k, v in blk.state_dict().items()}
-    assert got == want
+    recorded = [(k, tuple(v)) for k, v in rec["state_dict"]]
+    assert dict(recorded) == want
+    assert {"mixer." + k: tuple(v.shape) for k, v in mixer.state_dict().items()} == \
+        {k: v for k, v in want.items() if k.startswith("mixer.")}
+    torch.manual_seed(0)
+    blk = create_block(**rec["create_block"])
+    before = {k: v.clone() for k, v in blk.state_dict().items()}
+    blk.apply(partial(_init_weights, n_layer=rec["init_n_layer"]))
+    assert [(k, tuple(v.shape)) for k, v in blk.state_dict().items()] == recorded
+    assert blk.layer_idx == rec["block_layer_idx"] and blk.mixer.layer_idx == rec["block_layer_idx"]
+    assert [k for k, v in blk.state_dict().items() if not torch.equal(v, before[k])] == rec["reinitialised"]
     assert getattr(blk.mixer.dt_proj.bias, "_no_reinit", False)
     assert blk.mixer.dt_proj.bias.detach().abs().min() > 0

@@ -15,7 +15,7 @@ run() { # name, timeout, cmd...
 }
 run tests 900 python -m pytest tests -m gpu -q --no-header -rf -p no:cacheprovider
 tail -2 $O/tests.log
-run bench 600 python bench.py --steps 10 --warmup 3
+run bench 600 python bench.py --steps 10 --warmup 3 --full
 grep '^{' $O/bench.log | tail -1 > $O/bench.json
 run prof_f32 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f32 -- python3 bench.py --steps 7 --warmup 1 --no-cpu-baseline --no-headline --no-kernel-timing --no-bf16-step
 cp "$(find $O/prof_f32 -name '*kernel_stats.csv' | head -1)" $O/bench_kernel_stats.csv

@@ -13,7 +13,7 @@ run() { # name, timeout, cmd...
 }
 run tests 900 python -m pytest tests -m gpu -q --no-header -rf -p no:cacheprovider
 tail -4 gpurun_out/tests.log
-run bench 600 python bench.py --steps 5 --warmup 2
+run bench 600 python bench.py --steps 5 --warmup 2 --full
 tail -1 gpurun_out/bench.log
 if [ "${PROFILE:-1}" = "1" ]; then
   run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
