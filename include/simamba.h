@@ -133,7 +133,8 @@ int simamba_selective_scan_fwd(const void* u, const void* delta, const float* A,
  * forward; ckpt_step selects the kernel: _ROW the row-scan backward, _SEQ the sequential one).
  * du, ddelta, dz : io_dtype (dz NULL iff z NULL).
  * dA (dim,dstate), dB, dC (batch,dstate,seqlen), dD, ddelta_bias (dim): fp32; the library
- * zeroes them on `stream` and then accumulates (float atomics: last-bit run-to-run jitter).
+ * zeroes them on `stream` and then accumulates (float atomics: last-bit run-to-run jitter; see the
+ * _ex form below for the deterministic alternative).
  * Not one byte outside these five spans is written: spans that are exactly adjacent in memory
  * (one ends where the next begins) are cleared by a single memset node, all others one by one.
  * dD / ddelta_bias may be NULL when D / delta_bias are NULL.  dB / dC are always contiguous
@@ -148,6 +149,32 @@ int simamba_selective_scan_bwd(const void* u, const void* delta, const float* A,
                                int io_dtype, int delta_softplus, long long z_bstride,
                                long long dz_bstride, long long bc_bstride, long long bc_nstride,
                                long long bc_tstride, int ckpt_step, void* stream);
+
+/*
+ * Deterministic backward (flags of the *_ex backward entry points; 0 = the plain entry point, bit for bit).
+ *   SIMAMBA_BWD_DETERMINISTIC: no float atomics.  Every workgroup stores its partial sums to `workspace` and a
+ *   fixed-order sum pass (ascending partial index, fp32) writes the parameter gradients -- dA, dB, dC, dD, ddelta_bias
+ *   of the scan, dw, dbias of the conv -- WHOLE, so the result is bitwise reproducible run to run for the same inputs,
+ *   shape and device.  Written: exactly the spans the plain call writes (no memset is issued: the sum pass stores
+ *   every element) plus the first *_workspace_floats() floats of `workspace` (scratch, contents undefined afterwards).
+ *   workspace: device memory, 16-byte aligned (else SIMAMBA_E_ALIGN), at least *_workspace_floats() floats (else, or
+ *   NULL, SIMAMBA_E_WORKSPACE); unknown flag bits: SIMAMBA_E_VARIANT.  All three checks precede any launch.
+ *   *_workspace_floats(): the size for a shape (host arithmetic only); 0 for flags == 0 (workspace may be NULL);
+ *   a negative SIMAMBA_E_* for arguments the backward would refuse.  ckpt_step as given to the backward (0 = _ROW;
+ *   the dt form always uses _SEQ).
+ */
+#define SIMAMBA_BWD_DETERMINISTIC 1
+long long simamba_scan_bwd_workspace_floats(int batch, int dim, int seqlen, int dstate, int ckpt_step, int flags);
+int simamba_selective_scan_bwd_ex(const void* u, const void* delta, const float* A,
+                                  const void* B, const void* C, const float* D, const void* z,
+                                  const float* delta_bias, const void* dout, const float* x_ckpt,
+                                  void* du, void* ddelta, float* dA, float* dB, float* dC,
+                                  float* dD, void* dz, float* ddelta_bias,
+                                  int batch, int dim, int seqlen, int dstate,
+                                  int io_dtype, int delta_softplus, long long z_bstride,
+                                  long long dz_bstride, long long bc_bstride, long long bc_nstride,
+                                  long long bc_tstride, int ckpt_step, int flags, float* workspace,
+                                  long long workspace_floats, void* stream);
 
 /*
  * The mixer's scan with delta formed INSIDE the scan kernels (no (batch, dim, seqlen) delta tensor exists): what
@@ -177,6 +204,14 @@ int simamba_selective_scan_dt_bwd(const void* u, const void* xdbl, const void* w
                                   float* ddelta_bias, int batch, int dim, int seqlen, int dstate, int dt_rank,
                                   int io_dtype, long long z_bstride, long long dz_bstride, long long xdbl_bstride,
                                   long long xdbl_tstride, void* stream);
+/* ... and its deterministic form (flags / workspace as simamba_selective_scan_bwd_ex, ckpt_step _SEQ) */
+int simamba_selective_scan_dt_bwd_ex(const void* u, const void* xdbl, const void* wdt, const float* A, const float* D,
+                                     const void* z, const float* delta_bias, const void* dout, const float* x_ckpt,
+                                     void* du, void* ddelta, float* dA, float* dB, float* dC, float* dD, void* dz,
+                                     float* ddelta_bias, int batch, int dim, int seqlen, int dstate, int dt_rank,
+                                     int io_dtype, long long z_bstride, long long dz_bstride, long long xdbl_bstride,
+                                     long long xdbl_tstride, int flags, float* workspace, long long workspace_floats,
+                                     void* stream);
 
 /*
  * Fused x_proj -> dt_proj of the mixer on the matrix cores (the two skinny GEMMs between the conv and the scan
@@ -220,7 +255,9 @@ int simamba_seq_gather_bwd(const void* dout, const int* inv, void* din, int batc
 /*
  * Causal depthwise conv1d (+ optional SiLU).
  *   x, out, dout, dx : (batch, dim, seqlen) io_dtype
- *   w : (dim, width) fp32; bias : (dim) fp32 or NULL; dw, dbias fp32, zeroed then accumulated.
+ *   w : (dim, width) fp32; bias : (dim) fp32 or NULL; dw, dbias fp32, zeroed then accumulated (float atomics:
+ *   last-bit run-to-run jitter; the _ex form with SIMAMBA_BWD_DETERMINISTIC writes them whole, bitwise reproducible,
+ *   from per-workgroup partials in `workspace`, contract as simamba_selective_scan_bwd_ex).
  *   out[b,d,t] = act(bias[d] + sum_k w[d,k] * x[b,d,t-(width-1)+k])
  *   x_bstride / dx_bstride: elements between batch samples of x / dx (0 => dim*seqlen).
  */
@@ -231,6 +268,12 @@ int simamba_causal_conv1d_bwd(const void* x, const float* w, const float* bias,
                               const void* dout, void* dx, float* dw, float* dbias,
                               int batch, int dim, int seqlen, int width, int silu,
                               int io_dtype, long long x_bstride, long long dx_bstride, void* stream);
+long long simamba_causal_conv1d_bwd_workspace_floats(int batch, int dim, int seqlen, int width, int flags);
+int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const float* bias,
+                                 const void* dout, void* dx, float* dw, float* dbias,
+                                 int batch, int dim, int seqlen, int width, int silu,
+                                 int io_dtype, long long x_bstride, long long dx_bstride, int flags,
+                                 float* workspace, long long workspace_floats, void* stream);
 
 /*
  * Fused (DropPath-scaled) residual add + LayerNorm: the "Add -> LayerNorm" half of the reference's

@@ -9,6 +9,7 @@ from .mamba_simple import Mamba
 from .block import Block, MixerModel, create_block, DropPath
 from . import spectral
 from .shim import install_shim
+from ._lib import deterministic, deterministic_enabled, set_deterministic
 
 __all__ = ["causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
-           "DropPath", "spectral", "install_shim"]
+           "DropPath", "spectral", "install_shim", "deterministic", "deterministic_enabled", "set_deterministic"]

@@ -26,6 +26,8 @@ SPEC_SIGMA_MEAN = 0x20
 SCAN_AUTO, SCAN_ROWSCAN, SCAN_LPC2, SCAN_LPC4, SCAN_MIX = 0, 1, 2, 4, 6
 # checkpoint layouts handed from the forward scan to the backward (= which backward kernel runs)
 CKPT_ROW, CKPT_SEQ = 128, 16
+# flags of the *_ex backward entry points: no float atomics, bitwise reproducible parameter gradients
+BWD_DETERMINISTIC = 1
 
 # name -> (restype, argtypes); mirrors include/simamba.h one to one
 _P = c_void_p
@@ -45,6 +47,11 @@ SIGNATURES = {
                                            _P, _P, _P, _P, _P, _P, _P, _P,
                                            c_int, c_int, c_int, c_int, c_int, c_int,
                                            _LL, _LL, _LL, _LL, _LL, c_int, _P]),
+    "simamba_scan_bwd_workspace_floats": (_LL, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "simamba_selective_scan_bwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              _P, _P, _P, _P, _P, _P, _P, _P,
+                                              c_int, c_int, c_int, c_int, c_int, c_int,
+                                              _LL, _LL, _LL, _LL, _LL, c_int, c_int, _P, _LL, _P]),
     "simamba_selective_scan_dt_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                               c_int, c_int, c_int, c_int, c_int, c_int,
                                               _LL, _LL, _LL, c_int, c_int, _P]),
@@ -52,6 +59,10 @@ SIGNATURES = {
                                               _P, _P, _P, _P, _P, _P, _P, _P,
                                               c_int, c_int, c_int, c_int, c_int, c_int,
                                               _LL, _LL, _LL, _LL, _P]),
+    "simamba_selective_scan_dt_bwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                 _P, _P, _P, _P, _P, _P, _P, _P,
+                                                 c_int, c_int, c_int, c_int, c_int, c_int,
+                                                 _LL, _LL, _LL, _LL, c_int, _P, _LL, _P]),
     "simamba_xdt_proj_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _LL, _P]),
     "simamba_conv_xdt_proj_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _LL,
                                           _P]),
@@ -60,6 +71,9 @@ SIGNATURES = {
     "simamba_causal_conv1d_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _LL, _P]),
     "simamba_causal_conv1d_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P,
                                           c_int, c_int, c_int, c_int, c_int, c_int, _LL, _LL, _P]),
+    "simamba_causal_conv1d_bwd_workspace_floats": (_LL, [c_int, c_int, c_int, c_int, c_int]),
+    "simamba_causal_conv1d_bwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P,
+                                             c_int, c_int, c_int, c_int, c_int, c_int, _LL, _LL, c_int, _P, _LL, _P]),
     "simamba_add_layer_norm_grid": (c_int, [c_int, c_int]),
     "simamba_add_layer_norm_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float,
                                            c_int, c_int, _P]),
@@ -359,3 +373,49 @@ def scan_bwd_accumulators(batch, dim, seqlen, dstate, has_D, has_bias, device):
     dB = parts[1].view(batch, dstate, seqlen)
     dC = parts[2].view(batch, dstate, seqlen)
     return dA, dB, dC, (parts[3] if has_D else None), (parts[4] if has_bias else None)
+
+
+# ---- deterministic backward ------------------------------------------------------------------------------------------
+_deterministic = [None]   # None: follow torch.are_deterministic_algorithms_enabled(); True / False: forced
+
+
+def set_deterministic(on):
+    """Deterministic backward of the scan and conv1d kernels (SIMAMBA_BWD_DETERMINISTIC: per-workgroup partials and a
+    fixed-order sum instead of float atomics; bitwise reproducible gradients).  ``True`` / ``False`` force it on / off,
+    ``None`` (the default) follows ``torch.use_deterministic_algorithms``.  ``torch.backends.cudnn.deterministic`` is
+    not consulted."""
+    _deterministic[0] = None if on is None else bool(on)
+
+
+class deterministic:
+    """Context manager form of set_deterministic: ``with deterministic(True): loss.backward()``."""
+
+    def __init__(self, on):
+        self.v, self.prev = (None if on is None else bool(on)), None
+
+    def __enter__(self):
+        self.prev, _deterministic[0] = _deterministic[0], self.v
+        return self
+
+    def __exit__(self, *exc):
+        _deterministic[0] = self.prev
+        return False
+
+
+def deterministic_enabled():
+    """True when the backward kernels run their deterministic form: the explicit override if one is set, else
+    torch.are_deterministic_algorithms_enabled()."""
+    if _deterministic[0] is not None:
+        return _deterministic[0]
+    import torch
+    return torch.are_deterministic_algorithms_enabled()
+
+
+def bwd_flags_workspace(n_floats, device):
+    """(flags, workspace or None, its size in floats) for an *_ex backward call; ``n_floats`` from the library's
+    *_workspace_floats() for BWD_DETERMINISTIC (a negative value is an argument error the call itself reports).  The
+    workspace comes from torch's caching allocator, so the route is captured by torch.cuda.graph like any other."""
+    import torch
+    if n_floats <= 0:
+        return BWD_DETERMINISTIC, None, 0
+    return BWD_DETERMINISTIC, torch.empty(n_floats, device=device, dtype=torch.float32), n_floats

@@ -48,12 +48,17 @@ class CausalConv1dFn(torch.autograd.Function):
         dx = torch.empty(batch, dim, L, device=xc.device, dtype=xc.dtype)
         dw = torch.empty_like(wc)
         db = torch.empty(dim, device=xc.device, dtype=torch.float32) if bc is not None else None
+        flags, ws, nws = 0, None, 0
+        if _lib.deterministic_enabled():            # partials + fixed-order sum instead of float atomics
+            flags, ws, nws = _lib.bwd_flags_workspace(
+                lib.simamba_causal_conv1d_bwd_workspace_floats(batch, dim, L, W, _lib.BWD_DETERMINISTIC), xc.device)
+        _lib.count("conv1d_bwd_det" if flags else "conv1d_bwd_atomic")
         with torch.cuda.device(xc.device), _lib.timed("conv1d_bwd", xc.device):
-            rc = lib.simamba_causal_conv1d_bwd(_lib.ptr(xc), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(dout),
-                                               _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
-                                               batch, dim, L, W, ctx.silu, _lib.dtype_code(xc.dtype),
-                                               xc.stride(0), 0, _lib.stream_ptr(xc.device))
-        _lib.check(rc, "simamba_causal_conv1d_bwd")
+            rc = lib.simamba_causal_conv1d_bwd_ex(_lib.ptr(xc), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(dout),
+                                                  _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                                  batch, dim, L, W, ctx.silu, _lib.dtype_code(xc.dtype),
+                                                  xc.stride(0), 0, flags, _lib.ptr(ws), nws, _lib.stream_ptr(xc.device))
+        _lib.check(rc, "simamba_causal_conv1d_bwd_ex")
         return dx, dw.to(ctx.w_dtype), None if db is None else db.to(ctx.b_dtype), None
 
 

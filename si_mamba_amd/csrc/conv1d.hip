@@ -7,8 +7,12 @@
 // slice of the batch, so the weight-gradient reduction over (batch, time) happens in registers,
 // then over the 16-lane DPP row, then in LDS, and only one atomic per (channel, tap) and
 // workgroup reaches HBM.
+// Deterministic form (kDet, SIMAMBA_BWD_DETERMINISTIC): the 16-lane rows park their sums in LDS slots of their own, one
+// thread per (channel, tap) adds a channel's slots in index order, and the workgroup STORES that partial to the
+// workspace, [batch slice][dim][width] (dw) and [batch slice][dim] (dbias); det_reduce.hip sums over the slices.
 // Algorithmic HBM bytes: fwd 2*B*D*L*s, bwd 3*B*D*L*s (+ (W+1)*D*4 parameters).
 #include "common.h"
+#include "det_reduce.h"
 
 namespace simamba {
 
@@ -88,12 +92,38 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_fwd_kernel(ConvArgs p) {
   }
 }
 
+template <bool kDet = false>
 __device__ __forceinline__ void conv_bwd_reduce(const ConvArgs& p, float (&sacc)[16][5], float (&gw)[4], float gb, int drow,
                                                 int rows_per_blk, bool dvalid) {
   // 16-lane rows never straddle channels (ppr is a multiple of 16)
 #pragma unroll
   for (int j = 0; j < 4; ++j) gw[j] = row_allreduce_sum(gw[j]);
   gb = row_allreduce_sum(gb);
+  if (kDet) {
+    // sacc[16-lane row][tap]: a slot per row, no atomics; channel r owns rows r * rpc .. r * rpc + rpc - 1
+    const int q = threadIdx.x >> 4, rpc = 16 / rows_per_blk;
+    if ((threadIdx.x & 15) == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sacc[q][j] = gw[j];
+      sacc[q][4] = gb;
+    }
+    __syncthreads();
+    if (threadIdx.x < rows_per_blk * 5) {
+      const int r = threadIdx.x / 5, j = threadIdx.x % 5;
+      const int dd = blockIdx.x * rows_per_blk + r;
+      if (dd < p.dim) {
+        float v = 0.f;
+        for (int i = 0; i < rpc; ++i) v += sacc[r * rpc + i][j];
+        if (j < 4) {
+          const int k = j - (4 - p.width);
+          if (k >= 0) p.dw[(static_cast<size_t>(blockIdx.y) * p.dim + dd) * p.width + k] = v;
+        } else if (p.dbias) {
+          p.dbias[static_cast<size_t>(blockIdx.y) * p.dim + dd] = v;
+        }
+      }
+    }
+    return;
+  }
   if ((threadIdx.x & 15) == 0 && dvalid) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) atomicAdd(&sacc[drow][j], gw[j]);
@@ -117,7 +147,7 @@ __device__ __forceinline__ void conv_bwd_reduce(const ConvArgs& p, float (&sacc)
 
 // P: timesteps per lane and step -- one 16-byte access: 4 for fp32, 8 for bf16 (with 4 the bf16 kernel issued twice the
 // loads and recomputed 7 SiLU derivatives per 4 outputs instead of 11 per 8: 120 us where its bytes take 55)
-template <typename T, int P>
+template <typename T, int P, bool kDet = false>
 __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_kernel(ConvArgs p) {
   __shared__ float sacc[16][5];   // up to 16 channels per workgroup x (4 taps + bias)
   const int L = p.seqlen, D = p.dim;
@@ -183,7 +213,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_kernel(ConvArgs p) {
       if (dvalid) store_items<T, P>(dxg + doff + t0, L - t0, vec, dx);
     }
   }
-  conv_bwd_reduce(p, sacc, gw, gb, drow, rows_per_blk, dvalid);
+  conv_bwd_reduce<kDet>(p, sacc, gw, gb, drow, rows_per_blk, dvalid);
 }
 
 // ---- the aligned case (every pack one whole 16-byte access, L % P == 0): same arithmetic, software-pipelined ----------
@@ -206,7 +236,7 @@ __device__ __forceinline__ void unpack16(const uint4& r, float (&v)[P]) {
   }
 }
 
-template <typename T, int P>
+template <typename T, int P, bool kDet = false>
 __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_fast_kernel(ConvArgs p) {
   static_assert(sizeof(T) * P == 16, "one 16-byte access per pack");
   __shared__ float sacc[16][5];
@@ -302,7 +332,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_fast_kernel(ConvArgs 
       cur = nxt;
     }
   }
-  conv_bwd_reduce(p, sacc, gw, gb, drow, rows_per_blk, dvalid);
+  conv_bwd_reduce<kDet>(p, sacc, gw, gb, drow, rows_per_blk, dvalid);
 }
 
 static int fill_common(ConvArgs& a, int io_dtype, int pack = kPack) {
@@ -358,21 +388,54 @@ extern "C" int simamba_causal_conv1d_fwd(const void* x, const float* w, const fl
   return static_cast<int>(hipGetLastError());
 }
 
-extern "C" int simamba_causal_conv1d_bwd(const void* x, const float* w, const float* bias, const void* dout,
-                                         void* dx, float* dw, float* dbias, int batch, int dim, int seqlen,
-                                         int width, int silu, int io_dtype, long long x_bstride,
-                                         long long dx_bstride, void* stream) {
+// Deterministic form: workspace of the per-batch-slice partials (det_layout), in floats; the slicing depends on the
+// I/O type's pack, the size asked for covers both.
+static long long conv_det_slices(int batch, int dim, int seqlen, int io_dtype) {
+  ConvArgs a{};
+  a.batch = batch; a.dim = dim; a.seqlen = seqlen;
+  fill_common(a, io_dtype, io_dtype == SIMAMBA_F32 ? 4 : 8);
+  return (batch + a.bchunk - 1) / a.bchunk;
+}
+static long long conv_det_dw_floats(long long slices, int dim, int width) {
+  return (slices * dim * width + 63) & ~63ll;                 // dbias partials start on a 256-byte boundary
+}
+
+extern "C" long long simamba_causal_conv1d_bwd_workspace_floats(int batch, int dim, int seqlen, int width, int flags) {
+  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  if (!flags) return 0;
+  if (batch < 0 || dim <= 0 || seqlen < 0) return SIMAMBA_E_SHAPE;
+  if (width < 2 || width > 4) return SIMAMBA_E_WIDTH;
+  if (batch == 0 || seqlen == 0) return 0;
+  const long long s4 = conv_det_slices(batch, dim, seqlen, SIMAMBA_F32), s8 = conv_det_slices(batch, dim, seqlen, SIMAMBA_BF16);
+  const long long sl = s4 > s8 ? s4 : s8;
+  return conv_det_dw_floats(sl, dim, width) + sl * dim;
+}
+
+extern "C" int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const float* bias, const void* dout,
+                                            void* dx, float* dw, float* dbias, int batch, int dim, int seqlen,
+                                            int width, int silu, int io_dtype, long long x_bstride,
+                                            long long dx_bstride, int flags, float* workspace,
+                                            long long workspace_floats, void* stream) {
+  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  const bool det = flags != 0;
   int rc = check_conv(x, w, batch, dim, seqlen, width, io_dtype);
   if (rc) return rc;
   if (!dout || !dx || !dw) return SIMAMBA_E_NULLPTR;
+  if (det && simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags) > 0 &&
+      (!workspace || workspace_floats < simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags)))
+    return SIMAMBA_E_WORKSPACE;
+  if (det && !al16(workspace)) return SIMAMBA_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the two accumulators are zeroed here; a caller that carves dbias directly behind dw gets one memset node
-  const bool joined = dbias == dw + static_cast<size_t>(dim) * width;
-  hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (static_cast<size_t>(dim) * width + (joined ? dim : 0)), s);
-  if (e != hipSuccess) return static_cast<int>(e);
-  if (dbias && !joined) {
-    e = hipMemsetAsync(dbias, 0, sizeof(float) * dim, s);
+  // (the deterministic form writes them whole in its sum pass: nothing to clear but for an empty problem)
+  if (!det || batch == 0 || seqlen == 0) {
+    const bool joined = dbias == dw + static_cast<size_t>(dim) * width;
+    hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (static_cast<size_t>(dim) * width + (joined ? dim : 0)), s);
     if (e != hipSuccess) return static_cast<int>(e);
+    if (dbias && !joined) {
+      e = hipMemsetAsync(dbias, 0, sizeof(float) * dim, s);
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
   }
   if (batch == 0 || seqlen == 0) return SIMAMBA_OK;
   ConvArgs a{};
@@ -385,6 +448,23 @@ extern "C" int simamba_causal_conv1d_bwd(const void* x, const float* w, const fl
   a.vec = a.vec && al16(x) && al16(dx) && al16(dout) && (a.x_bs * esz_) % 16 == 0 && (a.o_bs * esz_) % 16 == 0;
   dim3 grid(dblocks, (batch + a.bchunk - 1) / a.bchunk);
   const bool fast = a.vec && seqlen % (io_dtype == SIMAMBA_F32 ? 4 : 8) == 0;
+  if (det) {                                                 // partials in place of the accumulators
+    a.dw = workspace;
+    a.dbias = dbias ? workspace + conv_det_dw_floats(grid.y, dim, width) : nullptr;
+    if (io_dtype == SIMAMBA_F32) {
+      if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<float, 4, true>), grid, dim3(kConvThreads), 0, s, a);
+      else hipLaunchKernelGGL((conv1d_bwd_kernel<float, 4, true>), grid, dim3(kConvThreads), 0, s, a);
+    } else {
+      if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<bf16_t, 8, true>), grid, dim3(kConvThreads), 0, s, a);
+      else hipLaunchKernelGGL((conv1d_bwd_kernel<bf16_t, 8, true>), grid, dim3(kConvThreads), 0, s, a);
+    }
+    const int e = static_cast<int>(hipGetLastError());
+    if (e) return e;
+    DetSumJob jobs[2] = {{a.dw, dw, static_cast<long long>(dim) * width, static_cast<long long>(dim) * width,
+                          static_cast<int>(grid.y)},
+                         {a.dbias, dbias, dim, dim, static_cast<int>(grid.y)}};
+    return det_sum_launch(jobs, dbias ? 2 : 1, s);
+  }
   if (io_dtype == SIMAMBA_F32) {
     if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<float, 4>), grid, dim3(kConvThreads), 0, s, a);
     else hipLaunchKernelGGL((conv1d_bwd_kernel<float, 4>), grid, dim3(kConvThreads), 0, s, a);
@@ -393,4 +473,12 @@ extern "C" int simamba_causal_conv1d_bwd(const void* x, const float* w, const fl
     else hipLaunchKernelGGL((conv1d_bwd_kernel<bf16_t, 8>), grid, dim3(kConvThreads), 0, s, a);
   }
   return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_causal_conv1d_bwd(const void* x, const float* w, const float* bias, const void* dout,
+                                         void* dx, float* dw, float* dbias, int batch, int dim, int seqlen,
+                                         int width, int silu, int io_dtype, long long x_bstride,
+                                         long long dx_bstride, void* stream) {
+  return simamba_causal_conv1d_bwd_ex(x, w, bias, dout, dx, dw, dbias, batch, dim, seqlen, width, silu, io_dtype,
+                                      x_bstride, dx_bstride, 0, nullptr, 0, stream);
 }

@@ -9,12 +9,18 @@
 //           16*R channels -> one coalesced float-atomic flush per workgroup and chunk;
 //   dA, dD, ddelta_bias (sum over time and batch): DPP row all-reduce -> one atomic per row.
 // Algorithmic HBM bytes: 7*B*D*L*s + 2*B*N*L*(s+4) + small.
+//
+// Deterministic form (kDet, SIMAMBA_BWD_DETERMINISTIC): the same kernel with plain stores of partials instead of the
+// atomics; the accumulator pointers then point into the caller's workspace (det_layout below): dB | dC per workgroup
+// column into the slab [group][tensor][batch][N][L] (p.dC = p.dB + batch * N * L), dA / dD / ddelta_bias per (chunk,
+// sample, row).  det_reduce.hip sums them in a fixed order.
 #include "scan_common.h"
 #include "scan_xlane.h"
+#include "det_reduce.h"
 
 namespace simamba {
 
-template <typename T, int kItems>
+template <typename T, int kItems, bool kDet = false>
 __global__ __launch_bounds__(kScanThreads, 2) void scan_bwd_kernel(ScanArgs p) {
   constexpr int LC = 16 * kItems;
   constexpr int LDP = LC + 4;
@@ -218,7 +224,12 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_bwd_kernel(ScanArgs p) {
       }
       sD = row_allreduce_sum(sD);
       sBias = row_allreduce_sum(sBias);
-      if (dvalid) {
+      if (kDet && dvalid) {
+        const size_t pr = (static_cast<size_t>(c) * p.batch + b) * D + d;
+        if (lane16 < N) p.dA[pr * N + lane16] = dAlane;
+        if (lane16 == 0 && p.dD) p.dD[pr] = sD;
+        if (lane16 == 1 && p.ddelta_bias) p.ddelta_bias[pr] = sBias;
+      } else if (dvalid) {
         if (lane16 < N) atomicAdd(&p.dA[static_cast<size_t>(d) * N + lane16], dAlane);
         if (lane16 == 0 && p.dD) atomicAdd(&p.dD[d], sD);
         if (lane16 == 1 && p.ddelta_bias) atomicAdd(&p.ddelta_bias[d], sBias);
@@ -250,8 +261,14 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_bwd_kernel(ScanArgs p) {
       const int n = rem / LC, t = rem - n * LC;
       const int gt = c * LC + t;
       if (gt < L) {
-        float* dst = (tensor == 0 ? p.dB : p.dC) + (static_cast<size_t>(b) * N + n) * L + gt;
-        atomicAdd(dst, sAcc[(tensor * kMaxState + n) * LC + t]);
+        if (kDet) {
+          float* dst = (tensor == 0 ? p.dB : p.dC) + static_cast<size_t>(tile_id) * 2 * p.batch * N * L +
+                       (static_cast<size_t>(b) * N + n) * L + gt;
+          *dst = sAcc[(tensor * kMaxState + n) * LC + t];
+        } else {
+          float* dst = (tensor == 0 ? p.dB : p.dC) + (static_cast<size_t>(b) * N + n) * L + gt;
+          atomicAdd(dst, sAcc[(tensor * kMaxState + n) * LC + t]);
+        }
       }
     }
   }
@@ -264,8 +281,15 @@ static size_t bwd_smem_bytes(int kItems, int passes) {
 }
 
 template <typename T>
-static int launch_bwd(const ScanArgs& a, hipStream_t s) {
+static int launch_bwd(const ScanArgs& a, hipStream_t s, bool det) {
   dim3 grid((a.dim + kRowsPerPass * a.passes - 1) / (kRowsPerPass * a.passes), a.batch);
+  if (det) {
+    if (a.seqlen <= 64)
+      hipLaunchKernelGGL((scan_bwd_kernel<T, 4, true>), grid, dim3(kScanThreads), bwd_smem_bytes(4, a.passes), s, a);
+    else
+      hipLaunchKernelGGL((scan_bwd_kernel<T, 8, true>), grid, dim3(kScanThreads), bwd_smem_bytes(8, a.passes), s, a);
+    return static_cast<int>(hipGetLastError());
+  }
   if (a.seqlen <= 64) {
     hipLaunchKernelGGL((scan_bwd_kernel<T, 4>), grid, dim3(kScanThreads), bwd_smem_bytes(4, a.passes), s, a);
   } else {
@@ -277,15 +301,79 @@ static int launch_bwd(const ScanArgs& a, hipStream_t s) {
 struct BwdSeqArgs;
 bool scan_bwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, int vec, long long z_bs, long long dz_bs,
                      bool has_z, int bc_mode, long long bc_ns, long long bc_ts);
-int scan_bwd_seq_dispatch(const ScanArgs& a, int io_dtype, int bc_mode, hipStream_t s, const void* dt = nullptr,
-                          const void* wdt = nullptr, long long dt_bs = 0, long long dt_ts = 0, int dt_rank = 0);
+int scan_bwd_seq_dispatch(const ScanArgs& a, int io_dtype, int bc_mode, hipStream_t s, const void* dt, const void* wdt,
+                          long long dt_bs, long long dt_ts, int dt_rank, bool det);
 int scan_fwd_seq_bc_mode(const void* B, const void* C, int io_dtype, long long bc_bs, long long bc_ns, long long bc_ts);
+
+// channels per workgroup of the row-scan backward = 16 * passes (the more, the fewer dB/dC atomics reach HBM; measured
+// at (64,768,1024,16): 134 MB of flush traffic at passes = 3, 18 % on top of the 604 MB of gradient stores); but keep
+// >= 2 workgroups per CU, the number resident at this kernel's register footprint.
+static int bwd_passes(int batch, int dim) {
+  static const int kCand[] = {12, 8, 6, 4, 3, 2, 1};
+  for (int cand : kCand) {
+    if (static_cast<long long>(batch) * ((dim + 16 * cand - 1) / (16 * cand)) >= 512) return cand;
+  }
+  return 1;
+}
+
+// Workspace of the deterministic backward, in floats; every region starts on a 256-byte boundary.
+//   bc   dB | dC partials: [groups][2][batch][dstate][seqlen] (groups = workgroup columns of the launch)
+//   a    dA partials:      [K][dim][dstate]   K = batch (sequential kernel) or nchunks * batch (row scan)
+//   d    dD partials:      [K][dim]
+//   bias ddelta_bias partials: [K][dim]
+constexpr int kSeqBwdChannels = 64;         // channels per workgroup of scan_bwd_seq_kernel (kBsCh)
+struct DetLayout { long long bc, a, d, bias, total; int groups, K; };
+static long long round64(long long n) { return (n + 63) & ~63ll; }
+static DetLayout det_layout(int batch, int dim, int seqlen, int dstate, int ckpt_step) {
+  DetLayout l{};
+  if (ckpt_step == SIMAMBA_SCAN_CKPT_SEQ) {
+    l.groups = (dim + kSeqBwdChannels - 1) / kSeqBwdChannels;
+    l.K = batch;
+  } else {
+    const int passes = bwd_passes(batch, dim);
+    l.groups = (dim + kRowsPerPass * passes - 1) / (kRowsPerPass * passes);
+    l.K = simamba_scan_num_chunks(seqlen) * batch;
+  }
+  const long long part = static_cast<long long>(l.K) * dim;
+  l.bc = 0;
+  l.a = round64(2ll * l.groups * batch * dstate * seqlen);
+  l.d = l.a + round64(part * dstate);
+  l.bias = l.d + round64(part);
+  l.total = l.bias + round64(part);
+  return l;
+}
 
 }  // namespace simamba
 
 using namespace simamba;
 
+extern "C" long long simamba_scan_bwd_workspace_floats(int batch, int dim, int seqlen, int dstate, int ckpt_step,
+                                                       int flags) {
+  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  if (!flags) return 0;
+  if (batch < 0 || dim <= 0 || seqlen < 0 || batch > 65535) return SIMAMBA_E_SHAPE;
+  if (dstate < 1 || dstate > kMaxState) return SIMAMBA_E_DSTATE;
+  if (ckpt_step == 0) ckpt_step = SIMAMBA_SCAN_CKPT_ROW;
+  if (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) return SIMAMBA_E_VARIANT;
+  return det_layout(batch, dim, seqlen, dstate, ckpt_step).total;
+}
+
 static bool aligned16b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// the fixed-order sum pass of the deterministic form: partials (a.dA ... in the workspace) -> the caller's spans
+static int scan_det_sum(const DetLayout& wl, const ScanArgs& a, float* dA, float* dB, float* dC, float* dD,
+                        float* ddelta_bias, hipStream_t s) {
+  const long long bnl = static_cast<long long>(a.batch) * a.dstate * a.seqlen;
+  const long long part = static_cast<long long>(a.dim);
+  DetSumJob jobs[5];
+  int n = 0;
+  jobs[n++] = DetSumJob{a.dB, dB, 2 * bnl, bnl, wl.groups};
+  jobs[n++] = DetSumJob{a.dC, dC, 2 * bnl, bnl, wl.groups};
+  jobs[n++] = DetSumJob{a.dA, dA, part * a.dstate, part * a.dstate, wl.K};
+  if (dD) jobs[n++] = DetSumJob{a.dD, dD, part, part, wl.K};
+  if (ddelta_bias) jobs[n++] = DetSumJob{a.ddelta_bias, ddelta_bias, part, part, wl.K};
+  return det_sum_launch(jobs, n, s);
+}
 
 // dt != NULL: delta is formed inside the (sequential) kernel from the x_proj output; `delta` is then NULL
 static int scan_bwd_impl(const void* u, const void* delta, const float* A, const void* B,
@@ -296,7 +384,10 @@ static int scan_bwd_impl(const void* u, const void* delta, const float* A, const
                          int dstate, int io_dtype, int delta_softplus, long long z_bstride,
                          long long dz_bstride, long long bc_bstride, long long bc_nstride,
                          long long bc_tstride, int ckpt_step, void* stream, const void* dt, const void* wdt,
-                         long long dt_bs, long long dt_ts, int dt_rank) {
+                         long long dt_bs, long long dt_ts, int dt_rank, int flags, float* workspace,
+                         long long workspace_floats) {
+  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  const bool det = flags != 0;
   if (batch < 0 || dim <= 0 || seqlen < 0 || batch > 65535) return SIMAMBA_E_SHAPE;
   if (ckpt_step == 0) ckpt_step = SIMAMBA_SCAN_CKPT_ROW;
   if (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) return SIMAMBA_E_VARIANT;
@@ -309,13 +400,17 @@ static int scan_bwd_impl(const void* u, const void* delta, const float* A, const
   }
   const int nchunks = simamba_scan_num_chunks(seqlen);
   if (ckpt_step == SIMAMBA_SCAN_CKPT_SEQ ? (seqlen > 16 && !x_ckpt) : (nchunks > 1 && !x_ckpt)) return SIMAMBA_E_NULLPTR;
+  const DetLayout wl = det_layout(batch, dim, seqlen, dstate, ckpt_step);
+  if (det && wl.total > 0 && (!workspace || workspace_floats < wl.total)) return SIMAMBA_E_WORKSPACE;
+  if (det && (reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return SIMAMBA_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e;
   // The five accumulators are zeroed here (the kernel adds into them).  Never a byte outside the five spans:
   // spans that are EXACTLY adjacent in memory (the next one starts where the previous one ends; the Python
   // callers carve them that way out of one allocation) are merged into one memset node, anything else --
   // separately allocated buffers, with whatever lives between them -- gets a memset of its own.
-  {
+  // The deterministic form's sum pass writes the five spans whole: nothing to clear there (but for an empty problem).
+  if (!det || batch == 0 || seqlen == 0) {
     const size_t bc = sizeof(float) * static_cast<size_t>(batch) * dstate * seqlen;
     struct Span { char* p; size_t n; } sp[5] = {{reinterpret_cast<char*>(dA), sizeof(float) * dim * dstate},
                                                  {reinterpret_cast<char*>(dB), bc},
@@ -341,6 +436,13 @@ static int scan_bwd_impl(const void* u, const void* delta, const float* A, const
   a.dout = dout; a.x_ckpt = const_cast<float*>(x_ckpt);
   a.du = du; a.ddelta = ddelta; a.dA = dA; a.dB = dB; a.dC = dC; a.dD = dD; a.dz = dz;
   a.ddelta_bias = ddelta_bias;
+  if (det) {                                                 // the kernels store partials; the sum pass below adds them up
+    a.dB = workspace + wl.bc;
+    a.dC = a.dB + static_cast<size_t>(batch) * dstate * seqlen;
+    a.dA = workspace + wl.a;
+    a.dD = dD ? workspace + wl.d : nullptr;
+    a.ddelta_bias = ddelta_bias ? workspace + wl.bias : nullptr;
+  }
   a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.dstate = dstate;
   a.nchunks = nchunks;
   a.softplus = delta_softplus;
@@ -360,19 +462,28 @@ static int scan_bwd_impl(const void* u, const void* delta, const float* A, const
                          a.bc_ns, a.bc_ts) ||
         (reinterpret_cast<uintptr_t>(A) & 15u) != 0 || (x_ckpt && (reinterpret_cast<uintptr_t>(x_ckpt) & 15u) != 0))
       return SIMAMBA_E_VARIANT;
-    return scan_bwd_seq_dispatch(a, io_dtype, bc_mode, s, dt, wdt, dt_bs, dt_ts, dt_rank);
+    const int rc = scan_bwd_seq_dispatch(a, io_dtype, bc_mode, s, dt, wdt, dt_bs, dt_ts, dt_rank, det);
+    return (rc || !det) ? rc : scan_det_sum(wl, a, dA, dB, dC, dD, ddelta_bias, s);
   }
   if (dt) return SIMAMBA_E_VARIANT;                          // only the sequential kernel forms delta itself
-  // channels per workgroup (16 * passes): the more, the fewer dB/dC atomics reach HBM (measured at
-  // (64,768,1024,16): 134 MB of flush traffic at passes = 3, 18 % on top of the 604 MB of gradient stores);
-  // but keep >= 2 workgroups per CU, the number resident at this kernel's register footprint.
-  static const int kCand[] = {12, 8, 6, 4, 3, 2, 1};
-  int passes = 1;
-  for (int cand : kCand) {
-    if (static_cast<long long>(batch) * ((dim + 16 * cand - 1) / (16 * cand)) >= 512) { passes = cand; break; }
-  }
-  a.passes = passes;
-  return io_dtype == SIMAMBA_F32 ? launch_bwd<float>(a, s) : launch_bwd<bf16_t>(a, s);
+  a.passes = bwd_passes(batch, dim);
+  const int rc = io_dtype == SIMAMBA_F32 ? launch_bwd<float>(a, s, det) : launch_bwd<bf16_t>(a, s, det);
+  return (rc || !det) ? rc : scan_det_sum(wl, a, dA, dB, dC, dD, ddelta_bias, s);
+}
+
+extern "C" int simamba_selective_scan_bwd_ex(const void* u, const void* delta, const float* A, const void* B,
+                                             const void* C, const float* D, const void* z,
+                                             const float* delta_bias, const void* dout, const float* x_ckpt,
+                                             void* du, void* ddelta, float* dA, float* dB, float* dC, float* dD,
+                                             void* dz, float* ddelta_bias, int batch, int dim, int seqlen,
+                                             int dstate, int io_dtype, int delta_softplus, long long z_bstride,
+                                             long long dz_bstride, long long bc_bstride, long long bc_nstride,
+                                             long long bc_tstride, int ckpt_step, int flags, float* workspace,
+                                             long long workspace_floats, void* stream) {
+  return scan_bwd_impl(u, delta, A, B, C, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD, dz, ddelta_bias,
+                       batch, dim, seqlen, dstate, io_dtype, delta_softplus, z_bstride, dz_bstride, bc_bstride,
+                       bc_nstride, bc_tstride, ckpt_step, stream, nullptr, nullptr, 0, 0, 0, flags, workspace,
+                       workspace_floats);
 }
 
 extern "C" int simamba_selective_scan_bwd(const void* u, const void* delta, const float* A, const void* B,
@@ -383,20 +494,23 @@ extern "C" int simamba_selective_scan_bwd(const void* u, const void* delta, cons
                                           int dstate, int io_dtype, int delta_softplus, long long z_bstride,
                                           long long dz_bstride, long long bc_bstride, long long bc_nstride,
                                           long long bc_tstride, int ckpt_step, void* stream) {
-  return scan_bwd_impl(u, delta, A, B, C, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD, dz, ddelta_bias,
-                       batch, dim, seqlen, dstate, io_dtype, delta_softplus, z_bstride, dz_bstride, bc_bstride,
-                       bc_nstride, bc_tstride, ckpt_step, stream, nullptr, nullptr, 0, 0, 0);
+  return simamba_selective_scan_bwd_ex(u, delta, A, B, C, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD,
+                                       dz, ddelta_bias, batch, dim, seqlen, dstate, io_dtype, delta_softplus,
+                                       z_bstride, dz_bstride, bc_bstride, bc_nstride, bc_tstride, ckpt_step, 0,
+                                       nullptr, 0, stream);
 }
 
 // Backward of simamba_selective_scan_dt_fwd: same operands (+ dout, the forward's 16-step checkpoints); ddelta is the
 // gradient with respect to the delta the kernels form (before bias and softplus), as in simamba_selective_scan_bwd.
-extern "C" int simamba_selective_scan_dt_bwd(const void* u, const void* xdbl, const void* wdt, const float* A,
-                                             const float* D, const void* z, const float* delta_bias, const void* dout,
-                                             const float* x_ckpt, void* du, void* ddelta, float* dA, float* dB,
-                                             float* dC, float* dD, void* dz, float* ddelta_bias, int batch, int dim,
-                                             int seqlen, int dstate, int dt_rank, int io_dtype, long long z_bstride,
-                                             long long dz_bstride, long long xdbl_bstride, long long xdbl_tstride,
-                                             void* stream) {
+extern "C" int simamba_selective_scan_dt_bwd_ex(const void* u, const void* xdbl, const void* wdt, const float* A,
+                                                const float* D, const void* z, const float* delta_bias,
+                                                const void* dout, const float* x_ckpt, void* du, void* ddelta,
+                                                float* dA, float* dB, float* dC, float* dD, void* dz,
+                                                float* ddelta_bias, int batch, int dim, int seqlen, int dstate,
+                                                int dt_rank, int io_dtype, long long z_bstride, long long dz_bstride,
+                                                long long xdbl_bstride, long long xdbl_tstride, int flags,
+                                                float* workspace, long long workspace_floats, void* stream) {
+  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
   if (dstate != kMaxState) return SIMAMBA_E_DSTATE;
   if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
   const int pack = io_dtype == SIMAMBA_F32 ? 4 : 8;
@@ -412,5 +526,17 @@ extern "C" int simamba_selective_scan_dt_bwd(const void* u, const void* xdbl, co
   const char* Cp = Bp + kMaxState * esz;
   return scan_bwd_impl(u, nullptr, A, Bp, Cp, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD, dz,
                        ddelta_bias, batch, dim, seqlen, dstate, io_dtype, 1, z_bstride, dz_bstride, xb, 1, xt,
-                       SIMAMBA_SCAN_CKPT_SEQ, stream, xdbl, wdt, xb, xt, dt_rank);
+                       SIMAMBA_SCAN_CKPT_SEQ, stream, xdbl, wdt, xb, xt, dt_rank, flags, workspace, workspace_floats);
+}
+
+extern "C" int simamba_selective_scan_dt_bwd(const void* u, const void* xdbl, const void* wdt, const float* A,
+                                             const float* D, const void* z, const float* delta_bias, const void* dout,
+                                             const float* x_ckpt, void* du, void* ddelta, float* dA, float* dB,
+                                             float* dC, float* dD, void* dz, float* ddelta_bias, int batch, int dim,
+                                             int seqlen, int dstate, int dt_rank, int io_dtype, long long z_bstride,
+                                             long long dz_bstride, long long xdbl_bstride, long long xdbl_tstride,
+                                             void* stream) {
+  return simamba_selective_scan_dt_bwd_ex(u, xdbl, wdt, A, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD,
+                                          dz, ddelta_bias, batch, dim, seqlen, dstate, dt_rank, io_dtype, z_bstride,
+                                          dz_bstride, xdbl_bstride, xdbl_tstride, 0, nullptr, 0, stream);
 }

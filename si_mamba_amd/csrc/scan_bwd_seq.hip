@@ -131,7 +131,12 @@ __device__ __forceinline__ void bs_quad_sum2(float& a, float& b) {
 using f32x4_t = __attribute__((ext_vector_type(4))) float;
 using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 
-template <typename T, bool kHasZ, bool kDt = false>
+// kDet: the deterministic form (SIMAMBA_BWD_DETERMINISTIC).  No float atomics: dA / dB / dC / dD / ddelta_bias then
+// point at the partial buffers of the caller's workspace (scan_bwd.hip, det_layout) and every workgroup STORES its
+// partials -- dB | dC into the slab [tile][tensor][batch][16][L] (p.dC = p.dB + batch * 16 * L), dA into (batch, dim, 16),
+// dD / ddelta_bias into (batch, dim); the per-row chunk sums of ddelta_bias add up in a wave-private LDS slot (the unused
+// padding column of the wave's tP tile: no LDS beyond the atomic form's), always by the same lane, in chunk order.  det_reduce.hip sums the partials in a fixed order into the destinations.
+template <typename T, bool kHasZ, bool kDt = false, bool kDet = false>
 __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_kernel(BwdSeqArgs p) {
   __shared__ __attribute__((aligned(16))) float smem[kBsSmemFloats];
   const int tid = threadIdx.x;
@@ -166,6 +171,10 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
   // element f of a dB | dC row that this lane's finished sum belongs to (see the reduction below)
   const int pf = (r4 >> 1) * 16 + 4 * pq + 2 * (r4 & 1) + (cq >> 1);
   const float* ckl = p.ckpt + (static_cast<size_t>(b) * p.nck * D + dch) * kMaxState + 4 * pq;   // + block * D * 16
+  // kDet: ddelta_bias sums of the wave's 16 rows, row r at tDb[r * kBsPPitch] (column 32 of tP, never read or written
+  // by the dB | dC partials)
+  float* tDb = smem + wave * kBsWaveFloats + 4 * kBsTile + kBsTC;
+  if (kDet && lane < kBsR) tDb[lane * kBsPPitch] = 0.f;
 
   // ---- phase A / C identity: pack pk = lane + 64 j covers row pk / 8, steps 4 (pk % 8) .. + 4 ----------------
   // Phase B needs every register it can get for h (64) and its working set, so NOTHING of phases A / C lives through
@@ -526,7 +535,11 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
           dsum += dpp<DPP_QUAD_XOR1>(0.f, dsum);
           dsum += dpp<DPP_QUAD_XOR2>(0.f, dsum);
           dsum += dpp<DPP_ROW_HALF_MIRROR>(0.f, dsum);
-          if ((l & 7) == 0) atomicAdd(&p.ddelta_bias[d0w + (l >> 3) + 8 * j], dsum);
+          if (kDet) {
+            if ((l & 7) == 0) tDb[((l >> 3) + 8 * j) * kBsPPitch] += dsum;
+          } else {
+            if ((l & 7) == 0) atomicAdd(&p.ddelta_bias[d0w + (l >> 3) + 8 * j], dsum);
+          }
         }
       }
       // the next chunk's operands: requested here, where phase B's registers are free, behind this chunk's stores in the
@@ -556,14 +569,28 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
 #else
         if (t0 + t < L) {
 #endif
-          float* dst = ((f >> 4) ? p.dC : p.dB) + (static_cast<size_t>(b) * kMaxState + (f & 15)) * L + t0 + t;
-          atomicAdd(dst, v);
+          if (kDet) {
+            float* dst = ((f >> 4) ? p.dC : p.dB) + static_cast<size_t>(tile_id) * 2 * p.batch * kMaxState * L +
+                         (static_cast<size_t>(b) * kMaxState + (f & 15)) * L + t0 + t;
+            *dst = v;
+          } else {
+            float* dst = ((f >> 4) ? p.dC : p.dB) + (static_cast<size_t>(b) * kMaxState + (f & 15)) * L + t0 + t;
+            atomicAdd(dst, v);
+          }
         }
       }
     }
   }
 
   // ---- sums over time: one atomic per (channel, state) / channel and sample ---------------------------------
+  if (kDet) {                                                // ... or one partial per sample
+    const size_t row = static_cast<size_t>(b) * D + dch;
+    *reinterpret_cast<float4*>(p.dA + row * kMaxState + 4 * pq) = make_float4(dAacc[0], dAacc[1], dAacc[2], dAacc[3]);
+    if (p.dD && pq == 0) p.dD[row] = dDacc;
+    const int l = lane_now();                                // (the lane id is not kept live through phase B)
+    if (p.ddelta_bias && l < kBsR) p.ddelta_bias[static_cast<size_t>(b) * D + d0w + l] = tDb[l * kBsPPitch];
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < 4; ++j) atomicAdd(&p.dA[static_cast<size_t>(dch) * kMaxState + 4 * pq + j], dAacc[j]);
   if (p.dD && pq == 0) atomicAdd(&p.dD[dch], dDacc);
@@ -581,7 +608,7 @@ bool scan_bwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, i
 }
 
 int scan_bwd_seq_dispatch(const ScanArgs& sa, int io_dtype, int bc_mode, hipStream_t s, const void* dt, const void* wdt,
-                          long long dt_bs, long long dt_ts, int dt_rank) {
+                          long long dt_bs, long long dt_ts, int dt_rank, bool det) {
   BwdSeqArgs a{};
   a.u = sa.u; a.delta = sa.delta; a.z = sa.z; a.dout = sa.dout;
   a.du = sa.du; a.ddelta = sa.ddelta; a.dz = sa.dz;
@@ -593,6 +620,19 @@ int scan_bwd_seq_dispatch(const ScanArgs& sa, int io_dtype, int bc_mode, hipStre
   a.z_bs = sa.z_bs; a.dz_bs = sa.dz_bs; a.bc_bs = sa.bc_bs; a.bc_ns = sa.bc_ns; a.bc_ts = sa.bc_ts;
   a.dt = dt; a.wdt = wdt; a.dt_bs = dt_bs; a.dt_ts = dt_ts; a.dt_rank = dt_rank;
   dim3 grid(a.dim / kBsCh, a.batch);
+  if (det) {                                                 // partial buffers in place of the accumulators
+    if (a.dt) {
+      if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true, true, true>), grid, dim3(kBsThreads), 0, s, a);
+      else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true, true, true>), grid, dim3(kBsThreads), 0, s, a);
+    } else if (io_dtype == SIMAMBA_F32) {
+      if (a.z) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true, false, true>), grid, dim3(kBsThreads), 0, s, a);
+      else hipLaunchKernelGGL((scan_bwd_seq_kernel<float, false, false, true>), grid, dim3(kBsThreads), 0, s, a);
+    } else {
+      if (a.z) hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true, false, true>), grid, dim3(kBsThreads), 0, s, a);
+      else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, false, false, true>), grid, dim3(kBsThreads), 0, s, a);
+    }
+    return static_cast<int>(hipGetLastError());
+  }
   if (a.dt) {                                                // the mixer's form: gated, delta formed in the kernel
     if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true, true>), grid, dim3(kBsThreads), 0, s, a);
     else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true, true>), grid, dim3(kBsThreads), 0, s, a);

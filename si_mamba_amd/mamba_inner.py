@@ -284,22 +284,30 @@ class MambaInnerFn(torch.autograd.Function):
         dA, dB, dC, dD, dbias = _lib.scan_bwd_accumulators(Bsz, Dm, L, N, Df is not None, bf is not None, dev)
         Bv, Cv = x_dbl[:, :, R:R + N], x_dbl[:, :, R + N:]
         z, dz = xz[:, Dm:], dxz[:, Dm:]
+        det = _lib.deterministic_enabled()          # partials + fixed-order sums instead of float atomics
+        flags, ws, nws = 0, None, 0
+        if det:
+            flags, ws, nws = _lib.bwd_flags_workspace(
+                lib.simamba_scan_bwd_workspace_floats(Bsz, Dm, L, N, _lib.CKPT_SEQ if ctx.dtw_k is not None
+                                                      else ctx.ckpt_step, _lib.BWD_DETERMINISTIC), dev)
+        _lib.count("scan_bwd_det" if det else "scan_bwd_atomic")
         with torch.cuda.device(dev), _lib.timed("scan_bwd", dev):
             if ctx.dtw_k is not None:
-                rc = lib.simamba_selective_scan_dt_bwd(
+                rc = lib.simamba_selective_scan_dt_bwd_ex(
                     x_conv.data_ptr(), x_dbl.data_ptr(), ctx.dtw_k.data_ptr(), Af.data_ptr(), _lib.ptr(Df),
                     z.data_ptr(), _lib.ptr(bf), dy.data_ptr(), _lib.ptr(x_ckpt),
                     du.data_ptr(), ddelta.data_ptr(), dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), _lib.ptr(dD),
                     dz.data_ptr(), _lib.ptr(dbias), Bsz, Dm, L, N, R, code,
-                    xbs, dxz.stride(0), x_dbl.stride(0), x_dbl.stride(1), stream)
+                    xbs, dxz.stride(0), x_dbl.stride(0), x_dbl.stride(1), flags, _lib.ptr(ws), nws, stream)
             else:
-                rc = lib.simamba_selective_scan_bwd(
+                rc = lib.simamba_selective_scan_bwd_ex(
                     x_conv.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bv.data_ptr(), Cv.data_ptr(), _lib.ptr(Df),
                     z.data_ptr(), _lib.ptr(bf), dy.data_ptr(), _lib.ptr(x_ckpt),
                     du.data_ptr(), ddelta.data_ptr(), dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), _lib.ptr(dD),
                     dz.data_ptr(), _lib.ptr(dbias), Bsz, Dm, L, N, code, 1,
-                    xbs, dxz.stride(0), x_dbl.stride(0), 1, x_dbl.stride(1), ctx.ckpt_step, stream)
-        _lib.check(rc, "simamba_selective_scan_bwd")
+                    xbs, dxz.stride(0), x_dbl.stride(0), 1, x_dbl.stride(1), ctx.ckpt_step, flags, _lib.ptr(ws), nws,
+                    stream)
+        _lib.check(rc, "simamba_selective_scan_bwd_ex")
 
         # dt_proj / x_proj
         dx_dbl = torch.empty(Bsz, L, S, device=dev, dtype=io)
@@ -319,11 +327,17 @@ class MambaInnerFn(torch.autograd.Function):
         dconv = torch.empty(Dm * W + (Dm if cb is not None else 0), **f32)
         dcw = dconv[:Dm * W].view(Dm, W)
         dcb = dconv[Dm * W:] if cb is not None else None
+        flags, ws, nws = 0, None, 0
+        if det:
+            flags, ws, nws = _lib.bwd_flags_workspace(
+                lib.simamba_causal_conv1d_bwd_workspace_floats(Bsz, Dm, L, W, _lib.BWD_DETERMINISTIC), dev)
+        _lib.count("conv1d_bwd_det" if det else "conv1d_bwd_atomic")
         with torch.cuda.device(dev), _lib.timed("conv1d_bwd", dev):
-            rc = lib.simamba_causal_conv1d_bwd(xz.data_ptr(), cw.data_ptr(), _lib.ptr(cb), du.data_ptr(),
-                                               dxz.data_ptr(), dcw.data_ptr(), _lib.ptr(dcb),
-                                               Bsz, Dm, L, W, 1, code, xbs, dxz.stride(0), stream)
-        _lib.check(rc, "simamba_causal_conv1d_bwd")
+            rc = lib.simamba_causal_conv1d_bwd_ex(xz.data_ptr(), cw.data_ptr(), _lib.ptr(cb), du.data_ptr(),
+                                                  dxz.data_ptr(), dcw.data_ptr(), _lib.ptr(dcb),
+                                                  Bsz, Dm, L, W, 1, code, xbs, dxz.stride(0), flags, _lib.ptr(ws), nws,
+                                                  stream)
+        _lib.check(rc, "simamba_causal_conv1d_bwd_ex")
 
         t_cw, t_cb, t_xw, t_dtw, t_ow, t_A, t_D, t_b = ctx.param_dtypes
         return (dxz, dcw.to(t_cw), None if dcb is None else dcb.to(t_cb), d_x_w.to(t_xw), d_dt_w.to(t_dtw),

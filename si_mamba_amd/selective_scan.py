@@ -96,15 +96,21 @@ class SelectiveScanFn(torch.autograd.Function):
         dz = torch.empty_like(uc) if zc is not None else None
         dA, dB, dC, dD, dbias = _lib.scan_bwd_accumulators(batch, dim, L, N, Dc is not None, bc is not None,
                                                            uc.device)
+        flags, ws, nws = 0, None, 0
+        if _lib.deterministic_enabled():            # partials + fixed-order sum instead of float atomics
+            flags, ws, nws = _lib.bwd_flags_workspace(
+                lib.simamba_scan_bwd_workspace_floats(batch, dim, L, N, ctx.ckpt_step, _lib.BWD_DETERMINISTIC), uc.device)
+        _lib.count("scan_bwd_det" if flags else "scan_bwd_atomic")
         with torch.cuda.device(uc.device), _lib.timed("scan_bwd", uc.device):
-            rc = lib.simamba_selective_scan_bwd(
+            rc = lib.simamba_selective_scan_bwd_ex(
                 _lib.ptr(uc), _lib.ptr(dc), _lib.ptr(Ac), _lib.ptr(Bc), _lib.ptr(Cc), _lib.ptr(Dc),
                 _lib.ptr(zc), _lib.ptr(bc), _lib.ptr(dout), _lib.ptr(x_ckpt),
                 _lib.ptr(du), _lib.ptr(ddelta), _lib.ptr(dA), _lib.ptr(dB), _lib.ptr(dC), _lib.ptr(dD),
                 _lib.ptr(dz), _lib.ptr(dbias), batch, dim, L, N, _lib.dtype_code(io),
                 int(ctx.delta_softplus), 0 if zc is None else zc.stride(0), 0,
-                Bc.stride(0), Bc.stride(1), Bc.stride(2), ctx.ckpt_step, _lib.stream_ptr(uc.device))
-        _lib.check(rc, "simamba_selective_scan_bwd")
+                Bc.stride(0), Bc.stride(1), Bc.stride(2), ctx.ckpt_step, flags, _lib.ptr(ws), nws,
+                _lib.stream_ptr(uc.device))
+        _lib.check(rc, "simamba_selective_scan_bwd_ex")
         dt_delta, dt_B, dt_C, dt_D, dt_z, dt_bias, dt_A = ctx.in_dtypes
         dB = dB.to(dt_B)
         dC = dC.to(dt_C)
