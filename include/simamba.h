@@ -14,8 +14,9 @@
  *                                    same call site (inside the mixer).
  *   simamba_xdt_proj_fwd             the x_proj / dt_proj GEMM pair of the same mixer (cuBLAS calls inside
  *                                    upstream's mamba_inner_fn).
- *   simamba_add_layer_norm_fwd/bwd   the Add -> LayerNorm of models/block.py:56-60 (torch ops there).
- *   simamba_out_proj_add_ln_fwd      out_proj of the mixer + that Add -> LayerNorm, one kernel (bf16).
+ *   simamba_add_layer_norm_fwd/bwd   the Add -> LayerNorm of models/block.py:56-60 (torch ops there); the _ex
+ *                                    forms also take RMSNorm (mamba-ssm's Triton kernel upstream).
+ *   simamba_out_proj_add_ln_fwd      out_proj of the mixer + that Add -> LayerNorm (or RMSNorm), one kernel (bf16).
  *   simamba_in_proj_fwd              in_proj of the same mixer (a cuBLAS GEMM upstream), fp32 and bf16.
  *   simamba_selective_scan_dt_fwd/bwd  the scan with delta formed in the kernel (same call site, bf16 path).
  *   simamba_knn_graph                models/point_mamba.py:620-661 and :664-715
@@ -64,7 +65,9 @@ extern "C" {
 #define SIMAMBA_E_WORKSPACE  -6
 #define SIMAMBA_E_GROUPS     -7   /* G in [2,128], knn + 1 <= min(G,32), k (+1) <= G, F in [1,64] */
 #define SIMAMBA_E_ALIGN      -8
-#define SIMAMBA_E_VARIANT    -9   /* unknown forward-scan variant, or one the shape / alignment cannot take */
+#define SIMAMBA_E_VARIANT    -9   /* unknown forward-scan variant, or one the shape / alignment cannot take; unknown
+                                     flag bits */
+#define SIMAMBA_E_BIAS       -10  /* SIMAMBA_NORM_RMS with a bias / beta (RMSNorm has none: pass NULL) */
 
 /* timesteps per scan chunk; simamba_scan_num_chunks(L) = ceil(L / chunk) */
 #define SIMAMBA_SCAN_CHUNK 128
@@ -303,6 +306,26 @@ int simamba_add_layer_norm_bwd(const void* dnormed, const float* dresidual_out,
                                int dim, int hidden_dtype, int out_dtype, void* stream);
 
 /*
+ * Norm flags of the *_ex forms of the add + norm entry points (0 = LayerNorm: the plain entry point, bit for bit).
+ *   SIMAMBA_NORM_RMS: RMSNorm (mamba-ssm's RMSNorm, the reference's rms_norm=True: models/point_mamba.py:164, :227)
+ *   in place of LayerNorm:  rstd = 1 / sqrt(mean(x^2) + eps), normed = x * rstd * weight.  No mean, no bias:
+ *   bias / beta must be NULL (else SIMAMBA_E_BIAS); mean is neither read nor written and may be NULL.  Backward:
+ *   dresidual = rstd * (g - x^ * mean(g * x^)) + dresidual_out with x^ = x * rstd, g = dnormed * weight; dwb_partial
+ *   keeps its (grid, 2, dim) layout, row 0 of each partial = dweight, row 1 (dbias) unspecified (not written).
+ *   Unknown flag bits: SIMAMBA_E_VARIANT.  Both flag checks precede every other check.
+ */
+#define SIMAMBA_NORM_RMS 1
+int simamba_add_layer_norm_fwd_ex(const void* hidden, const float* residual, const float* rowscale,
+                                  const float* weight, const float* bias, float* residual_out,
+                                  void* normed, float* mean, float* rstd, int batch, int rows_per_batch,
+                                  int dim, float eps, int hidden_dtype, int out_dtype, int flags, void* stream);
+int simamba_add_layer_norm_bwd_ex(const void* dnormed, const float* dresidual_out,
+                                  const float* residual_out, const float* mean, const float* rstd,
+                                  const float* weight, const float* rowscale, float* dresidual,
+                                  void* dhidden, float* dwb_partial, int batch, int rows_per_batch,
+                                  int dim, int hidden_dtype, int out_dtype, int flags, void* stream);
+
+/*
  * out_proj -> (+ DropPath-scaled residual) -> LayerNorm in one kernel on the matrix cores, bf16 operands: the mixer's
  * out_proj (upstream mamba_inner_fn, models/block.py:72) fused with the Add -> LayerNorm that opens the next block
  * (models/block.py:56-58) or closes the stack (models/point_mamba.py:257-258).  The out_proj result is rounded to bf16
@@ -316,6 +339,12 @@ int simamba_add_layer_norm_bwd(const void* dnormed, const float* dresidual_out,
 int simamba_out_proj_add_ln_fwd(const void* y, const void* w, const float* residual, const float* rowscale,
                                 const float* gamma, const float* beta, float* residual_out, void* normed, float* mean,
                                 float* rstd, int batch, int K, int L, int C, float eps, int out_dtype, void* stream);
+/* ... with the norm flags above (SIMAMBA_NORM_RMS: beta NULL, mean may be NULL; the backward is
+ * simamba_add_layer_norm_bwd_ex with the same flags) */
+int simamba_out_proj_add_ln_fwd_ex(const void* y, const void* w, const float* residual, const float* rowscale,
+                                   const float* gamma, const float* beta, float* residual_out, void* normed,
+                                   float* mean, float* rstd, int batch, int K, int L, int C, float eps, int out_dtype,
+                                   int flags, void* stream);
 
 /*
  * in_proj of the mixer on the matrix cores (the first product of upstream's Mamba.forward, reached from

@@ -7,9 +7,11 @@ from .causal_conv1d import causal_conv1d_fn
 from .selective_scan import selective_scan_fn
 from .mamba_simple import Mamba
 from .block import Block, MixerModel, create_block, DropPath
+from .rms_norm import RMSNorm
 from . import spectral
 from .shim import install_shim
 from ._lib import deterministic, deterministic_enabled, set_deterministic
 
 __all__ = ["causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
-           "DropPath", "spectral", "install_shim", "deterministic", "deterministic_enabled", "set_deterministic"]
+           "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
+           "set_deterministic"]

@@ -28,6 +28,8 @@ SCAN_AUTO, SCAN_ROWSCAN, SCAN_LPC2, SCAN_LPC4, SCAN_MIX = 0, 1, 2, 4, 6
 CKPT_ROW, CKPT_SEQ = 128, 16
 # flags of the *_ex backward entry points: no float atomics, bitwise reproducible parameter gradients
 BWD_DETERMINISTIC = 1
+# flags of the add + norm *_ex entry points: RMSNorm in place of LayerNorm
+NORM_RMS = 1
 
 # name -> (restype, argtypes); mirrors include/simamba.h one to one
 _P = c_void_p
@@ -79,8 +81,14 @@ SIGNATURES = {
                                            c_int, c_int, _P]),
     "simamba_add_layer_norm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int,
                                            c_int, c_int, _P]),
+    "simamba_add_layer_norm_fwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float,
+                                              c_int, c_int, c_int, _P]),
+    "simamba_add_layer_norm_bwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int,
+                                              c_int, c_int, c_int, _P]),
     "simamba_out_proj_add_ln_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,
                                             c_int, _P]),
+    "simamba_out_proj_add_ln_fwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                               c_float, c_int, c_int, _P]),
     "simamba_in_proj_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "simamba_bn_relu_grid": (c_int, [_LL]),
     "simamba_bn_relu_fwd": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_float, c_float, c_int, _P, _P, _P, _P, _LL, c_int,

@@ -1,9 +1,9 @@
-"""Fused DropPath-scaled residual add + LayerNorm on the MI355X kernel (csrc/add_norm.hip).
+"""Fused DropPath-scaled residual add + LayerNorm (or RMSNorm) on the MI355X kernel (csrc/add_norm.hip).
 
 Computes exactly what the reference's Block.forward does before the mixer (models/block.py:56-60):
 
     residual = drop_path(hidden) + residual        (or hidden when residual is None)
-    normed   = LayerNorm(residual)
+    normed   = LayerNorm(residual)                 (rms=True: RMSNorm(residual), no bias)
 
 as one streaming pass forward and one backward.  ``rowscale`` is the per-sample DropPath factor
 (keep-mask / keep-prob) or None.
@@ -17,7 +17,7 @@ from . import _lib
 
 class AddLayerNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, residual, weight, bias, eps, rowscale, out_dtype):
+    def forward(ctx, hidden, residual, weight, bias, eps, rowscale, out_dtype, rms=False):
         _lib.require_gpu(hidden, "add_layer_norm_fn")
         lib = _lib.load()
         h = hidden.contiguous()
@@ -25,6 +25,7 @@ class AddLayerNormFn(torch.autograd.Function):
         dev = h.device
         hcode = _lib.dtype_code(h.dtype)
         ocode = _lib.dtype_code(out_dtype)
+        flags = _lib.NORM_RMS if rms else 0
         res = None if residual is None else residual.float().contiguous()
         w = weight.float().contiguous()
         b = None if bias is None else bias.float().contiguous()
@@ -32,23 +33,23 @@ class AddLayerNormFn(torch.autograd.Function):
         alias = res is None and h.dtype == torch.float32        # residual_out is hidden itself
         res_out = h if alias else torch.empty(h.shape, device=dev, dtype=torch.float32)
         normed = torch.empty(h.shape, device=dev, dtype=out_dtype)
-        mean = torch.empty(Bsz * rows, device=dev, dtype=torch.float32)
+        mean = None if rms else torch.empty(Bsz * rows, device=dev, dtype=torch.float32)   # RMSNorm has no mean
         rstd = torch.empty(Bsz * rows, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("add_ln_fwd", dev):
-            rc = lib.simamba_add_layer_norm_fwd(h.data_ptr(), _lib.ptr(res), _lib.ptr(rs), w.data_ptr(), _lib.ptr(b),
-                                                None if alias else res_out.data_ptr(), normed.data_ptr(),
-                                                mean.data_ptr(), rstd.data_ptr(), Bsz, rows, dim, float(eps),
-                                                hcode, ocode, _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_add_layer_norm_fwd")
+        with torch.cuda.device(dev), _lib.timed("add_rms_fwd" if rms else "add_ln_fwd", dev):
+            rc = lib.simamba_add_layer_norm_fwd_ex(h.data_ptr(), _lib.ptr(res), _lib.ptr(rs), w.data_ptr(),
+                                                   _lib.ptr(b), None if alias else res_out.data_ptr(),
+                                                   normed.data_ptr(), _lib.ptr(mean), rstd.data_ptr(), Bsz, rows, dim,
+                                                   float(eps), hcode, ocode, flags, _lib.stream_ptr(dev))
+        _lib.check(rc, "simamba_add_layer_norm_fwd_ex")
         ctx.save_for_backward(res_out, mean, rstd, w, rs)
         ctx.meta = (Bsz, rows, dim, hcode, ocode, h.dtype, residual is not None,
-                    None if residual is None else residual.dtype, weight.dtype, bias is not None)
+                    None if residual is None else residual.dtype, weight.dtype, bias is not None, flags)
         return normed, res_out
 
     @staticmethod
     def backward(ctx, dnormed, dres_out):
         res_out, mean, rstd, w, rs = ctx.saved_tensors
-        Bsz, rows, dim, hcode, ocode, hdtype, has_res, res_dtype, wdtype, has_bias = ctx.meta
+        Bsz, rows, dim, hcode, ocode, hdtype, has_res, res_dtype, wdtype, has_bias, flags = ctx.meta
         lib = _lib.load()
         dev = res_out.device
         dn = dnormed.contiguous()
@@ -60,21 +61,30 @@ class AddLayerNormFn(torch.autograd.Function):
         dhid = torch.empty(res_out.shape, device=dev, dtype=hdtype) if need_split else None
         grid = lib.simamba_add_layer_norm_grid(Bsz, rows)
         part = torch.empty(grid, 2, dim, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("add_ln_bwd", dev):
-            rc = lib.simamba_add_layer_norm_bwd(dn.data_ptr(), _lib.ptr(dro), res_out.data_ptr(), mean.data_ptr(),
-                                                rstd.data_ptr(), w.data_ptr(), _lib.ptr(rs), _lib.ptr(dres),
-                                                _lib.ptr(dhid), part.data_ptr(), Bsz, rows, dim, hcode, ocode,
-                                                _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_add_layer_norm_bwd")
-        dwb = part.sum(0)
+        with torch.cuda.device(dev), _lib.timed("add_rms_bwd" if flags else "add_ln_bwd", dev):
+            rc = lib.simamba_add_layer_norm_bwd_ex(dn.data_ptr(), _lib.ptr(dro), res_out.data_ptr(), _lib.ptr(mean),
+                                                   rstd.data_ptr(), w.data_ptr(), _lib.ptr(rs), _lib.ptr(dres),
+                                                   _lib.ptr(dhid), part.data_ptr(), Bsz, rows, dim, hcode, ocode,
+                                                   flags, _lib.stream_ptr(dev))
+        _lib.check(rc, "simamba_add_layer_norm_bwd_ex")
+        # RMS: only the dweight half of the partials is written
+        dwb = part[:, :1].sum(0) if flags else part.sum(0)
         if dhid is None:
             dhid = dres
         return (dhid, None if not has_res else dres.to(res_dtype), dwb[0].to(wdtype),
-                dwb[1].to(wdtype) if has_bias else None, None, None, None)
+                dwb[1].to(wdtype) if has_bias else None, None, None, None, None)
 
 
-def add_layer_norm_fn(hidden, residual, weight, bias, eps=1e-5, rowscale=None, out_dtype=None):
-    """-> (normed, residual_out).  hidden: (B, ..., dim); residual: same shape or None; rowscale: (B,) or None."""
+def add_layer_norm_fn(hidden, residual, weight, bias, eps=1e-5, rowscale=None, out_dtype=None, rms=False):
+    """-> (normed, residual_out).  hidden: (B, ..., dim); residual: same shape or None; rowscale: (B,) or None.
+    ``rms=True``: RMSNorm (``bias`` must be None) in place of LayerNorm."""
+    if rms and bias is not None:
+        raise ValueError("add_layer_norm_fn(rms=True): RMSNorm takes no bias")
     if out_dtype is None:
         out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else weight.dtype
-    return AddLayerNormFn.apply(hidden, residual, weight, bias, eps, rowscale, out_dtype)
+    return AddLayerNormFn.apply(hidden, residual, weight, bias, eps, rowscale, out_dtype, bool(rms))
+
+
+def add_rms_norm_fn(hidden, residual, weight, eps=1e-5, rowscale=None, out_dtype=None):
+    """add_layer_norm_fn with RMSNorm: -> (normed, residual_out)."""
+    return add_layer_norm_fn(hidden, residual, weight, None, eps, rowscale=rowscale, out_dtype=out_dtype, rms=True)

@@ -24,6 +24,19 @@ from . import _lib
 from .add_norm import add_layer_norm_fn
 from .mamba_simple import Mamba
 from .out_norm import out_proj_add_ln_fn, out_proj_add_ln_ok
+from .rms_norm import RMSNorm
+
+_KERNEL_NORMS = (nn.LayerNorm, RMSNorm)      # the norms the add + norm kernels compute
+
+
+def _fused_norm(hidden, residual, norm, rowscale=None, out_dtype=None):
+    """Add (+ DropPath) + ``norm`` (an nn.LayerNorm or an RMSNorm) through the add_norm kernel: -> (normed, residual).
+    RMSNorm routes are counted (``add_rms_norm``)."""
+    rms = type(norm) is RMSNorm
+    if rms:
+        _lib.count("add_rms_norm")
+    return add_layer_norm_fn(hidden, residual, norm.weight, norm.bias, norm.eps, rowscale=rowscale,
+                             out_dtype=out_dtype, rms=rms)
 
 
 class DropPath(nn.Module):
@@ -67,12 +80,11 @@ class Block(nn.Module):
         implementation): the mixer's -exp(A_log) when the caller has already formed it (MixerModel does, for all
         layers in one launch); handed on as an argument, never parked on the module.
 
-        Add (+ DropPath) + LayerNorm run as one HIP pass each way (add_norm.py) for LayerNorm blocks on the
+        Add (+ DropPath) + LayerNorm (or RMSNorm) run as one HIP pass each way (add_norm.py) for such blocks on the
         GPU; the composed torch form below is the reference's own and serves any other norm / device."""
-        if hidden_states.is_cuda and type(self.norm) is nn.LayerNorm and hidden_states.dim() == 3:
+        if hidden_states.is_cuda and type(self.norm) in _KERNEL_NORMS and hidden_states.dim() == 3:
             scale = self.drop_path.rowscale(hidden_states) if isinstance(self.drop_path, DropPath) else None
-            hidden_states, residual = add_layer_norm_fn(hidden_states, residual, self.norm.weight, self.norm.bias,
-                                                        self.norm.eps, rowscale=scale)
+            hidden_states, residual = _fused_norm(hidden_states, residual, self.norm, rowscale=scale)
         else:
             residual = (self.drop_path(hidden_states) + residual) if residual is not None else hidden_states
             hidden_states = self.norm(residual.to(dtype=self.norm.weight.dtype))
@@ -106,12 +118,10 @@ def _init_weights(module, n_layer, initializer_range=0.02, rescale_prenorm_resid
 
 def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, rms_norm=False, residual_in_fp32=False,
                  fused_add_norm=False, layer_idx=None, drop_path=0., device=None, dtype=None):
-    if rms_norm:
-        raise NotImplementedError("rms_norm=True needs mamba-ssm's Triton RMSNorm; every reference cfg sets False")
     ssm_cfg = {} if ssm_cfg is None else ssm_cfg
     factory_kwargs = {"device": device, "dtype": dtype}
     mixer_cls = partial(Mamba, layer_idx=layer_idx, **ssm_cfg, **factory_kwargs)
-    norm_cls = partial(nn.LayerNorm, eps=norm_epsilon, **factory_kwargs)
+    norm_cls = partial(nn.LayerNorm if not rms_norm else RMSNorm, eps=norm_epsilon, **factory_kwargs)
     block = Block(d_model, mixer_cls, norm_cls=norm_cls, fused_add_norm=fused_add_norm,
                   residual_in_fp32=residual_in_fp32, drop_path=drop_path)
     block.layer_idx = layer_idx
@@ -132,7 +142,7 @@ class MixerModel(nn.Module):
                          residual_in_fp32=residual_in_fp32, fused_add_norm=fused_add_norm, layer_idx=i,
                          drop_path=drop_path, **factory_kwargs)
             for i in range(n_layer)])
-        self.norm_f = nn.LayerNorm(d_model, eps=norm_epsilon, **factory_kwargs)
+        self.norm_f = (nn.LayerNorm if not rms_norm else RMSNorm)(d_model, eps=norm_epsilon, **factory_kwargs)
         self.apply(partial(_init_weights, n_layer=n_layer,
                            **(initializer_cfg if initializer_cfg is not None else {})))
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
@@ -150,7 +160,7 @@ class MixerModel(nn.Module):
         from . import seq_expand
         layer = self.layers[0]
         mixer = layer.mixer
-        if not (tokens.is_cuda and type(layer.norm) is nn.LayerNorm and isinstance(mixer, Mamba)
+        if not (tokens.is_cuda and type(layer.norm) in _KERNEL_NORMS and isinstance(mixer, Mamba)
                 and mixer.use_fast_path and seq_expand.expansion_ok(tokens, token_index)):
             return None
         inv32 = seq_expand.inverse_positions(token_index, tokens.shape[1])
@@ -160,9 +170,9 @@ class MixerModel(nn.Module):
         # residual_0 = tokens + pos and its LayerNorm in one pass over the G tokens.  (Low-precision operands: the
         # reference's `input_ids + pos` rounds the sum to that dtype first -- keep that rounding.)
         if tokens.dtype == torch.float32:
-            normed, res0 = add_layer_norm_fn(tokens, pos, layer.norm.weight, layer.norm.bias, layer.norm.eps)
+            normed, res0 = _fused_norm(tokens, pos, layer.norm)
         else:
-            normed, res0 = add_layer_norm_fn(tokens + pos, None, layer.norm.weight, layer.norm.bias, layer.norm.eps)
+            normed, res0 = _fused_norm(tokens + pos, None, layer.norm)
         xz = seq_expand.seq_gather_last(mixer.in_proj_xz(normed), idx32, inv32)          # (B, 2D, L)
         hidden = mixer.forward_xz(xz, A=A, emit_y=emit_y)
         residual = torch.gather(res0, 1, token_index.unsqueeze(-1).expand(-1, -1, res0.shape[-1]))
@@ -181,9 +191,10 @@ class MixerModel(nn.Module):
     def _chain_ok(self, x):
         """Can the stack run as  add+LN -> [in_proj -> mixer body -> (out_proj + add + LN)] * n  with the bracketed
         out_proj / add / LayerNorm as ONE kernel (out_norm.py)?  bf16 compute (autocast or bf16 modules), plain
-        LayerNorm blocks around fast-path Mamba mixers without an out_proj bias, nothing between the blocks."""
+        LayerNorm (or RMSNorm) blocks around fast-path Mamba mixers without an out_proj bias, nothing between the
+        blocks."""
         if not (_lib.fuse_out_norm_enabled() and x.is_cuda and x.dim() == 3
-                and isinstance(self.drop_out_in_block, nn.Identity) and type(self.norm_f) is nn.LayerNorm):
+                and isinstance(self.drop_out_in_block, nn.Identity) and type(self.norm_f) in _KERNEL_NORMS):
             return False
         # the dtype the projections compute in: autocast's, else the parameters'
         io = (torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda")
@@ -193,7 +204,7 @@ class MixerModel(nn.Module):
         d_model = x.shape[-1]
         for layer in self.layers:
             m = layer.mixer
-            if not (type(layer) is Block and type(layer.norm) is nn.LayerNorm and type(m) is Mamba and m.use_fast_path
+            if not (type(layer) is Block and type(layer.norm) in _KERNEL_NORMS and type(m) is Mamba and m.use_fast_path
                     and m.out_proj.bias is None and m.d_model == d_model and d_model % 128 == 0 and d_model <= 384
                     and m.d_inner % 64 == 0):
                 return False
@@ -218,13 +229,13 @@ class MixerModel(nn.Module):
                 else:
                     norm, scale, out_dtype = self.norm_f, None, self.norm_f.weight.dtype
                 if out_proj_add_ln_ok(y, prev.out_proj.weight, prev.d_model):
-                    _lib.count("out_proj_add_ln")
+                    rms = type(norm) is RMSNorm
+                    _lib.count("out_proj_add_rms" if rms else "out_proj_add_ln")
                     normed, residual = out_proj_add_ln_fn(y, prev.out_proj.weight, residual, norm.weight, norm.bias,
-                                                          norm.eps, rowscale=scale, out_dtype=out_dtype)
+                                                          norm.eps, rowscale=scale, out_dtype=out_dtype, rms=rms)
                 else:
                     hidden = torch.matmul(y.transpose(1, 2), prev.out_proj.weight.t().to(y.dtype))
-                    normed, residual = add_layer_norm_fn(hidden, residual, norm.weight, norm.bias, norm.eps,
-                                                         rowscale=scale, out_dtype=out_dtype)
+                    normed, residual = _fused_norm(hidden, residual, norm, rowscale=scale, out_dtype=out_dtype)
                 if i == n:
                     return normed
             mixer = self.layers[i].mixer
@@ -261,17 +272,15 @@ class MixerModel(nn.Module):
         if chain:
             l0 = self.layers[0]
             scale = l0.drop_path.rowscale(hidden_states) if isinstance(l0.drop_path, DropPath) else None
-            normed, residual = add_layer_norm_fn(hidden_states, None, l0.norm.weight, l0.norm.bias, l0.norm.eps,
-                                                 rowscale=scale)
+            normed, residual = _fused_norm(hidden_states, None, l0.norm, rowscale=scale)
             return self._chain(0, None, normed, residual, A_all)
         for i in range(first, len(self.layers)):
             hidden_states, residual = self.layers[i](hidden_states, residual, inference_params=inference_params,
                                                      A=A_all[i])
             hidden_states = self.drop_out_in_block(hidden_states)
-        if hidden_states.is_cuda and type(self.norm_f) is nn.LayerNorm and hidden_states.dim() == 3:
+        if hidden_states.is_cuda and type(self.norm_f) in _KERNEL_NORMS and hidden_states.dim() == 3:
             # the stack's output norm returns the parameter dtype (fp32) under autocast too, as F.layer_norm does
             # there; the block norms feed a GEMM and may hand over the autocast dtype directly
-            return add_layer_norm_fn(hidden_states, residual, self.norm_f.weight, self.norm_f.bias,
-                                     self.norm_f.eps, out_dtype=self.norm_f.weight.dtype)[0]
+            return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
         residual = (hidden_states + residual) if residual is not None else hidden_states
         return self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))

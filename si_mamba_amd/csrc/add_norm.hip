@@ -10,6 +10,12 @@
 // per lane across the rows a wave walks, summed over the workgroup's 4 waves in LDS and written as one
 // partial row per workgroup (summed by the caller -- deterministic, no atomics).
 // HBM-bound: 4*R*dim*s bytes forward, 4-5 * R*dim*s backward (R = batch * rows_per_batch).
+//
+// kRms (SIMAMBA_NORM_RMS): RMSNorm in place of LayerNorm -- mamba-ssm's RMSNorm, which the reference's create_block /
+// MixerModel take for rms_norm=True (models/point_mamba.py:164, :227):  rstd = rsqrt(mean(x^2) + eps),
+// normed = x * rstd * w, no mean, no bias; backward with x^ = x * rstd, g = dnormed * w:
+// dx = rstd * (g - x^ * mean(g * x^)), dw = sum_rows dnormed * x^.  Same bytes each way; `mean` is neither read nor
+// written and the partial rows' dbias half is left as it is.
 #include "common.h"
 
 namespace simamba {
@@ -56,7 +62,7 @@ __device__ __forceinline__ void st4(T* p, float4 v) {
   *reinterpret_cast<Pack<T, 4>*>(p) = pk;
 }
 
-template <typename TH, typename TO, int kChunks>
+template <typename TH, typename TO, int kChunks, bool kRms>
 __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
   const int lane = threadIdx.x & 63;
   const int wave_global = (blockIdx.x * kLnThreads + threadIdx.x) >> 6;
@@ -70,7 +76,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
   for (int k = 0; k < kChunks; ++k) {
     const int c = lane + 64 * k;
     w[k] = c < nch ? *reinterpret_cast<const float4*>(p.weight + 4 * c) : make_float4(0, 0, 0, 0);
-    bs[k] = (c < nch && p.bias) ? *reinterpret_cast<const float4*>(p.bias + 4 * c) : make_float4(0, 0, 0, 0);
+    bs[k] = (!kRms && c < nch && p.bias) ? *reinterpret_cast<const float4*>(p.bias + 4 * c) : make_float4(0, 0, 0, 0);
   }
   const float inv_dim = 1.f / p.dim;
   for (int row = wave_global; row < rows; row += nwaves) {
@@ -95,7 +101,8 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
         x[k] = make_float4(0, 0, 0, 0);
       }
     }
-    const float mean = wave_allreduce_sum(sum) * inv_dim;
+    // RMS: the constant 0 folds away (x - 0.f == x) and with it the row sum and its all-reduce
+    const float mean = kRms ? 0.f : wave_allreduce_sum(sum) * inv_dim;
     float sq = 0.f;
 #pragma unroll
     for (int k = 0; k < kChunks; ++k) {
@@ -117,11 +124,14 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
         st4<TO>(og + base + 4 * c, y);
       }
     }
-    if (lane == 0) { p.mean[row] = mean; p.rstd[row] = rstd; }
+    if (lane == 0) {
+      if (!kRms) p.mean[row] = mean;
+      p.rstd[row] = rstd;
+    }
   }
 }
 
-template <typename TH, typename TO, int kChunks>
+template <typename TH, typename TO, int kChunks, bool kRms>
 __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
   extern __shared__ float sred[];          // [4 waves][2][dim]
   const int lane = threadIdx.x & 63;
@@ -143,7 +153,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
   const float inv_dim = 1.f / p.dim;
   for (int row = wave_global; row < rows; row += nwaves) {
     const size_t base = static_cast<size_t>(row) * p.dim;
-    const float mean = p.mean[row], rstd = p.rstd[row];
+    const float mean = kRms ? 0.f : p.mean[row], rstd = p.rstd[row];
     float4 xh[kChunks], g[kChunks];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
         g[k] = make_float4(0, 0, 0, 0);
       }
     }
-    const float c1 = wave_allreduce_sum(s1) * inv_dim;
+    const float c1 = kRms ? 0.f : wave_allreduce_sum(s1) * inv_dim;     // RMS: no -mean(g) term
     const float c2 = wave_allreduce_sum(s2) * inv_dim;
     const float scale = (p.rowscale && dhg) ? p.rowscale[row / p.rows_per_batch] : 1.f;
 #pragma unroll
@@ -186,18 +196,19 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
     }
   }
   // weight / bias gradients: lanes -> LDS per wave -> sum over the 4 waves -> one partial row per workgroup
+  // (RMS: the weight half only)
   float* mine = sred + wave * 2 * p.dim;
 #pragma unroll
   for (int k = 0; k < kChunks; ++k) {
     const int c = lane + 64 * k;
     if (c < nch) {
       *reinterpret_cast<float4*>(mine + 4 * c) = dw[k];
-      *reinterpret_cast<float4*>(mine + p.dim + 4 * c) = db[k];
+      if (!kRms) *reinterpret_cast<float4*>(mine + p.dim + 4 * c) = db[k];
     }
   }
   __syncthreads();
   float* out = p.dwb_partial + static_cast<size_t>(blockIdx.x) * 2 * p.dim;
-  for (int i = threadIdx.x; i < 2 * p.dim; i += kLnThreads) {
+  for (int i = threadIdx.x; i < (kRms ? 1 : 2) * p.dim; i += kLnThreads) {
     float v = 0.f;
 #pragma unroll
     for (int wv = 0; wv < kLnThreads / 64; ++wv) v += sred[wv * 2 * p.dim + i];
@@ -210,16 +221,16 @@ static int ln_grid(int rows) {
   return g < 1 ? 1 : (g > 1024 ? 1024 : g);
 }
 
-template <typename TH, typename TO>
+template <typename TH, typename TO, bool kRms>
 static int launch_ln(const LnArgs& a, bool bwd, int grid, hipStream_t s) {
   const int chunks = ((a.dim >> 2) + 63) / 64;
 #define SIMAMBA_LN_CASE(K)                                                                                      \
   if (chunks <= K) {                                                                                             \
     if (bwd)                                                                                                     \
-      hipLaunchKernelGGL((add_ln_bwd_kernel<TH, TO, K>), dim3(grid), dim3(kLnThreads),                           \
+      hipLaunchKernelGGL((add_ln_bwd_kernel<TH, TO, K, kRms>), dim3(grid), dim3(kLnThreads),                     \
                          sizeof(float) * (kLnThreads / 64) * 2 * a.dim, s, a);                                   \
     else                                                                                                         \
-      hipLaunchKernelGGL((add_ln_fwd_kernel<TH, TO, K>), dim3(grid), dim3(kLnThreads), 0, s, a);                 \
+      hipLaunchKernelGGL((add_ln_fwd_kernel<TH, TO, K, kRms>), dim3(grid), dim3(kLnThreads), 0, s, a);           \
     return static_cast<int>(hipGetLastError());                                                                  \
   }
   SIMAMBA_LN_CASE(1)
@@ -230,11 +241,17 @@ static int launch_ln(const LnArgs& a, bool bwd, int grid, hipStream_t s) {
   return SIMAMBA_E_SHAPE;
 }
 
-static int dispatch_ln(const LnArgs& a, bool bwd, int grid, int hidden_dtype, int out_dtype, hipStream_t s) {
-  if (hidden_dtype == SIMAMBA_F32 && out_dtype == SIMAMBA_F32) return launch_ln<float, float>(a, bwd, grid, s);
-  if (hidden_dtype == SIMAMBA_BF16 && out_dtype == SIMAMBA_BF16) return launch_ln<bf16_t, bf16_t>(a, bwd, grid, s);
-  if (hidden_dtype == SIMAMBA_F32 && out_dtype == SIMAMBA_BF16) return launch_ln<float, bf16_t>(a, bwd, grid, s);
-  if (hidden_dtype == SIMAMBA_BF16 && out_dtype == SIMAMBA_F32) return launch_ln<bf16_t, float>(a, bwd, grid, s);
+template <typename TH, typename TO>
+static int launch_ln(const LnArgs& a, bool bwd, bool rms, int grid, hipStream_t s) {
+  return rms ? launch_ln<TH, TO, true>(a, bwd, grid, s) : launch_ln<TH, TO, false>(a, bwd, grid, s);
+}
+
+static int dispatch_ln(const LnArgs& a, bool bwd, bool rms, int grid, int hidden_dtype, int out_dtype, hipStream_t s) {
+  if (hidden_dtype == SIMAMBA_F32 && out_dtype == SIMAMBA_F32) return launch_ln<float, float>(a, bwd, rms, grid, s);
+  if (hidden_dtype == SIMAMBA_BF16 && out_dtype == SIMAMBA_BF16)
+    return launch_ln<bf16_t, bf16_t>(a, bwd, rms, grid, s);
+  if (hidden_dtype == SIMAMBA_F32 && out_dtype == SIMAMBA_BF16) return launch_ln<float, bf16_t>(a, bwd, rms, grid, s);
+  if (hidden_dtype == SIMAMBA_BF16 && out_dtype == SIMAMBA_F32) return launch_ln<bf16_t, float>(a, bwd, rms, grid, s);
   return SIMAMBA_E_DTYPE;
 }
 
@@ -253,19 +270,51 @@ extern "C" int simamba_add_layer_norm_grid(int batch, int rows_per_batch) {
   return ln_grid(rows > 2000000000ll ? 2000000000 : static_cast<int>(rows));
 }
 
-extern "C" int simamba_add_layer_norm_fwd(const void* hidden, const float* residual, const float* rowscale,
-                                          const float* weight, const float* bias, float* residual_out, void* normed,
-                                          float* mean, float* rstd, int batch, int rows_per_batch, int dim, float eps,
-                                          int hidden_dtype, int out_dtype, void* stream) {
+extern "C" int simamba_add_layer_norm_fwd_ex(const void* hidden, const float* residual, const float* rowscale,
+                                             const float* weight, const float* bias, float* residual_out, void* normed,
+                                             float* mean, float* rstd, int batch, int rows_per_batch, int dim,
+                                             float eps, int hidden_dtype, int out_dtype, int flags, void* stream) {
+  if (flags & ~SIMAMBA_NORM_RMS) return SIMAMBA_E_VARIANT;
+  const bool rms = (flags & SIMAMBA_NORM_RMS) != 0;
+  if (rms && bias) return SIMAMBA_E_BIAS;
   int rc = check_ln(batch, rows_per_batch, dim);
   if (rc) return rc;
   if (batch == 0 || rows_per_batch == 0) return SIMAMBA_OK;
-  if (!hidden || !weight || !normed || !mean || !rstd) return SIMAMBA_E_NULLPTR;
+  if (!hidden || !weight || !normed || (!mean && !rms) || !rstd) return SIMAMBA_E_NULLPTR;
   LnArgs a{};
   a.hidden = hidden; a.residual = residual; a.rowscale = rowscale; a.weight = weight; a.bias = bias;
   a.residual_out = residual_out; a.normed = normed; a.mean = mean; a.rstd = rstd;
   a.batch = batch; a.rows_per_batch = rows_per_batch; a.dim = dim; a.eps = eps;
-  return dispatch_ln(a, false, simamba_add_layer_norm_grid(batch, rows_per_batch), hidden_dtype, out_dtype,
+  return dispatch_ln(a, false, rms, simamba_add_layer_norm_grid(batch, rows_per_batch), hidden_dtype, out_dtype,
+                     static_cast<hipStream_t>(stream));
+}
+
+extern "C" int simamba_add_layer_norm_fwd(const void* hidden, const float* residual, const float* rowscale,
+                                          const float* weight, const float* bias, float* residual_out, void* normed,
+                                          float* mean, float* rstd, int batch, int rows_per_batch, int dim, float eps,
+                                          int hidden_dtype, int out_dtype, void* stream) {
+  return simamba_add_layer_norm_fwd_ex(hidden, residual, rowscale, weight, bias, residual_out, normed, mean, rstd,
+                                       batch, rows_per_batch, dim, eps, hidden_dtype, out_dtype, 0, stream);
+}
+
+extern "C" int simamba_add_layer_norm_bwd_ex(const void* dnormed, const float* dresidual_out,
+                                             const float* residual_out, const float* mean, const float* rstd,
+                                             const float* weight, const float* rowscale, float* dresidual,
+                                             void* dhidden, float* dwb_partial, int batch, int rows_per_batch, int dim,
+                                             int hidden_dtype, int out_dtype, int flags, void* stream) {
+  if (flags & ~SIMAMBA_NORM_RMS) return SIMAMBA_E_VARIANT;
+  const bool rms = (flags & SIMAMBA_NORM_RMS) != 0;
+  int rc = check_ln(batch, rows_per_batch, dim);
+  if (rc) return rc;
+  if (batch == 0 || rows_per_batch == 0) return SIMAMBA_OK;
+  if (!dnormed || !residual_out || (!mean && !rms) || !rstd || !weight || !dwb_partial || (!dresidual && !dhidden))
+    return SIMAMBA_E_NULLPTR;
+  LnArgs a{};
+  a.dnormed = dnormed; a.dresidual_out = dresidual_out; a.residual_out = const_cast<float*>(residual_out);
+  a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.weight = weight; a.rowscale = rowscale;
+  a.dresidual = dresidual; a.dhidden = dhidden; a.dwb_partial = dwb_partial;
+  a.batch = batch; a.rows_per_batch = rows_per_batch; a.dim = dim;
+  return dispatch_ln(a, true, rms, simamba_add_layer_norm_grid(batch, rows_per_batch), hidden_dtype, out_dtype,
                      static_cast<hipStream_t>(stream));
 }
 
@@ -274,16 +323,7 @@ extern "C" int simamba_add_layer_norm_bwd(const void* dnormed, const float* dres
                                           const float* rowscale, float* dresidual, void* dhidden, float* dwb_partial,
                                           int batch, int rows_per_batch, int dim, int hidden_dtype, int out_dtype,
                                           void* stream) {
-  int rc = check_ln(batch, rows_per_batch, dim);
-  if (rc) return rc;
-  if (batch == 0 || rows_per_batch == 0) return SIMAMBA_OK;
-  if (!dnormed || !residual_out || !mean || !rstd || !weight || !dwb_partial || (!dresidual && !dhidden))
-    return SIMAMBA_E_NULLPTR;
-  LnArgs a{};
-  a.dnormed = dnormed; a.dresidual_out = dresidual_out; a.residual_out = const_cast<float*>(residual_out);
-  a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.weight = weight; a.rowscale = rowscale;
-  a.dresidual = dresidual; a.dhidden = dhidden; a.dwb_partial = dwb_partial;
-  a.batch = batch; a.rows_per_batch = rows_per_batch; a.dim = dim;
-  return dispatch_ln(a, true, simamba_add_layer_norm_grid(batch, rows_per_batch), hidden_dtype, out_dtype,
-                     static_cast<hipStream_t>(stream));
+  return simamba_add_layer_norm_bwd_ex(dnormed, dresidual_out, residual_out, mean, rstd, weight, rowscale, dresidual,
+                                       dhidden, dwb_partial, batch, rows_per_batch, dim, hidden_dtype, out_dtype, 0,
+                                       stream);
 }

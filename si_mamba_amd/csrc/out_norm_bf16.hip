@@ -66,8 +66,9 @@ __device__ __forceinline__ float on_wave_sum(float v) {
   return v;
 }
 
-// CB: 16-channel blocks per wave (C = 128 CB); TO: type of `normed`
-template <int CB, typename TO>
+// CB: 16-channel blocks per wave (C = 128 CB); TO: type of `normed`; kRms: RMSNorm epilogue (SIMAMBA_NORM_RMS, the
+// arithmetic of add_ln_fwd_kernel<.., true>: no mean, no beta, `mean` not written)
+template <int CB, typename TO, bool kRms>
 __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p) {
   constexpr int C = 128 * CB;
   constexpr int kHP = C + 4;                                   // staging pitch (bf16): rows 2 dwords apart in the banks
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
   for (int k = 0; k < kChunks; ++k) {
     const int c = lane + 64 * k;
     gm[k] = c < nch ? *reinterpret_cast<const float4*>(p.gamma + 4 * c) : make_float4(0, 0, 0, 0);
-    bt[k] = (c < nch && p.beta) ? *reinterpret_cast<const float4*>(p.beta + 4 * c) : make_float4(0, 0, 0, 0);
+    bt[k] = (!kRms && c < nch && p.beta) ? *reinterpret_cast<const float4*>(p.beta + 4 * c) : make_float4(0, 0, 0, 0);
   }
   const float scale = (p.rowscale && p.residual) ? p.rowscale[b] : 1.f;
   const float inv_dim = 1.f / C;
@@ -272,7 +273,7 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
           x[k] = make_float4(0, 0, 0, 0);
         }
       }
-      const float mean = on_wave_sum(sum) * inv_dim;
+      const float mean = kRms ? 0.f : on_wave_sum(sum) * inv_dim;
       float sq = 0.f;
 #pragma unroll
       for (int k = 0; k < kChunks; ++k) {
@@ -294,29 +295,43 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
           *reinterpret_cast<Pack<TO, 4>*>(og + base + 4 * c) = pk;
         }
       }
-      if (lane == 0) { p.mean[row] = mean; p.rstd[row] = rstd; }
+      if (lane == 0) {
+        if (!kRms) p.mean[row] = mean;
+        p.rstd[row] = rstd;
+      }
     }
   }
 }
 
-template <int CB>
+template <int CB, bool kRms>
 static void on_launch(const OnArgs& a, int out_dtype, hipStream_t s) {
   const int tps = (a.L + kOnTok - 1) / kOnTok;
   dim3 grid(static_cast<unsigned>(a.batch) * tps);
   if (out_dtype == SIMAMBA_BF16)
-    hipLaunchKernelGGL((out_proj_add_ln_kernel<CB, bf16_t>), grid, dim3(kOnThreads), 0, s, a);
+    hipLaunchKernelGGL((out_proj_add_ln_kernel<CB, bf16_t, kRms>), grid, dim3(kOnThreads), 0, s, a);
   else
-    hipLaunchKernelGGL((out_proj_add_ln_kernel<CB, float>), grid, dim3(kOnThreads), 0, s, a);
+    hipLaunchKernelGGL((out_proj_add_ln_kernel<CB, float, kRms>), grid, dim3(kOnThreads), 0, s, a);
+}
+
+template <int CB>
+static void on_launch(const OnArgs& a, int out_dtype, bool rms, hipStream_t s) {
+  if (rms)
+    on_launch<CB, true>(a, out_dtype, s);
+  else
+    on_launch<CB, false>(a, out_dtype, s);
 }
 
 }  // namespace simamba
 
 using namespace simamba;
 
-extern "C" int simamba_out_proj_add_ln_fwd(const void* y, const void* w, const float* residual, const float* rowscale,
-                                           const float* gamma, const float* beta, float* residual_out, void* normed,
-                                           float* mean, float* rstd, int batch, int K, int L, int C, float eps,
-                                           int out_dtype, void* stream) {
+extern "C" int simamba_out_proj_add_ln_fwd_ex(const void* y, const void* w, const float* residual,
+                                              const float* rowscale, const float* gamma, const float* beta,
+                                              float* residual_out, void* normed, float* mean, float* rstd, int batch,
+                                              int K, int L, int C, float eps, int out_dtype, int flags, void* stream) {
+  if (flags & ~SIMAMBA_NORM_RMS) return SIMAMBA_E_VARIANT;
+  const bool rms = (flags & SIMAMBA_NORM_RMS) != 0;
+  if (rms && beta) return SIMAMBA_E_BIAS;
   if (batch < 0 || K <= 0 || L < 0 || C <= 0) return SIMAMBA_E_SHAPE;
   if (out_dtype != SIMAMBA_F32 && out_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
   // whole 128-channel groups (one 16-channel block per wave each; 128 tokens x 512 channels of bf16 staging would not
@@ -325,7 +340,7 @@ extern "C" int simamba_out_proj_add_ln_fwd(const void* y, const void* w, const f
   if (C % 128 || C > 384 || K % kOnKS || L % 8 || static_cast<long long>(K) * L * 2 >= (1LL << 32) - 65536)
     return SIMAMBA_E_SHAPE;
   if (batch == 0 || L == 0) return SIMAMBA_OK;
-  if (!y || !w || !gamma || !residual_out || !normed || !mean || !rstd) return SIMAMBA_E_NULLPTR;
+  if (!y || !w || !gamma || !residual_out || !normed || (!mean && !rms) || !rstd) return SIMAMBA_E_NULLPTR;
   uintptr_t al = reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(gamma) |
                  reinterpret_cast<uintptr_t>(residual_out) | reinterpret_cast<uintptr_t>(normed) |
                  reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(beta);
@@ -338,9 +353,17 @@ extern "C" int simamba_out_proj_add_ln_fwd(const void* y, const void* w, const f
   a.batch = batch; a.K = K; a.L = L; a.C = C; a.eps = eps;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (C / 128) {
-    case 1: on_launch<1>(a, out_dtype, s); break;
-    case 2: on_launch<2>(a, out_dtype, s); break;
-    default: on_launch<3>(a, out_dtype, s); break;
+    case 1: on_launch<1>(a, out_dtype, rms, s); break;
+    case 2: on_launch<2>(a, out_dtype, rms, s); break;
+    default: on_launch<3>(a, out_dtype, rms, s); break;
   }
   return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_out_proj_add_ln_fwd(const void* y, const void* w, const float* residual, const float* rowscale,
+                                           const float* gamma, const float* beta, float* residual_out, void* normed,
+                                           float* mean, float* rstd, int batch, int K, int L, int C, float eps,
+                                           int out_dtype, void* stream) {
+  return simamba_out_proj_add_ln_fwd_ex(y, w, residual, rowscale, gamma, beta, residual_out, normed, mean, rstd, batch,
+                                        K, L, C, eps, out_dtype, 0, stream);
 }

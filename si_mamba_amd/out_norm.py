@@ -7,7 +7,7 @@ What the reference computes across a block boundary under autocast -- the mixer'
 
     hidden   = y^T @ out_proj.weight^T          (bf16 GEMM output)
     residual = hidden * rowscale + residual     (fp32)
-    normed   = LayerNorm(residual)
+    normed   = LayerNorm(residual)              (rms=True: RMSNorm(residual), no bias)
 
 One kernel forward: the out_proj result never goes to memory.  Backward: the LayerNorm / add backward kernel of
 add_norm.py, then out_proj's input gradient through the hand-written token-times-weight kernel (csrc/in_proj_bf16.hip;
@@ -32,12 +32,13 @@ def out_proj_add_ln_ok(y, out_w, d_model):
 
 class OutProjAddLnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, out_w, residual, ln_w, ln_b, eps, rowscale, out_dtype):
+    def forward(ctx, y, out_w, residual, ln_w, ln_b, eps, rowscale, out_dtype, rms=False):
         _lib.require_gpu(y, "out_proj_add_ln_fn")
         lib = _lib.load()
         Bsz, D, L = y.shape
         C = out_w.shape[0]
         dev = y.device
+        flags = _lib.NORM_RMS if rms else 0
         wc = out_w.to(torch.bfloat16).contiguous()
         res = None if residual is None else residual.float().contiguous()
         lw = ln_w.float().contiguous()
@@ -45,23 +46,23 @@ class OutProjAddLnFn(torch.autograd.Function):
         rs = None if (rowscale is None or res is None) else rowscale.float().contiguous()
         res_out = torch.empty(Bsz, L, C, device=dev, dtype=torch.float32)
         normed = torch.empty(Bsz, L, C, device=dev, dtype=out_dtype)
-        mean = torch.empty(Bsz * L, device=dev, dtype=torch.float32)
+        mean = None if rms else torch.empty(Bsz * L, device=dev, dtype=torch.float32)      # RMSNorm has no mean
         rstd = torch.empty(Bsz * L, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("out_proj_add_ln_fwd", dev):
-            rc = lib.simamba_out_proj_add_ln_fwd(y.data_ptr(), wc.data_ptr(), _lib.ptr(res), _lib.ptr(rs), lw.data_ptr(),
-                                                 _lib.ptr(lb), res_out.data_ptr(), normed.data_ptr(), mean.data_ptr(),
-                                                 rstd.data_ptr(), Bsz, D, L, C, float(eps), _lib.dtype_code(out_dtype),
-                                                 _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_out_proj_add_ln_fwd")
+        with torch.cuda.device(dev), _lib.timed("out_proj_add_rms_fwd" if rms else "out_proj_add_ln_fwd", dev):
+            rc = lib.simamba_out_proj_add_ln_fwd_ex(y.data_ptr(), wc.data_ptr(), _lib.ptr(res), _lib.ptr(rs),
+                                                    lw.data_ptr(), _lib.ptr(lb), res_out.data_ptr(), normed.data_ptr(),
+                                                    _lib.ptr(mean), rstd.data_ptr(), Bsz, D, L, C, float(eps),
+                                                    _lib.dtype_code(out_dtype), flags, _lib.stream_ptr(dev))
+        _lib.check(rc, "simamba_out_proj_add_ln_fwd_ex")
         ctx.save_for_backward(y, wc, res_out, mean, rstd, lw, rs)
         ctx.meta = (Bsz, L, C, _lib.dtype_code(out_dtype), residual is not None,
-                    None if residual is None else residual.dtype, ln_w.dtype, ln_b is not None, out_w.dtype)
+                    None if residual is None else residual.dtype, ln_w.dtype, ln_b is not None, out_w.dtype, flags)
         return normed, res_out
 
     @staticmethod
     def backward(ctx, dnormed, dres_out):
         y, wc, res_out, mean, rstd, lw, rs = ctx.saved_tensors
-        Bsz, L, C, ocode, has_res, res_dtype, lwdtype, has_bias, owdtype = ctx.meta
+        Bsz, L, C, ocode, has_res, res_dtype, lwdtype, has_bias, owdtype, flags = ctx.meta
         lib = _lib.load()
         dev = y.device
         dn = dnormed.contiguous()
@@ -70,19 +71,22 @@ class OutProjAddLnFn(torch.autograd.Function):
         dhid = torch.empty(res_out.shape, device=dev, dtype=torch.bfloat16)     # gradient of the bf16 out_proj output
         grid = lib.simamba_add_layer_norm_grid(Bsz, L)
         part = torch.empty(grid, 2, C, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("add_ln_bwd", dev):
-            rc = lib.simamba_add_layer_norm_bwd(dn.data_ptr(), _lib.ptr(dro), res_out.data_ptr(), mean.data_ptr(),
-                                                rstd.data_ptr(), lw.data_ptr(), _lib.ptr(rs), _lib.ptr(dres),
-                                                dhid.data_ptr(), part.data_ptr(), Bsz, L, C, _lib.BF16, ocode,
-                                                _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_add_layer_norm_bwd")
-        dwb = part.sum(0)
+        with torch.cuda.device(dev), _lib.timed("add_rms_bwd" if flags else "add_ln_bwd", dev):
+            rc = lib.simamba_add_layer_norm_bwd_ex(dn.data_ptr(), _lib.ptr(dro), res_out.data_ptr(), _lib.ptr(mean),
+                                                   rstd.data_ptr(), lw.data_ptr(), _lib.ptr(rs), _lib.ptr(dres),
+                                                   dhid.data_ptr(), part.data_ptr(), Bsz, L, C, _lib.BF16, ocode,
+                                                   flags, _lib.stream_ptr(dev))
+        _lib.check(rc, "simamba_add_layer_norm_bwd_ex")
+        dwb = part[:, :1].sum(0) if flags else part.sum(0)                        # RMS: dweight half only
         dy = tokens_times_weight(dhid, wc.t())                                    # (B, D, L)
         d_out_w = _sum_bmm(dhid.transpose(1, 2), y.transpose(1, 2))               # (C, D)
         return (dy, d_out_w.to(owdtype), None if not has_res else dres.to(res_dtype), dwb[0].to(lwdtype),
-                dwb[1].to(lwdtype) if has_bias else None, None, None, None)
+                dwb[1].to(lwdtype) if has_bias else None, None, None, None, None)
 
 
-def out_proj_add_ln_fn(y, out_w, residual, ln_w, ln_b, eps=1e-5, rowscale=None, out_dtype=torch.bfloat16):
-    """y (B, D, L) bf16 -> (normed (B, L, C) out_dtype, residual_out (B, L, C) fp32)."""
-    return OutProjAddLnFn.apply(y, out_w, residual, ln_w, ln_b, eps, rowscale, out_dtype)
+def out_proj_add_ln_fn(y, out_w, residual, ln_w, ln_b, eps=1e-5, rowscale=None, out_dtype=torch.bfloat16, rms=False):
+    """y (B, D, L) bf16 -> (normed (B, L, C) out_dtype, residual_out (B, L, C) fp32).  ``rms=True``: RMSNorm
+    (``ln_b`` must be None) in place of LayerNorm."""
+    if rms and ln_b is not None:
+        raise ValueError("out_proj_add_ln_fn(rms=True): RMSNorm takes no bias")
+    return OutProjAddLnFn.apply(y, out_w, residual, ln_w, ln_b, eps, rowscale, out_dtype, bool(rms))

@@ -26,11 +26,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import spectral
-from .add_norm import add_layer_norm_fn
-from .block import DropPath, _init_weights, create_block
+from .block import DropPath, _fused_norm, _init_weights, create_block
 from .encoder_ops import bn_relu_fn, token_linear
 from .interp import three_interpolate, three_nn
 from .point_mamba import Encoder, Group
+from .rms_norm import RMSNorm
 
 
 def default_seg_config(**over):
@@ -50,8 +50,6 @@ class MixerModelForSegmentation(nn.Module):
                  fused_add_norm=False, residual_in_fp32=False, drop_path=0.1, fetch_idx=(3, 7, 11), device=None,
                  dtype=None):
         super().__init__()
-        if rms_norm:
-            raise NotImplementedError("rms_norm=True needs mamba-ssm's Triton RMSNorm; the reference cfg sets False")
         kw = {"device": device, "dtype": dtype}
         self.residual_in_fp32 = residual_in_fp32
         self.fused_add_norm = fused_add_norm
@@ -60,7 +58,7 @@ class MixerModelForSegmentation(nn.Module):
             create_block(d_model, ssm_cfg=ssm_cfg, norm_epsilon=norm_epsilon, rms_norm=rms_norm,
                          residual_in_fp32=residual_in_fp32, fused_add_norm=fused_add_norm, layer_idx=i,
                          drop_path=drop_path, **kw) for i in range(n_layer)])
-        self.norm_f = nn.LayerNorm(d_model, eps=norm_epsilon, **kw)
+        self.norm_f = (nn.LayerNorm if not rms_norm else RMSNorm)(d_model, eps=norm_epsilon, **kw)
         self.apply(partial(_init_weights, n_layer=n_layer, **(initializer_cfg if initializer_cfg is not None else {})))
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
 
@@ -72,8 +70,8 @@ class MixerModelForSegmentation(nn.Module):
             hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params)
             if i in self.fetch_idx:
                 if hidden_states.is_cuda:
-                    feats.append(add_layer_norm_fn(hidden_states, residual, self.norm_f.weight, self.norm_f.bias,
-                                                   self.norm_f.eps, out_dtype=self.norm_f.weight.dtype)[0])
+                    feats.append(_fused_norm(hidden_states, residual, self.norm_f,
+                                             out_dtype=self.norm_f.weight.dtype)[0])
                 else:
                     feats.append(self.norm_f((hidden_states + residual).to(self.norm_f.weight.dtype)))
         return feats
