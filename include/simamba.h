@@ -21,7 +21,7 @@
  *   simamba_selective_scan_dt_fwd/bwd  the scan with delta formed in the kernel (same call site, bf16 path).
  *   simamba_knn_graph                models/point_mamba.py:620-661 and :664-715
  *                                    (create_graph_from_centers / ..._feature_space_...).
- *   simamba_laplacian_topk           models/point_mamba.py:717-761 and :764-814
+ *   simamba_laplacian_topk[_ex]      models/point_mamba.py:717-761 and :764-814
  *                                    (per-sample torch.linalg.eigh loop, cuSOLVER underneath).
  *   simamba_spectral_topk            the two above fused: centres -> top-k eigenpairs + orders.
  *   simamba_argsort_rows             the torch.sort of models/point_mamba.py:820.
@@ -63,7 +63,8 @@ extern "C" {
 #define SIMAMBA_E_DSTATE     -4   /* dstate must be in [1,16] */
 #define SIMAMBA_E_WIDTH      -5   /* conv width must be in [2,4] */
 #define SIMAMBA_E_WORKSPACE  -6
-#define SIMAMBA_E_GROUPS     -7   /* G in [2,128], knn + 1 <= min(G,32), k (+1) <= G, F in [1,64] */
+#define SIMAMBA_E_GROUPS     -7   /* G in [2,128] (simamba_laplacian_topk) or [2,512] (graph, _ex, fused),
+                                     knn + 1 <= min(G,32), k (+1) <= G (<= 8 above 128), F in [1,64] */
 #define SIMAMBA_E_ALIGN      -8
 #define SIMAMBA_E_VARIANT    -9   /* unknown forward-scan variant, or one the shape / alignment cannot take; unknown
                                      flag bits */
@@ -438,16 +439,19 @@ int simamba_knn_group(const float* points, const float* centers, long long* idx,
 #define SIMAMBA_SPEC_SMALLEST    0x10u  /* k smallest eigenvalues (else k largest)              */
 #define SIMAMBA_SPEC_SIGMA_MEAN  0x20u  /* weight exp(-d^2 / 2 sigma^2), sigma = mean distance
                                            over the whole batch (reference alpha == 0 branch)  */
+#define SIMAMBA_SPEC_LARGE_G     0x40u  /* simamba_laplacian_topk_ex only: run the large-G kernel at
+                                           G <= 128 too (parity tests; production leaves it 0) */
 
 /*
- * k-NN graph adjacency.  points (B,G,F) fp32 -> adj (B,G,G) fp32.
- * workspace: >= simamba_spectral_workspace_bytes(B,G) bytes (used by SIGMA_MEAN only).
+ * k-NN graph adjacency.  points (B,G,F) fp32 -> adj (B,G,G) fp32, 2 <= G <= 512 (above 128: two launches over
+ * row blocks, the adjacency zero-filled in place; the same edges and weights as the G <= 128 kernel).
+ * workspace: >= 256 bytes (used by SIGMA_MEAN only).
  */
 int simamba_knn_graph(const float* points, float* adj, void* workspace, size_t ws_bytes,
                       int B, int G, int F, int knn, float alpha, unsigned flags, void* stream);
 
 /*
- * Laplacian eigen-decomposition, one workgroup per sample (cyclic Jacobi, LDS-resident).
+ * Laplacian eigen-decomposition, one workgroup per sample (cyclic Jacobi, LDS-resident), 2 <= G <= 128.
  *   adj        : (B,G,G) fp32
  *   evals      : (B,k)      evecs : (B,G,k)      order : (B,k,G) int64 (ascending argsort of
  *                each selected eigenvector, ties by index); any of the three may be NULL.
@@ -460,9 +464,23 @@ int simamba_laplacian_topk(const float* adj, float* evals, float* evecs, long lo
                            float* all_evals, float* all_evecs, int B, int G, int k,
                            unsigned flags, void* stream);
 
+/*
+ * Top-k eigenpairs for 2 <= G <= 512: the contract of simamba_laplacian_topk without the full-spectrum outputs.
+ * G <= 128 (and SIMAMBA_SPEC_LARGE_G clear): exactly simamba_laplacian_topk(..., NULL, NULL, ...); the workspace
+ * is not used and may be NULL.  Above 128 (or with SIMAMBA_SPEC_LARGE_G): Householder tridiagonalisation with the
+ * matrix in `workspace` (>= simamba_laplacian_topk_workspace_bytes(B,G) bytes, one G x G fp32 matrix per sample),
+ * fp64 bisection and inverse iteration; k (+1 for MATRIX_SYM) <= 8.  Unknown flag bits: SIMAMBA_E_VARIANT.
+ */
+size_t simamba_laplacian_topk_workspace_bytes(int B, int G);
+int simamba_laplacian_topk_ex(const float* adj, float* evals, float* evecs, long long* order,
+                              void* workspace, size_t ws_bytes, int B, int G, int k, unsigned flags,
+                              void* stream);
+
+/* 256 + 4*B*G*G for G <= 128; above, the large-G eigensolver's workspace is appended (256-byte aligned). */
 size_t simamba_spectral_workspace_bytes(int B, int G);
 
-/* centres (B,G,3) -> top-k eigenpairs + orders; workspace holds the (B,G,G) adjacency. */
+/* centres (B,G,3) -> top-k eigenpairs + orders, 2 <= G <= 512; workspace holds the (B,G,G) adjacency (and above
+ * 128 the eigensolver's matrix). */
 int simamba_spectral_topk(const float* centers, float* evals, float* evecs, long long* order,
                           void* workspace, size_t ws_bytes, int B, int G, int knn, float alpha,
                           int k, unsigned flags, void* stream);
@@ -471,7 +489,7 @@ int simamba_spectral_topk(const float* centers, float* evals, float* evecs, long
  * Farthest-point sampling (tokeniser step ahead of the hot path; replaces
  * pytorch3d.ops.sample_farthest_points at reference models/point_mamba.py:93).
  *   points (B, N, 3) fp32 -> idx (B, K) int64 (first pick = point 0, ties to the lower index),
- *   centers (B, K, 3) fp32 or NULL.  N <= 4096, K <= N.
+ *   centers (B, K, 3) fp32 or NULL.  N <= 8192 (a 1024-lane kernel above 4096), K <= N.
  */
 int simamba_farthest_point_sample(const float* points, long long* idx, float* centers, int B, int N,
                                   int K, void* stream);

@@ -21,6 +21,9 @@ SPEC_BINARY = 0x04
 SPEC_MATRIX_SYM = 0x08
 SPEC_SMALLEST = 0x10
 SPEC_SIGMA_MEAN = 0x20
+SPEC_LARGE_G = 0x40          # simamba_laplacian_topk_ex: the large-G kernel at G <= 128 too (parity tests only)
+SPEC_MAX_G = 128             # simamba_laplacian_topk and the full-spectrum outputs
+SPEC_MAX_G_LARGE = 512       # graph, simamba_laplacian_topk_ex and the fused call
 
 # forward-scan kernel selection (include/simamba.h): AUTO in production, the others for benchmarks / parity tests
 SCAN_AUTO, SCAN_ROWSCAN, SCAN_LPC2, SCAN_LPC4, SCAN_MIX = 0, 1, 2, 4, 6
@@ -105,6 +108,8 @@ SIGNATURES = {
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),
     "simamba_laplacian_topk": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_uint, _P]),
+    "simamba_laplacian_topk_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "simamba_laplacian_topk_ex": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_uint, _P]),
     "simamba_spectral_workspace_bytes": (c_size_t, [c_int, c_int]),
     "simamba_spectral_topk": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_float,
                                       c_int, c_uint, _P]),
@@ -255,6 +260,30 @@ class scan_ckpt:
     def __exit__(self, *exc):
         _scan_ckpt[0] = self.prev
         return False
+
+
+_spectral_large_g = [False]
+
+
+class spectral_large_g:
+    """Context manager for parity tests and benchmarks: top-k eigenpairs through the large-G kernel
+    (simamba_laplacian_topk_ex with SPEC_LARGE_G) at G <= 128 too, where the library otherwise runs the LDS-resident
+    tridiagonal kernel.  Production code never enters it: above 128 patches the large-G kernel is the only route."""
+
+    def __init__(self, on=True):
+        self.v, self.prev = bool(on), None
+
+    def __enter__(self):
+        self.prev, _spectral_large_g[0] = _spectral_large_g[0], self.v
+        return self
+
+    def __exit__(self, *exc):
+        _spectral_large_g[0] = self.prev
+        return False
+
+
+def spectral_large_g_forced():
+    return _spectral_large_g[0]
 
 
 _fuse_dt = [None]      # None: the measured default (bf16 I/O only, see fuse_dt_enabled); True / False: forced

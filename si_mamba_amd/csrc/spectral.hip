@@ -7,6 +7,7 @@
 // The G x G problem (G <= 128) lives entirely in LDS (matrix + eigenvector basis = 2*128*132*4
 // = 132 KiB of the CU's 160 KiB); the eigensolver is a cyclic one-sided (Hestenes) Jacobi with the
 // round-robin (tournament) ordering: G/2 disjoint column pairs per step, one 16-lane DPP row per pair.
+// Above 128 patches the graph and the top-k eigenpairs run on the global-workspace kernels of spectral_large.hip.
 // This file is compiled WITHOUT fast-math and with -ffp-contract=off so that distances and the
 // Laplacian entries round exactly like the reference's unfused torch ops.
 #include "spectral_common.h"
@@ -48,7 +49,6 @@ __global__ void dist_sum_kernel(const float* __restrict__ pts, double* __restric
 // a stable sort.  The picked (index, weight) lists go to LDS once and feed both index_put phases of the
 // reference.  (History: sweeping an LDS copy of the matrix cost 0.64 ms per batch of 64; one lane per node with
 // 128 registers 0.32 ms -- two waves per CU are latency-bound.)
-constexpr int kKnnMaxK = 32;   // knn + 1 <= 32 list entries per node
 constexpr int kKnnLanes = 4;   // lanes per node
 constexpr int kKnnPer = kSpecMaxG / kKnnLanes;   // distances per lane
 
@@ -385,9 +385,20 @@ __global__ void argsort_rows_kernel(const float* __restrict__ vals, long long* _
 
 using namespace simamba;
 
+static size_t round_up_256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+
+// G <= 128: 256 B (SIGMA_MEAN accumulator) + the (B,G,G) adjacency.  Above: + the large-G eigensolver's workspace,
+// 256-byte aligned behind the adjacency.
 extern "C" size_t simamba_spectral_workspace_bytes(int B, int G) {
   if (B < 0 || G < 0) return 0;
-  return 256 + sizeof(float) * static_cast<size_t>(B) * G * G;
+  const size_t adj = sizeof(float) * static_cast<size_t>(B) * G * G;
+  if (G <= kSpecMaxG) return 256 + adj;
+  return 256 + round_up_256(adj) + adj;
+}
+
+extern "C" size_t simamba_laplacian_topk_workspace_bytes(int B, int G) {
+  if (B < 0 || G < 0) return 0;
+  return sizeof(float) * static_cast<size_t>(B) * G * G;
 }
 
 // raise the dynamic-LDS cap of the two big-tile kernels once per process (thread-safe static init;
@@ -404,16 +415,16 @@ static void ensure_lds_attrs() {
   (void)once;
 }
 
-static int check_groups(int B, int G) {
+static int check_groups(int B, int G, int max_g = kSpecMaxG) {
   if (B < 0) return SIMAMBA_E_SHAPE;
-  if (G < 2 || G > kSpecMaxG) return SIMAMBA_E_GROUPS;
+  if (G < 2 || G > max_g) return SIMAMBA_E_GROUPS;
   return SIMAMBA_OK;
 }
 
 extern "C" int simamba_knn_graph(const float* points, float* adj, void* workspace, size_t ws_bytes, int B, int G,
                                  int F, int knn, float alpha, unsigned flags, void* stream) {
   if (!points || !adj) return SIMAMBA_E_NULLPTR;
-  int rc = check_groups(B, G);
+  int rc = check_groups(B, G, kSpecMaxGLarge);
   if (rc) return rc;
   if (F < 1 || F > 64 || knn < 0 || knn + 1 > G || knn + 1 > kKnnMaxK) return SIMAMBA_E_GROUPS;
   if (B == 0) return SIMAMBA_OK;
@@ -426,6 +437,7 @@ extern "C" int simamba_knn_graph(const float* points, float* adj, void* workspac
     if (e != hipSuccess) return static_cast<int>(e);
     hipLaunchKernelGGL(dist_sum_kernel, dim3(B), dim3(kGraphThreads), 0, s, points, acc, G, F);
   }
+  if (G > kSpecMaxG) return launch_knn_graph_large(points, adj, acc, B, G, F, knn, alpha, flags, s);
   ensure_lds_attrs();
   const size_t smem = sizeof(float) * (static_cast<size_t>(G) * (G + 1) + G * F + 2 * G * kKnnMaxK);
   hipLaunchKernelGGL(knn_graph_kernel, dim3(B), dim3(G * kKnnLanes), smem, s, points, adj, acc, B, G, F, knn, alpha,
@@ -453,6 +465,30 @@ extern "C" int simamba_laplacian_topk(const float* adj, float* evals, float* eve
   return static_cast<int>(hipGetLastError());
 }
 
+constexpr unsigned kSpecKnownFlags = SIMAMBA_SPEC_SYMMETRIC | SIMAMBA_SPEC_SELF_LOOP | SIMAMBA_SPEC_BINARY |
+                                     SIMAMBA_SPEC_MATRIX_SYM | SIMAMBA_SPEC_SMALLEST | SIMAMBA_SPEC_SIGMA_MEAN |
+                                     SIMAMBA_SPEC_LARGE_G;
+
+extern "C" int simamba_laplacian_topk_ex(const float* adj, float* evals, float* evecs, long long* order,
+                                         void* workspace, size_t ws_bytes, int B, int G, int k, unsigned flags,
+                                         void* stream) {
+  if (!adj) return SIMAMBA_E_NULLPTR;
+  if (flags & ~kSpecKnownFlags) return SIMAMBA_E_VARIANT;
+  int rc = check_groups(B, G, kSpecMaxGLarge);
+  if (rc) return rc;
+  const int need = k + ((flags & SIMAMBA_SPEC_MATRIX_SYM) ? 1 : 0);
+  if (k < 0 || need > G) return SIMAMBA_E_GROUPS;
+  const bool large = G > kSpecMaxG || (flags & SIMAMBA_SPEC_LARGE_G);
+  if (!large)
+    return simamba_laplacian_topk(adj, evals, evecs, order, nullptr, nullptr, B, G, k, flags, stream);
+  if (need > kTdMaxSel) return SIMAMBA_E_GROUPS;
+  if (!workspace) return SIMAMBA_E_NULLPTR;
+  if (ws_bytes < simamba_laplacian_topk_workspace_bytes(B, G)) return SIMAMBA_E_WORKSPACE;
+  if (B == 0) return SIMAMBA_OK;
+  EigArgs a{adj, evals, evecs, order, nullptr, nullptr, B, G, k, flags};
+  return launch_laplacian_large_topk(a, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 extern "C" int simamba_spectral_topk(const float* centers, float* evals, float* evecs, long long* order,
                                      void* workspace, size_t ws_bytes, int B, int G, int knn, float alpha, int k,
                                      unsigned flags, void* stream) {
@@ -461,7 +497,11 @@ extern "C" int simamba_spectral_topk(const float* centers, float* evals, float* 
   float* adj = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
   int rc = simamba_knn_graph(centers, adj, workspace, ws_bytes, B, G, 3, knn, alpha, flags, stream);
   if (rc) return rc;
-  return simamba_laplacian_topk(adj, evals, evecs, order, nullptr, nullptr, B, G, k, flags, stream);
+  if (G <= kSpecMaxG)
+    return simamba_laplacian_topk(adj, evals, evecs, order, nullptr, nullptr, B, G, k, flags, stream);
+  const size_t adj_bytes = round_up_256(sizeof(float) * static_cast<size_t>(B) * G * G);
+  return simamba_laplacian_topk_ex(adj, evals, evecs, order, static_cast<char*>(workspace) + 256 + adj_bytes,
+                                   ws_bytes - 256 - adj_bytes, B, G, k, flags & ~SIMAMBA_SPEC_LARGE_G, stream);
 }
 
 extern "C" int simamba_argsort_rows(const float* vals, long long* idx, int rows, int n, void* stream) {

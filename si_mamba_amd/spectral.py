@@ -68,22 +68,40 @@ def _eig(adj, k, smallest, matrix_sym, want_all=True, want_order=False):
     a = adj.detach().float().contiguous()
     B, G, _ = a.shape
     dev = a.device
+    large = G > _lib.SPEC_MAX_G or (_lib.spectral_large_g_forced() and not want_all)
+    if large and want_all:
+        raise NotImplementedError(
+            f"calc_top_k_eigenvalues_eigenvectors[_symmetric] with G = {G} > {_lib.SPEC_MAX_G}: the full spectrum "
+            "(all_vals, all_vecs) is computed up to 128 patches only; above that use spectral_order or the top-k "
+            "route (_eig(..., want_all=False)), which return the k selected eigenpairs and their orders")
     vals = torch.empty(B, k, device=dev, dtype=torch.float32)
     vecs = torch.empty(B, G, k, device=dev, dtype=torch.float32)
     order = torch.empty(B, k, G, device=dev, dtype=torch.int64) if want_order else None
     all_vals = torch.empty(B, G, device=dev, dtype=torch.float32) if want_all else None
     all_vecs = torch.empty(B, G, G, device=dev, dtype=torch.float32) if want_all else None
+    flags = _flags(matrix_sym=matrix_sym, smallest=smallest)
+    if large:
+        # the large-G kernel keeps each sample's G x G matrix in this workspace (torch's caching allocator)
+        nbytes = lib.simamba_laplacian_topk_workspace_bytes(B, G)
+        ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+        _lib.count("spectral_large_g")
+        with torch.cuda.device(dev):
+            rc = lib.simamba_laplacian_topk_ex(_lib.ptr(a), _lib.ptr(vals), _lib.ptr(vecs), _lib.ptr(order),
+                                               _lib.ptr(ws), nbytes, B, G, int(k), flags | _lib.SPEC_LARGE_G,
+                                               _lib.stream_ptr(dev))
+        _lib.check(rc, "simamba_laplacian_topk_ex")
+        return vals, vecs, all_vals, all_vecs, order
     with torch.cuda.device(dev):
         rc = lib.simamba_laplacian_topk(_lib.ptr(a), _lib.ptr(vals), _lib.ptr(vecs), _lib.ptr(order),
                                         _lib.ptr(all_vals), _lib.ptr(all_vecs), B, G, int(k),
-                                        _flags(matrix_sym=matrix_sym, smallest=smallest),
-                                        _lib.stream_ptr(dev))
+                                        flags, _lib.stream_ptr(dev))
     _lib.check(rc, "simamba_laplacian_topk")
     return vals, vecs, all_vals, all_vecs, order
 
 
 def calc_top_k_eigenvalues_eigenvectors(adj_matrices, k, smallest):
-    """reference :717-761 -> (vals (B,k), vecs (B,G,k), all_vals (B,G), all_vecs (B,G,G))."""
+    """reference :717-761 -> (vals (B,k), vecs (B,G,k), all_vals (B,G), all_vecs (B,G,G)).  G <= 128: the full
+    spectrum is part of the result; above, NotImplementedError (use spectral_order or the top-k route)."""
     return _eig(adj_matrices, k, smallest, matrix_sym=False)[:4]
 
 
@@ -121,7 +139,8 @@ def multilevel_travers(eigen_vectors, level):
 
 def spectral_order(center, knn_graph, alpha, k_top_eigenvectors, smallest=True, symmetric=False,
                    self_loop=False, binary=False, matrix="laplacian"):
-    """Fused SAST ordering: centres (B,G,3) -> (vals (B,k), vecs (B,G,k), order (B,k,G) int64).
+    """Fused SAST ordering: centres (B,G,3) -> (vals (B,k), vecs (B,G,k), order (B,k,G) int64), 2 <= G <= 512
+    (above 128 patches on the global-workspace kernels, k (+1) <= 8).
 
     Equivalent to reference :872 + :884 + the k argsorts of :889-890, without materialising
     anything on the host.
