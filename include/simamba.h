@@ -82,7 +82,7 @@ extern "C" {
  *                          dim % 64 == 0, delta_softplus, 16-byte aligned rows and B / C packs, tensors below 2^30
  *                          elements; anything else returns SIMAMBA_E_VARIANT).
  * simamba_scan_ckpt_step() is the library's own choice for a shape (host arithmetic only; the caller still has to
- * meet the alignment rules above or pass _ROW); simamba_scan_ckpt_floats() the size of x_ckpt in floats (0: none
+ * meet the alignment rules above or pass _ROW: simamba_scan_seq_applicable() answers that for a set of operands); simamba_scan_ckpt_floats() the size of x_ckpt in floats (0: none
  * needed, x_ckpt may be NULL).
  */
 #define SIMAMBA_SCAN_CKPT_ROW 128
@@ -96,6 +96,19 @@ int         simamba_scan_num_chunks(int seqlen);
 int         simamba_scan_fwd_auto_variant(int batch, int dim);
 int         simamba_scan_ckpt_step(int batch, int dim, int seqlen, int dstate, int io_dtype);
 long long   simamba_scan_ckpt_floats(int batch, int dim, int seqlen, int dstate, int ckpt_step);
+/* 1 when simamba_selective_scan_fwd (x_ckpt given, ckpt_step _SEQ, variant AUTO) and simamba_selective_scan_bwd(_ex)
+ * with _SEQ would both take these operands, 0 when either would answer SIMAMBA_E_VARIANT: what a caller asks before it
+ * allocates 16-step checkpoints (pass _ROW where the answer is 0).  Host arithmetic only, nothing is launched or
+ * dereferenced; the answer is built from the predicates the two entry points themselves evaluate.
+ *   act_addr_or : bitwise OR of the addresses of every activation-sized operand of both calls (u, delta, out, z,
+ *                 dout, du, ddelta, dz) and of x_ckpt: each has to lie on a 16-byte boundary
+ *   A_addr, B_addr, C_addr : addresses of A, B and C (B / C: a pack = 4 elements of io_dtype; A: 16 bytes)
+ *   strides     : in elements, as in the two calls; 0 => the contiguous default
+ * (still ABI version 9: a symbol added, none changed) */
+int         simamba_scan_seq_applicable(int batch, int dim, int seqlen, int dstate, int io_dtype, int delta_softplus,
+                                        int has_z, size_t act_addr_or, size_t A_addr, size_t B_addr, size_t C_addr,
+                                        long long z_bstride, long long dz_bstride, long long bc_bstride,
+                                        long long bc_nstride, long long bc_tstride);
 
 /*
  * Selective scan forward.

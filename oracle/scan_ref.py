@@ -93,8 +93,8 @@ def selective_scan_closed_form(u, delta, A, B, C, D=None, z=None, delta_bias=Non
     return y
 
 
-def causal_conv1d_ref(x, weight, bias=None, activation=None):
-    """Depthwise causal conv.  x: (B,D,L); weight: (D,W); bias: (D).
+def causal_conv1d_ref(x, weight, bias=None, activation=None, acc_dtype=torch.float32):
+    """Depthwise causal conv.  x: (B,D,L); weight: (D,W); bias: (D).  Computed in ``acc_dtype``.
 
     out[b,d,t] = bias[d] + sum_k weight[d,k] * x[b,d,t-(W-1)+k]  (zero left pad),
     optionally followed by SiLU -- the op the mixer applies before x_proj
@@ -105,8 +105,8 @@ def causal_conv1d_ref(x, weight, bias=None, activation=None):
     io_dtype = x.dtype
     D, W = weight.shape
     L = x.shape[-1]
-    out = F.conv1d(x.float(), weight.float()[:, None, :],
-                   None if bias is None else bias.float(), padding=W - 1, groups=D)[..., :L]
+    out = F.conv1d(x.to(acc_dtype), weight.to(acc_dtype)[:, None, :],
+                   None if bias is None else bias.to(acc_dtype), padding=W - 1, groups=D)[..., :L]
     if activation is not None:
         out = F.silu(out)
     return out.to(io_dtype)
@@ -151,26 +151,45 @@ class MambaRef(nn.Module):
         self.D._no_weight_decay = True
         self.out_proj = nn.Linear(self.d_inner, d_model, bias=bias)
 
-    def forward(self, hidden_states, inference_params=None, io_dtype=None):
+    def forward(self, hidden_states, inference_params=None, io_dtype=None, acc_dtype=torch.float32):
         """``io_dtype=torch.bfloat16`` restates the mixer as it runs under ``torch.autocast`` (the reference's
         pre-training and segmentation runners, tools/runner_pretrain.py:243): upstream ``mamba_inner_fn`` casts
         the three projection weights (and in_proj goes through autocast's linear) to the autocast dtype, every
         GEMM, the conv and the scan read and write that dtype and accumulate in fp32, while conv1d.weight/bias,
         A, D and dt_proj.bias stay fp32.  Here: values are rounded to ``io_dtype`` at exactly those op
         boundaries and carried as fp32 in between, so a device path with the same roundings differs from this
-        only by accumulation order."""
-        r = (lambda t: t) if io_dtype is None else (lambda t: t.to(io_dtype).float())
+        only by accumulation order.
+
+        ``acc_dtype=torch.float64`` (with ``io_dtype=None``) is the high-precision statement of the whole mixer:
+        in_proj, conv + SiLU, x_proj, dt_proj, scan, gate and out_proj all read the (fp32) parameters and the input
+        exactly and compute in float64; the result and, through autograd, every gradient are float64.  The default
+        (float32) leaves the arithmetic above exactly as it was."""
+        acc = acc_dtype
+        if io_dtype is not None and acc != torch.float32:
+            raise ValueError("the autocast restatement (io_dtype) is an fp32 computation")
+        if io_dtype is not None:
+            r = lambda t: t.to(io_dtype).float()                     # noqa: E731
+        else:
+            r = (lambda t: t) if acc == torch.float32 else (lambda t: t.to(acc))
         Bsz, L, _ = hidden_states.shape
         xz = F.linear(r(hidden_states), r(self.in_proj.weight), None if self.in_proj.bias is None
                       else r(self.in_proj.bias))
         xz = r(xz).transpose(1, 2)                                   # (B,2D,L)
         x, z = xz.chunk(2, dim=1)
-        x = r(causal_conv1d_ref(x, self.conv1d.weight[:, 0], self.conv1d.bias, "silu"))
+        x = r(causal_conv1d_ref(x, self.conv1d.weight[:, 0], self.conv1d.bias, "silu", acc_dtype=acc))
         x_dbl = r(F.linear(x.transpose(1, 2), r(self.x_proj.weight)))    # (B,L,R+2N)
         dt, Bm, Cm = torch.split(x_dbl, [self.dt_rank, self.d_state, self.d_state], dim=-1)
         delta = r(dt @ r(self.dt_proj.weight).t()).transpose(1, 2)  # bias goes into the scan
-        y = selective_scan_ref(x, delta, -torch.exp(self.A_log.float()),
-                               Bm.transpose(1, 2), Cm.transpose(1, 2), self.D.float(),
-                               z=z, delta_bias=self.dt_proj.bias.float(), delta_softplus=True)
+        y = selective_scan_ref(x, delta, -torch.exp(self.A_log.to(acc)),
+                               Bm.transpose(1, 2), Cm.transpose(1, 2), self.D.to(acc),
+                               z=z, delta_bias=self.dt_proj.bias.to(acc), delta_softplus=True, acc_dtype=acc)
         return r(F.linear(r(y).transpose(1, 2), r(self.out_proj.weight),
                           None if self.out_proj.bias is None else r(self.out_proj.bias)))
+
+
+def mamba_ref_f64(ref: MambaRef) -> MambaRef:
+    """A float64 copy of ``ref`` (every parameter holds the same value, exactly): called with
+    ``acc_dtype=torch.float64`` on a float64 input it is the high-precision mixer, and autograd leaves float64
+    gradients on its parameters (on the fp32 module they would be rounded to fp32 on the way into ``.grad``)."""
+    import copy
+    return copy.deepcopy(ref).double()

@@ -45,6 +45,8 @@ SIGNATURES = {
     "simamba_scan_fwd_auto_variant": (c_int, [c_int, c_int]),
     "simamba_scan_ckpt_step": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "simamba_scan_ckpt_floats": (_LL, [c_int, c_int, c_int, c_int, c_int]),
+    "simamba_scan_seq_applicable": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_size_t, c_size_t, c_size_t, c_size_t, _LL, _LL, _LL, _LL, _LL]),
     "simamba_selective_scan_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                            c_int, c_int, c_int, c_int, c_int, c_int,
                                            _LL, _LL, _LL, _LL, c_int, c_int, _P]),
@@ -374,22 +376,47 @@ def in_proj_hand_enabled(workgroups, dtype=None):
 IN_PROJ_MIN_WORKGROUPS = 192
 
 
-def scan_plan(batch, dim, seqlen, dstate, dtype, aligned, device, need_grad):
-    """(ckpt_step, x_ckpt or None) for one forward / backward pair.  ``aligned``: the caller's statement that every
-    activation operand is 16-byte aligned with pack-aligned strides (what the sequential backward needs; the library
-    checks again and refuses otherwise)."""
-    import torch
+def scan_plan_step(batch, dim, seqlen, dstate, dtype, *, softplus=True, has_z=True, act_addr_or=0, a_addr=0,
+                   b_addr=0, c_addr=0, z_bs=0, dz_bs=0, bc_strides=(0, 0, 0)):
+    """The checkpoint step of one forward / backward pair: CKPT_SEQ only where the library's row-count rule picks it
+    (simamba_scan_ckpt_step) AND both sequential entry points would take these operands
+    (simamba_scan_seq_applicable: B / C packs and strides per dtype, A, every batch stride and the 2^30 offset
+    bounds); CKPT_ROW -- the row-scan pair, which reads anything -- otherwise.  Host arithmetic only.
+    ``act_addr_or``: OR of the addresses of all activation-sized operands; strides in elements, 0 = contiguous."""
     lib = load()
     code = dtype_code(dtype)
     step = _scan_ckpt[0] or lib.simamba_scan_ckpt_step(batch, dim, seqlen, dstate, code)
-    if step == CKPT_SEQ and not (aligned and dstate == 16 and dim % 64 == 0 and
-                                 seqlen % (4 if code == F32 else 8) == 0):
+    if step == CKPT_SEQ and not lib.simamba_scan_seq_applicable(
+            batch, dim, seqlen, dstate, code, int(bool(softplus)), int(bool(has_z)), act_addr_or, a_addr, b_addr,
+            c_addr, z_bs, dz_bs, *bc_strides):
         step = CKPT_ROW
     if _scan_variant[0] == SCAN_ROWSCAN:
         step = CKPT_ROW                 # an explicit row-scan forward writes 128-step checkpoints only
+    return step
+
+
+def mixer_scan_operands(xz_addr, a_addr, dim, seqlen, dt_rank, dstate, esz, xz_bs):
+    """scan_plan_step's operand description of the fused mixer's scan (mamba_inner.MambaInnerFn), stated before most of
+    the operands exist: z / dz are the second halves of xz (B, 2 dim, L) and of a dxz with the same strides, every
+    other activation-sized tensor is a fresh allocation (16-byte aligned), and B / C are the columns [R, R + N) and
+    [R + N, S) of the token-major x_proj output (B, L, S = R + 2N) -- off a pack boundary, and with a token stride that
+    is no multiple of the pack, when R % 4 != 0 (d_model = 32 * odd).  x_dbl's own base only has to be 16-byte
+    aligned, so B / C are described by their offsets from it."""
+    S = dt_rank + 2 * dstate
+    return dict(softplus=True, has_z=True, act_addr_or=xz_addr | (xz_addr + dim * seqlen * esz), a_addr=a_addr,
+                b_addr=dt_rank * esz, c_addr=(dt_rank + dstate) * esz, z_bs=xz_bs, dz_bs=xz_bs,
+                bc_strides=(seqlen * S, 1, S))
+
+
+def scan_plan(batch, dim, seqlen, dstate, dtype, device, need_grad, **operands):
+    """(ckpt_step, x_ckpt or None) for one forward / backward pair; ``operands``: scan_plan_step's description of what
+    the two calls will be handed (x_ckpt itself comes from the allocator, 16-byte aligned)."""
+    import torch
+    step = scan_plan_step(batch, dim, seqlen, dstate, dtype, **operands)
+    count("scan_ckpt_seq" if step == CKPT_SEQ else "scan_ckpt_row")
     if not need_grad:
         return step, None
-    n = lib.simamba_scan_ckpt_floats(batch, dim, seqlen, dstate, step)
+    n = load().simamba_scan_ckpt_floats(batch, dim, seqlen, dstate, step)
     return step, (torch.empty(n, device=device, dtype=torch.float32) if n else None)
 
 

@@ -167,6 +167,8 @@ int scan_fwd_seq_dispatch(const void* u, const void* delta, const float* A, cons
                           int dt_rank = 0);
 int scan_fwd_seq_bc_mode(const void* B, const void* C, int io_dtype, long long bc_bs, long long bc_ns, long long bc_ts);
 int scan_fwd_seq_mix_c4(int batch, int dim);
+bool scan_bwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, int vec, long long z_bs, long long dz_bs,
+                     bool has_z, int bc_mode, long long bc_ns, long long bc_ts);
 
 // Kernel choice when the caller leaves it to the library (variant == SIMAMBA_SCAN_AUTO).  The lanes-per-channel
 // kernel (scan_fwd_seq.hip) issues 5 VALU per (row, step, state) against ~7 for the row-scan kernel, but a wave
@@ -222,6 +224,50 @@ extern "C" long long simamba_scan_ckpt_floats(int batch, int dim, int seqlen, in
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// What the lanes-per-channel forward assumes beyond the argument checks of simamba_selective_scan_fwd: 16 states,
+// softplus on (the only form the reference's mixer uses), pack-aligned rows (`vec`) and B / C, 32-bit byte offsets.
+// One statement of it for the entry point and for simamba_scan_seq_applicable.
+static bool scan_fwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, int vec, const void* A,
+                            const void* B, const void* C, int io_dtype, long long z_bs, long long bc_bs, long long bc_ns,
+                            long long bc_ts) {
+  const long long rows = static_cast<long long>(batch) * dim;
+  return dstate == kMaxState && softplus && vec && rows * seqlen < (1ll << 30) &&
+         scan_fwd_seq_bc_mode(B, C, io_dtype, bc_bs, bc_ns, bc_ts) != 0 &&
+         static_cast<long long>(batch) * z_bs < (1ll << 30) &&
+         (reinterpret_cast<uintptr_t>(A) & 15u) == 0 && bc_ns >= 0 && bc_ts >= 0 &&
+         (kMaxState - 1) * bc_ns + (seqlen - 1) * bc_ts < (1ll << 30);
+}
+
+// Launch-free statement of what a CKPT_SEQ forward / backward pair accepts (include/simamba.h).  Addresses are only
+// examined for alignment.  Built from the same predicates the two entry points evaluate: scan_fwd_seq_ok above, and
+// scan_fwd_seq_bc_mode + scan_bwd_seq_ok + the A / x_ckpt alignment test of scan_bwd_impl (scan_bwd.hip).
+extern "C" int simamba_scan_seq_applicable(int batch, int dim, int seqlen, int dstate, int io_dtype,
+                                           int delta_softplus, int has_z, size_t act_addr_or, size_t A_addr,
+                                           size_t B_addr, size_t C_addr, long long z_bstride, long long dz_bstride,
+                                           long long bc_bstride, long long bc_nstride, long long bc_tstride) {
+  if (batch <= 0 || dim <= 0 || seqlen <= 0 || batch > 65535) return 0;
+  if (dstate < 1 || dstate > kMaxState) return 0;
+  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return 0;
+  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
+  const long long z_bs = z_bstride ? z_bstride : static_cast<long long>(dim) * seqlen;
+  const long long dz_bs = dz_bstride ? dz_bstride : static_cast<long long>(dim) * seqlen;
+  if (!bc_bstride && !bc_nstride && !bc_tstride) {
+    bc_bstride = static_cast<long long>(dstate) * seqlen; bc_nstride = seqlen; bc_tstride = 1;
+  }
+  // ScanArgs::vec of both entry points: every activation operand (and x_ckpt) on a 16-byte boundary, rows whole packs
+  const int vec = ((seqlen * esz) % 16 == 0) && (act_addr_or & 15u) == 0 &&
+                  (!has_z || ((z_bs * esz) % 16 == 0 && (dz_bs * esz) % 16 == 0));
+  const void* A = reinterpret_cast<const void*>(A_addr);
+  const void* B = reinterpret_cast<const void*>(B_addr);
+  const void* C = reinterpret_cast<const void*>(C_addr);
+  if (!scan_fwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, vec, A, B, C, io_dtype, z_bs, bc_bstride,
+                       bc_nstride, bc_tstride))
+    return 0;
+  const int bc_mode = scan_fwd_seq_bc_mode(B, C, io_dtype, bc_bstride, bc_nstride, bc_tstride);
+  return scan_bwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, vec, z_bs, dz_bs, has_z != 0, bc_mode,
+                         bc_nstride, bc_tstride) ? 1 : 0;
+}
+
 extern "C" int simamba_selective_scan_fwd(const void* u, const void* delta, const float* A, const void* B,
                                           const void* C, const float* D, const void* z,
                                           const float* delta_bias, void* out, float* x_ckpt,
@@ -257,11 +303,8 @@ extern "C" int simamba_selective_scan_fwd(const void* u, const void* delta, cons
   const long long rows = static_cast<long long>(batch) * dim;
   // what the lanes-per-channel kernel assumes: 16 states, softplus on (the only form the reference's mixer uses),
   // pack-aligned rows and B / C, 32-bit byte offsets
-  const bool seq_ok = dstate == kMaxState && delta_softplus && a.vec && rows * seqlen < (1ll << 30) &&
-                      scan_fwd_seq_bc_mode(B, C, io_dtype, a.bc_bs, a.bc_ns, a.bc_ts) != 0 &&
-                      static_cast<long long>(batch) * a.z_bs < (1ll << 30) &&
-                      (reinterpret_cast<uintptr_t>(A) & 15u) == 0 && a.bc_ns >= 0 && a.bc_ts >= 0 &&
-                      (kMaxState - 1) * a.bc_ns + (seqlen - 1) * a.bc_ts < (1ll << 30);
+  const bool seq_ok = scan_fwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, a.vec, A, B, C, io_dtype, a.z_bs,
+                                      a.bc_bs, a.bc_ns, a.bc_ts);
   int v = variant == SIMAMBA_SCAN_AUTO ? auto_variant(rows, batch, dim) : variant;
   // 16-step checkpoints are written by the lanes-per-channel kernels only (four lanes per channel where two would
   // leave the chip short of waves)

@@ -185,8 +185,8 @@ class MambaInnerFn(torch.autograd.Function):
         # (ctx.needs_input_grad is True under torch.no_grad() too: the caller's grad mode comes in as an argument)
         need_grad = grad_mode and any(ctx.needs_input_grad)
         pack = 4 if io == torch.float32 else 8
-        aligned = xz.data_ptr() % 16 == 0 and (xbs * xz.element_size()) % 16 == 0
-        ckpt_step, x_ckpt = _lib.scan_plan(Bsz, Dm, L, N, io, aligned, dev, need_grad)
+        ckpt_step, x_ckpt = _lib.scan_plan(Bsz, Dm, L, N, io, dev, need_grad, **_lib.mixer_scan_operands(
+            xz.data_ptr(), Af.data_ptr(), Dm, L, R, N, xz.element_size(), xbs))
         # Where both scan directions run the lanes-per-channel kernels (scan_plan: CKPT_SEQ) those kernels can form
         # delta = dt_proj.weight @ dt themselves on the matrix pipe, and the (B, D, L) delta tensor never exists: one
         # write and two reads of it per layer and step less (csrc/scan_fwd_seq.hip, csrc/scan_bwd_seq.hip).  Taken
@@ -197,6 +197,7 @@ class MambaInnerFn(torch.autograd.Function):
             # conv1d + SiLU -> x_proj (-> dt_proj) as ONE pass over the x half of xz on the matrix cores
             # (csrc/xdt_proj.hip); x_conv is written as a by-product for the scan and the backward
             x_dbl, delta = xdt_proj_fwd(x_in, xw_c, dtw_c, conv=(cw, cb, x_conv), want_delta=not fuse_dt)
+            _lib.count("xdt_conv_fused")
         else:
             fuse_dt = False
             with torch.cuda.device(dev), _lib.timed("conv1d_fwd", dev):
@@ -205,12 +206,14 @@ class MambaInnerFn(torch.autograd.Function):
             _lib.check(rc, "simamba_causal_conv1d_fwd")
             if xdt_proj_fused_ok(x_conv, xw_c, dtw_c):
                 x_dbl, delta = xdt_proj_fwd(x_conv, xw_c, dtw_c)
+                _lib.count("xdt_fused")
             else:
+                _lib.count("xdt_gemm")
                 x_dbl = _xw(x_conv.transpose(1, 2), xw_c.t())                          # (B, L, S)
                 delta = _wx(dtw_c, x_dbl[:, :, :R].transpose(1, 2))                    # (B, D, L)
         Bv, Cv = x_dbl[:, :, R:R + N], x_dbl[:, :, R + N:]                            # (B, L, N) views
-        if x_dbl.data_ptr() % 16:
-            raise RuntimeError("mamba_inner_fn: unaligned x_proj output")              # the allocator never does this
+        if x_dbl.data_ptr() % 16 or not x_dbl.is_contiguous():
+            raise RuntimeError("mamba_inner_fn: x_proj output not as planned")         # the allocator never does this
 
         y = torch.empty(Bsz, Dm, L, device=dev, dtype=io)
         dtw_k = dtw_c.contiguous() if fuse_dt else None

@@ -58,8 +58,12 @@ class SelectiveScanFn(torch.autograd.Function):
         out = torch.empty_like(uc)
         # ctx.needs_input_grad is True under torch.no_grad() too: the caller's grad mode comes in as an argument
         needs_grad = grad_mode and any(ctx.needs_input_grad)
-        aligned = all(t is None or t.data_ptr() % 16 == 0 for t in (uc, dc, Bc, Cc, zc))
-        ckpt_step, x_ckpt = _lib.scan_plan(batch, dim, L, N, io, aligned and bool(delta_softplus), u.device, needs_grad)
+        # out and the backward's dout / du / ddelta / dz are fresh contiguous allocations (16-byte aligned)
+        addr_or = uc.data_ptr() | dc.data_ptr() | (0 if zc is None else zc.data_ptr())
+        ckpt_step, x_ckpt = _lib.scan_plan(batch, dim, L, N, io, u.device, needs_grad, softplus=delta_softplus,
+                                           has_z=zc is not None, act_addr_or=addr_or, a_addr=Ac.data_ptr(),
+                                           b_addr=Bc.data_ptr(), c_addr=Cc.data_ptr(),
+                                           z_bs=0 if zc is None else zc.stride(0), bc_strides=Bc.stride())
         last = (torch.empty(batch, dim, N, device=u.device, dtype=torch.float32)
                 if return_last_state else None)
         with torch.cuda.device(u.device), _lib.timed("scan_fwd", u.device):

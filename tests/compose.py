@@ -26,6 +26,50 @@ def nerr(got, want):
     return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
+def scaled_err(got, want):
+    """(max |got - want| / max |want|, rms(got - want) / rms(want)) in float64: the error on the tensor's OWN scale, with
+    no floor of 1 -- what a gradient of order 1e-3 needs (``nerr`` lets an absolute 1e-3 through, i.e. all of it).
+    Explicit fallback for a reference that is exactly zero (no scale to divide by): the two ABSOLUTE errors
+    (max |got|, rms(got)); a bound stated on the ratio then demands |got| below that bound outright."""
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    diff = got - want
+    dmax, drms = diff.abs().max().item(), diff.square().mean().sqrt().item()
+    wmax, wrms = want.abs().max().item(), want.square().mean().sqrt().item()
+    if wmax == 0.0:
+        return dmax, drms
+    return dmax / wmax, drms / wrms
+
+
+def mixer_oracle_run(ref, h, dout, io_dtype=None, f64=False):
+    """{'out', 'hidden', <parameter names>}: forward, input gradient and parameter gradients of one CPU oracle run of
+    the mixer ``ref`` (scan_ref.MambaRef): fp32, the bf16-autocast restatement (``io_dtype``), or -- ``f64`` -- the
+    float64 statement of the same weights and inputs, with float64 gradients."""
+    m = scan_ref.mamba_ref_f64(ref) if f64 else ref
+    m.zero_grad(set_to_none=True)
+    hh = (h.double() if f64 else h.clone()).requires_grad_(True)
+    out = m(hh, io_dtype=io_dtype, acc_dtype=torch.float64 if f64 else torch.float32)
+    out.backward(dout.double() if f64 else dout)
+    res = {"out": out.detach(), "hidden": hh.grad}
+    res.update({k: p.grad for k, p in m.named_parameters()})
+    m.zero_grad(set_to_none=True)
+    return res
+
+
+def mixer_scaled_bound_violations(ref, h, dout, got, dtype, names):
+    """The scale-aware bound of tests/test_gpu_mixer_routes.py (see its docstring for the reasoning) on the tensors
+    ``names`` of a device result ``got``: E_dev <= 16 * max(E_ref, 2^-23) in fp32, <= 4 * E_ref under bf16 autocast,
+    both errors measured against the float64 mixer, E_ref being the CPU oracle of that dtype.  -> list of violations."""
+    want = mixer_oracle_run(ref, h, dout, f64=True)
+    cpu = mixer_oracle_run(ref, h, dout, io_dtype=None if dtype == torch.float32 else dtype)
+    factor, floor = (16.0, 2.0 ** -23) if dtype == torch.float32 else (4.0, 0.0)
+    bad = []
+    for k in names:
+        e_ref, e_dev = scaled_err(cpu[k], want[k]), scaled_err(got[k], want[k])
+        print(f"{k}: E_ref {e_ref[0]:.3e} / {e_ref[1]:.3e}  E_dev {e_dev[0]:.3e} / {e_dev[1]:.3e}")
+        bad += [(k, what, d, r) for what, d, r in zip(("max", "rms"), e_dev, e_ref) if not d <= factor * max(r, floor)]
+    return bad
+
+
 def oracle_mixers(layers, d, d_state=16):
     refs = []
     for layer in layers:

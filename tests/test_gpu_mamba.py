@@ -2,10 +2,15 @@
 import pytest
 import torch
 
+from compose import mixer_scaled_bound_violations
 from conftest import load_golden
 from oracle import scan_ref
 
 pytestmark = pytest.mark.gpu
+
+# the three mixer gradients of order 1e-3 .. 1e-2, where ``nerr`` (floor of 1) passes anything: also held to the
+# scale-aware bound of tests/test_gpu_mixer_routes.py
+SMALL_GRADS = ("dt_proj.weight", "dt_proj.bias", "A_log")
 
 
 def nerr(got, want):
@@ -27,6 +32,11 @@ def test_mamba_block_cfg1_golden(device):
     assert nerr(h.grad, torch.from_numpy(g["grad_hidden"])) < 1e-3
     for k, p in m.named_parameters():
         assert nerr(p.grad, torch.from_numpy(g["grad." + k])) < 1e-3, k
+    ref = scan_ref.MambaRef(128)
+    ref.load_state_dict({k: v.detach().cpu() for k, v in m.state_dict().items()})
+    got = {k: p.grad for k, p in m.named_parameters()}
+    assert not mixer_scaled_bound_violations(ref, torch.from_numpy(g["hidden"]), torch.from_numpy(g["dout"]), got,
+                                             torch.float32, SMALL_GRADS)
 
 
 def test_block_and_stack_match_reference_semantics(device):
@@ -111,9 +121,12 @@ def test_fused_inner_fn_equals_composed_ops(shape, dtype, device):
     assert nerr(outs[0][1], outs[1][1]) < tol
     for k in outs[0][2]:
         assert nerr(outs[0][2][k], outs[1][2][k]) < tol, k
+    ref = scan_ref.MambaRef(d)
+    ref.load_state_dict({k: v.cpu() for k, v in fast.state_dict().items()})
+    dout_seen = dout if dtype == torch.float32 else dout.to(dtype).float()       # what the device was handed
+    for route in outs:
+        assert not mixer_scaled_bound_violations(ref, h, dout_seen, route[2], dtype, SMALL_GRADS)
     if dtype == torch.float32:
-        ref = scan_ref.MambaRef(d)
-        ref.load_state_dict({k: v.cpu() for k, v in fast.state_dict().items()})
         hr = h.clone().requires_grad_(True)
         ro = ref(hr)
         ro.backward(dout)
