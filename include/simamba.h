@@ -443,6 +443,20 @@ int simamba_chamfer_bwd(const float* pred, const float* gt, const float* ddist, 
  */
 int simamba_knn_group(const float* points, const float* centers, long long* idx, int batch, int N, int G, int K,
                       void* stream);
+/*
+ * The same for ragged batches: clouds padded to a common N, centre sets padded to a common G.
+ *   len_points  : (batch) int64, device, or NULL (= N everywhere): the candidates of cloud b are its first
+ *                 len_points[b] points; nothing beyond them is read.  The kernel clamps the value to [1, N]; the
+ *                 library never reads it on the host.  With len_points[b] < K (K <= N still holds, else
+ *                 SIMAMBA_E_SHAPE) the first len_points[b] slots of a row are its neighbours and the rest is 0.
+ *   len_centers : (batch) int64, device, or NULL (= G everywhere): rows g >= len_centers[b] are not computed and are
+ *                 written as 0.
+ * Order within a row and the tie rule as above; every row is what simamba_knn_group returns for the cloud alone at its
+ * true length.  With both pointers NULL this is simamba_knn_group (which is that call).  Still ABI version 9: symbols
+ * added, none changed.
+ */
+int simamba_knn_group_ex(const float* points, const float* centers, const long long* len_points,
+                         const long long* len_centers, long long* idx, int batch, int N, int G, int K, void* stream);
 
 /* ---- spectral ordering ---------------------------------------------------------------- */
 #define SIMAMBA_SPEC_SYMMETRIC   0x01u  /* also write A[j,i] for every kNN edge (i,j)          */
@@ -506,6 +520,20 @@ int simamba_spectral_topk(const float* centers, float* evals, float* evecs, long
  */
 int simamba_farthest_point_sample(const float* points, long long* idx, float* centers, int B, int N,
                                   int K, void* stream);
+/*
+ * The same for ragged batches: clouds padded to a common N.
+ *   lengths : (B) int64, device, or NULL (= N everywhere): cloud b consists of its first lengths[b] points; nothing
+ *             beyond them is read, so the padding may hold anything (NaN, Inf).  The kernel clamps the value to
+ *             [1, N]; the library never reads it on the host.
+ *   start   : (B) int64, device, or NULL (= point 0): the first pick of cloud b, 0 <= start[b] < lengths[b] (clamped
+ *             into that range by the kernel).
+ * K <= N as above (else SIMAMBA_E_SHAPE); K > lengths[b] is legal: min(K, lengths[b]) picks are made, the remaining idx
+ * slots are written as -1 and the remaining centers rows as 0.  The picks are those of simamba_farthest_point_sample
+ * on the cloud alone at its true length.  With both pointers NULL this is simamba_farthest_point_sample (which is that
+ * call).  Still ABI version 9.
+ */
+int simamba_farthest_point_sample_ex(const float* points, const long long* lengths, const long long* start,
+                                     long long* idx, float* centers, int B, int N, int K, void* stream);
 
 /* vals (rows, n) fp32 -> idx (rows, n) int64, ascending, ties by index.  n <= 1024. */
 int simamba_argsort_rows(const float* vals, long long* idx, int rows, int n, void* stream);

@@ -11,6 +11,12 @@
 // Distances are accumulated exactly like the torch formulation ((dx^2 + dy^2) + dz^2, no FMA contraction;
 // this file is built with -ffp-contract=off) and ties go to the lower index, so the picks are bit-identical
 // to the oracle's.
+//
+// Ragged batches (kRagged): clouds padded to a common N with lengths[b] real points each.  A workgroup reads its length
+// once; points >= len are never loaded (their lanes carry md = -1 like the lanes beyond N, so whatever the padding
+// holds -- NaN, Inf -- enters no arithmetic), the first pick is start[b] instead of point 0 when given, min(K, len)
+// picks are made and the remaining idx / centers slots are written as -1 / 0, pytorch3d's padding.  The picks are
+// those of the unpadded cloud run alone.  The kRagged = false instantiations are the fixed-length kernels unchanged.
 #include "common.h"
 
 namespace simamba {
@@ -26,25 +32,33 @@ __device__ __forceinline__ void argmax_combine(float& v, int& i, float ov, int o
   if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
 
+template <bool kRagged>
 __global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restrict__ pts, long long* __restrict__ idx,
-                                                          float* __restrict__ centers, int N, int K) {
+                                                          float* __restrict__ centers, int N, int K,
+                                                          const long long* __restrict__ lengths,
+                                                          const long long* __restrict__ start) {
   __shared__ float sCur[3];
   __shared__ float sVal[kFpsThreads / 64];
   __shared__ int sIdx[kFpsThreads / 64];
   const float* P = pts + static_cast<size_t>(blockIdx.x) * N * 3;
   const int tid = threadIdx.x;
+  int len = N, cur = 0;
+  if constexpr (kRagged) {
+    if (lengths) len = static_cast<int>(min(max(lengths[blockIdx.x], 1LL), static_cast<long long>(N)));
+    if (start) cur = static_cast<int>(min(max(start[blockIdx.x], 0LL), static_cast<long long>(len - 1)));
+  }
+  const int picks = kRagged ? min(K, len) : K;
   float px[kFpsMaxPer], py[kFpsMaxPer], pz[kFpsMaxPer], md[kFpsMaxPer];
 #pragma unroll
   for (int k = 0; k < kFpsMaxPer; ++k) {
     const int i = tid + k * kFpsThreads;
-    const bool ok = i < N;
+    const bool ok = i < len;
     px[k] = ok ? P[3 * i] : 0.f;
     py[k] = ok ? P[3 * i + 1] : 0.f;
     pz[k] = ok ? P[3 * i + 2] : 0.f;
     md[k] = ok ? __builtin_inff() : -1.f;    // padding never wins the arg-max
   }
-  int cur = 0;
-  for (int r = 0; r < K; ++r) {
+  for (int r = 0; r < picks; ++r) {
     if (tid == 0) {
       idx[static_cast<size_t>(blockIdx.x) * K + r] = cur;
       const float cx = P[3 * cur], cy = P[3 * cur + 1], cz = P[3 * cur + 2];
@@ -60,7 +74,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restric
     int bi = 0x7fffffff;
 #pragma unroll
     for (int k = 0; k < kFpsMaxPer; ++k) {
-      if (k * kFpsThreads < N) {
+      if (k * kFpsThreads < len) {
         const float dx = px[k] - cx, dy = py[k] - cy, dz = pz[k] - cz;
         const float d = (dx * dx + dy * dy) + dz * dz;
         md[k] = fminf(md[k], d);
@@ -81,30 +95,47 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restric
     for (int w = 1; w < kFpsThreads / 64; ++w) argmax_combine(bv, bi, sVal[w], sIdx[w]);
     cur = bi;
   }
+  if constexpr (kRagged) {                       // fewer points than picks: pytorch3d's padding
+    for (int r = picks + tid; r < K; r += kFpsThreads) {
+      idx[static_cast<size_t>(blockIdx.x) * K + r] = -1;
+      if (centers) {
+        float* c = centers + (static_cast<size_t>(blockIdx.x) * K + r) * 3;
+        c[0] = 0.f; c[1] = 0.f; c[2] = 0.f;
+      }
+    }
+  }
 }
 
 // The same rounds as fps_kernel, 1024 lanes x 8 points.  A copy rather than a template shared with fps_kernel: the
 // shared form changes fps_kernel's register allocation, and the N <= 4096 path is kept exactly as it was.
+template <bool kRagged>
 __global__ __launch_bounds__(kFpsWideThreads) void fps_wide_kernel(const float* __restrict__ pts,
                                                                    long long* __restrict__ idx,
-                                                                   float* __restrict__ centers, int N, int K) {
+                                                                   float* __restrict__ centers, int N, int K,
+                                                                   const long long* __restrict__ lengths,
+                                                                   const long long* __restrict__ start) {
   __shared__ float sCur[3];
   __shared__ float sVal[kFpsWideThreads / 64];
   __shared__ int sIdx[kFpsWideThreads / 64];
   const float* P = pts + static_cast<size_t>(blockIdx.x) * N * 3;
   const int tid = threadIdx.x;
+  int len = N, cur = 0;
+  if constexpr (kRagged) {
+    if (lengths) len = static_cast<int>(min(max(lengths[blockIdx.x], 1LL), static_cast<long long>(N)));
+    if (start) cur = static_cast<int>(min(max(start[blockIdx.x], 0LL), static_cast<long long>(len - 1)));
+  }
+  const int picks = kRagged ? min(K, len) : K;
   float px[kFpsWidePer], py[kFpsWidePer], pz[kFpsWidePer], md[kFpsWidePer];
 #pragma unroll
   for (int k = 0; k < kFpsWidePer; ++k) {
     const int i = tid + k * kFpsWideThreads;
-    const bool ok = i < N;
+    const bool ok = i < len;
     px[k] = ok ? P[3 * i] : 0.f;
     py[k] = ok ? P[3 * i + 1] : 0.f;
     pz[k] = ok ? P[3 * i + 2] : 0.f;
     md[k] = ok ? __builtin_inff() : -1.f;    // padding never wins the arg-max
   }
-  int cur = 0;
-  for (int r = 0; r < K; ++r) {
+  for (int r = 0; r < picks; ++r) {
     if (tid == 0) {
       idx[static_cast<size_t>(blockIdx.x) * K + r] = cur;
       const float cx = P[3 * cur], cy = P[3 * cur + 1], cz = P[3 * cur + 2];
@@ -120,7 +151,7 @@ __global__ __launch_bounds__(kFpsWideThreads) void fps_wide_kernel(const float* 
     int bi = 0x7fffffff;
 #pragma unroll
     for (int k = 0; k < kFpsWidePer; ++k) {
-      if (k * kFpsWideThreads < N) {
+      if (k * kFpsWideThreads < len) {
         const float dx = px[k] - cx, dy = py[k] - cy, dz = pz[k] - cz;
         const float d = (dx * dx + dy * dy) + dz * dz;
         md[k] = fminf(md[k], d);
@@ -141,22 +172,46 @@ __global__ __launch_bounds__(kFpsWideThreads) void fps_wide_kernel(const float* 
     for (int w = 1; w < kFpsWideThreads / 64; ++w) argmax_combine(bv, bi, sVal[w], sIdx[w]);
     cur = bi;
   }
+  if constexpr (kRagged) {                       // fewer points than picks: pytorch3d's padding
+    for (int r = picks + tid; r < K; r += kFpsWideThreads) {
+      idx[static_cast<size_t>(blockIdx.x) * K + r] = -1;
+      if (centers) {
+        float* c = centers + (static_cast<size_t>(blockIdx.x) * K + r) * 3;
+        c[0] = 0.f; c[1] = 0.f; c[2] = 0.f;
+      }
+    }
+  }
 }
 
 }  // namespace simamba
 
 using namespace simamba;
 
-extern "C" int simamba_farthest_point_sample(const float* points, long long* idx, float* centers, int B, int N, int K,
-                                             void* stream) {
+namespace {
+
+template <bool kRagged>
+void launch_fps(const float* points, const long long* lengths, const long long* start, long long* idx, float* centers,
+                int B, int N, int K, hipStream_t s) {
+  if (N <= kFpsThreads * kFpsMaxPer)
+    hipLaunchKernelGGL(fps_kernel<kRagged>, dim3(B), dim3(kFpsThreads), 0, s, points, idx, centers, N, K, lengths, start);
+  else
+    hipLaunchKernelGGL(fps_wide_kernel<kRagged>, dim3(B), dim3(kFpsWideThreads), 0, s, points, idx, centers, N, K, lengths,
+                       start);
+}
+
+}  // namespace
+
+extern "C" int simamba_farthest_point_sample_ex(const float* points, const long long* lengths, const long long* start,
+                                                long long* idx, float* centers, int B, int N, int K, void* stream) {
   if (B < 0 || N <= 0 || K < 0 || K > N || N > kFpsWideThreads * kFpsWidePer) return SIMAMBA_E_SHAPE;
   if (B == 0 || K == 0) return SIMAMBA_OK;
   if (!points || !idx) return SIMAMBA_E_NULLPTR;
-  if (N <= kFpsThreads * kFpsMaxPer)
-    hipLaunchKernelGGL(fps_kernel, dim3(B), dim3(kFpsThreads), 0, static_cast<hipStream_t>(stream), points, idx,
-                       centers, N, K);
-  else
-    hipLaunchKernelGGL(fps_wide_kernel, dim3(B), dim3(kFpsWideThreads), 0, static_cast<hipStream_t>(stream), points,
-                       idx, centers, N, K);
+  if (lengths || start) launch_fps<true>(points, lengths, start, idx, centers, B, N, K, static_cast<hipStream_t>(stream));
+  else launch_fps<false>(points, nullptr, nullptr, idx, centers, B, N, K, static_cast<hipStream_t>(stream));
   return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_farthest_point_sample(const float* points, long long* idx, float* centers, int B, int N, int K,
+                                             void* stream) {
+  return simamba_farthest_point_sample_ex(points, nullptr, nullptr, idx, centers, B, N, K, stream);
 }

@@ -254,7 +254,7 @@ class Point_MAE_Mamba(nn.Module):
 
     def forward(self, pts, noaug=False, vis=False, tau=None, use_wavelets=False, use_diff_sort=False,
                 ret_policy=False, ret_only_policy=False, save_pts_dir=None, epoch=None, orders=None, mask=None,
-                return_parts=False, **kwargs):
+                return_parts=False, lengths=None, **kwargs):
         """Reference signature (models/point_mamba.py:3053-3054; the pre-training runner calls
         ``base_model(points, tau=tau, ret_policy=False, use_wavelets=True)``, tools/runner_pretrain.py:244).
         Built: the spectral-order route of the published method.  The wavelet-traversal, learned-permutation,
@@ -268,6 +268,9 @@ class Point_MAE_Mamba(nn.Module):
                 raise NotImplementedError(f"Point_MAE_Mamba.forward({name}=...): that branch of reference "
                                           "models/point_mamba.py:3053-3219 is outside the SI-Mamba hot-path scope; "
                                           "the spectral-order route runs with the argument left at its default")
+        if lengths is not None:
+            raise NotImplementedError("Point_MAE_Mamba.forward(lengths=...): ragged batches are built for PointMamba "
+                                      "only; pre-training takes clouds of one length")
         if kwargs:
             raise TypeError(f"Point_MAE_Mamba.forward: unexpected arguments {sorted(kwargs)}")
         neighborhood, center, _ = self.group_divider(pts)

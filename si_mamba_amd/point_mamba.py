@@ -32,6 +32,11 @@ class Group(nn.Module):
     grouping.knn_group, the counterparts of the pytorch3d calls at :93 and :96; clouds of up to 8192 points,
     larger ones and CPU tensors take cdist + topk).  ``fps_fn`` can be swapped (bench.py's CPU baseline plugs
     the oracle in).
+
+    ``lengths`` (B,): ragged batches, clouds padded to a common N with ``lengths[b]`` real points each.  The padding is
+    never read, and every cloud's patches are those of the cloud alone at its true length.  Every cloud needs at least
+    ``max(num_group, group_size)`` points, so that all G patches of M points exist and everything downstream keeps its
+    fixed shapes; that is checked with one host read of ``lengths.min()`` (not during a stream capture).
     """
 
     def __init__(self, num_group, group_size):
@@ -41,7 +46,19 @@ class Group(nn.Module):
         self.fps_fn = grouping.sample_farthest_points
 
     @torch.no_grad()
-    def _indices(self, xyz):
+    def _indices(self, xyz, lengths=None):
+        if lengths is not None:
+            if not (xyz.is_cuda and xyz.shape[1] <= 8192):
+                raise NotImplementedError("Group: lengths are taken by the HIP kernels only (a ROCm device, clouds of "
+                                          "up to 8192 points)")
+            need = max(self.num_group, self.group_size)
+            if not torch.cuda.is_current_stream_capturing():
+                shortest = int(lengths.min())
+                if shortest < need:
+                    raise ValueError(f"Group: the shortest cloud has {shortest} points, every cloud needs at least "
+                                     f"{need} (max of num_group = {self.num_group} and group_size = {self.group_size})")
+            center, _ = self.fps_fn(xyz, self.num_group, lengths=lengths)
+            return center, grouping.knn_group(center, xyz, self.group_size, lengths=lengths)
         center, _ = self.fps_fn(xyz, self.num_group)
         if xyz.is_cuda and xyz.shape[1] <= 8192:
             return center, grouping.knn_group(center, xyz, self.group_size)
@@ -49,9 +66,9 @@ class Group(nn.Module):
         nn_idx = d.topk(self.group_size, dim=-1, largest=False, sorted=False)[1]
         return center, nn_idx
 
-    def forward(self, xyz):
+    def forward(self, xyz, *, lengths=None):
         B, N, _ = xyz.shape
-        center, nn_idx = self._indices(xyz)
+        center, nn_idx = self._indices(xyz, lengths)
         flat = (nn_idx + torch.arange(B, device=xyz.device).view(-1, 1, 1) * N).view(-1)
         nb = xyz.reshape(B * N, -1)[flat].view(B, self.num_group, self.group_size, 3).contiguous()
         return nb - center.unsqueeze(2), center, nb
@@ -207,7 +224,7 @@ class PointMamba(nn.Module):
         t, p, _, _ = spectral.hlt_assemble(tokens, pos, center, vecs, self.k_top_eigenvectors, rand=rand)
         return t, p
 
-    def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None):
+    def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None, *, lengths=None):
         """Reference signature (models/point_mamba.py:843; the runner calls
         ``base_model(points, gt=None, tau=None, use_wavelets=True)``, tools/runner_finetune.py:201).  Built: the
         published spectral route (``tau is None``, ``use_wavelets=False``).  ``gt`` given -> ``(logits, policy)``
@@ -215,7 +232,8 @@ class PointMamba(nn.Module):
         (``tau``) and wavelet-traversal (``use_wavelets``) research branches are outside the hot-path scope
         (the wavelet branch calls a function the reference never defines, :879) and are
         refused by name rather than silently replaced.  ``save_pts_dir`` / ``epoch`` only feed the reference's
-        point-dump visualisation and are ignored."""
+        point-dump visualisation and are ignored.  ``lengths`` (B,), keyword-only and not in the reference: the point
+        count of every cloud of a padded batch (``Group``); only the tokeniser sees it."""
         if tau is not None:
             raise NotImplementedError("PointMamba.forward(tau=...): the learned-permutation branch (reference "
                                       "models/point_mamba.py:902-952) is outside the SI-Mamba hot-path scope")
@@ -226,7 +244,7 @@ class PointMamba(nn.Module):
         want_policy = gt is not None
         if want_policy and self.method != "SAST":
             raise NotImplementedError("PointMamba.forward(gt=...): the reference defines `policy` on the SAST route only")
-        neighborhood, center, _ = self.group_divider(pts)
+        neighborhood, center, _ = self.group_divider(pts, lengths=lengths)
         order = spec = None
         overlap = center.is_cuda and self.method == "SAST"
         # The eigen-ordering depends only on the centres and is latency-bound on B of the 256 CUs: run it

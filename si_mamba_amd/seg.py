@@ -195,7 +195,11 @@ class PartSegMamba(nn.Module):
                 torch.gather(center, 1, ex.expand(-1, -1, 3)))
 
     # ---- forward -------------------------------------------------------------------------------------------------
-    def forward(self, pts, cls_label):
+    def forward(self, pts, cls_label, *, lengths=None):
+        if lengths is not None:
+            raise NotImplementedError("PartSegMamba.forward(lengths=...): the per-point head runs BatchNorm over all "
+                                      "points of the batch, so padded points would enter its statistics; ragged "
+                                      "batches are built for PointMamba only")
         B, _, N = pts.shape
         pts = pts.transpose(-1, -2).contiguous()                                # (B, N, 3)
         neighborhood, center, _ = self.group_divider(pts)

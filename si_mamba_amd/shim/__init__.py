@@ -11,7 +11,8 @@ try/except falls back to plain ``nn.LayerNorm`` (the only path its configs use).
 ``install_shim(pytorch3d=True)`` additionally registers ``pytorch3d.ops`` / ``pytorch3d.loss`` stand-ins for the
 three pytorch3d entry points the reference calls (models/point_mamba.py:24, :37;
 part_segmentation/models/pt_mamba.py:13): ``sample_farthest_points``, ``knn_points`` and ``chamfer_distance``,
-on the HIP kernels, with the call forms and return shapes the reference uses.
+on the HIP kernels, with the call forms and return shapes the reference uses, plus the ``lengths`` /
+``random_start_point`` arguments of the first two for ragged batches (clouds padded to a common point count).
 """
 from __future__ import annotations
 
@@ -70,23 +71,35 @@ def _install_pytorch3d(_mod):
 
     import torch
 
-    from .. import grouping, mae
+    from .. import _lib, grouping, mae
 
     KNN = collections.namedtuple("_KNN", ["dists", "idx", "knn"])
 
     def sample_farthest_points(points, lengths=None, K=50, random_start_point=False):
-        if lengths is not None or random_start_point:
-            raise NotImplementedError("sample_farthest_points shim: fixed-length clouds, start at point 0")
-        return grouping.sample_farthest_points(points, K)
+        """(points (B,K,3), idx (B,K)); with ``lengths`` a cloud shorter than K is padded with 0 / -1."""
+        start = None
+        if random_start_point:
+            _lib.require_gpu(points, "sample_farthest_points")
+            B, N = points.shape[:2]
+            n = torch.full((B,), N, device=points.device) if lengths is None else lengths.to(points.device)
+            start = (torch.rand(B, device=points.device) * n).floor().long()
+            start = torch.minimum(start, n.long() - 1)               # rand(B) * n can round up to n
+        return grouping.sample_farthest_points(points, K, lengths=lengths, start_idx=start)
 
     def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False,
                    return_sorted=True):
-        if lengths1 is not None or lengths2 is not None or norm != 2 or return_nn:
-            raise NotImplementedError("knn_points shim: fixed-length clouds, squared L2, indices and distances only")
-        idx = grouping.knn_group(p1, p2, K)                                        # ascending: also valid for sorted
+        if norm != 2 or return_nn:
+            raise NotImplementedError("knn_points shim: squared L2, indices and distances only")
+        idx = grouping.knn_group(p1, p2, K, lengths=lengths2, center_lengths=lengths1)   # ascending: valid for sorted
         nb = torch.gather(p2.unsqueeze(1).expand(-1, p1.shape[1], -1, -1), 2,
                           idx.unsqueeze(-1).expand(-1, -1, -1, p2.shape[-1]))
-        return KNN(dists=((nb - p1.unsqueeze(2)) ** 2).sum(-1), idx=idx, knn=None)
+        dists = ((nb - p1.unsqueeze(2)) ** 2).sum(-1)
+        if lengths2 is not None:                                     # slots without a neighbour: idx 0, distance 0
+            dists = dists.masked_fill(torch.arange(K, device=idx.device) >= lengths2.view(-1, 1, 1), 0)
+        if lengths1 is not None:
+            dists = dists.masked_fill(torch.arange(p1.shape[1], device=idx.device).view(1, -1, 1)
+                                      >= lengths1.view(-1, 1, 1), 0)
+        return KNN(dists=dists, idx=idx, knn=None)
 
     def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
                          batch_reduction="mean", point_reduction="mean", norm=2, single_directional=False,
