@@ -81,6 +81,9 @@ def selective_scan_closed_form(u, delta, A, B, C, D=None, z=None, delta_bias=Non
     # gap[b,d,t,s] = sum_{s<m<=t} delta_m  (t >= s)
     gap = cs[:, :, :, None] - cs[:, :, None, :]
     mask = torch.tril(torch.ones(L, L, dtype=torch.bool))
+    # masked before the exponential: above the diagonal the gap is negative and exp(gap * A) overflows for a fast
+    # decay (delta * A below -30 per step), and inf * 0 is NaN
+    gap = torch.where(mask[None, None], gap, torch.zeros_like(gap))
     w = torch.exp(gap[..., None] * Af[None, :, None, None, :])       # (B,D,t,s,N)
     w = w * mask[None, None, :, :, None]
     src = (dt * uf)[:, :, None, :, None] * Bf.permute(0, 2, 1)[:, None, None, :, :]

@@ -208,8 +208,8 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_bwd_kernel(ScanArgs p) {
       float sD = 0.f, sBias = 0.f;
 #pragma unroll
       for (int i = 0; i < kItems; ++i) {
-        // d softplus(x)/dx = sigmoid(x) = 1 - exp(-softplus(x)); padded steps carry no gradient
-        const float sgm = p.softplus ? (1.f - fast_exp2(-dl[i] * kLog2e)) : 1.f;
+        // d softplus(x)/dx = sigmoid(x), from softplus(x); padded steps carry no gradient
+        const float sgm = p.softplus ? softplus_grad_from_sp(dl[i]) : 1.f;
         const float gd = fmaf(u[i], dxs[i], kLn2 * dda[i]) * sgm;
         ddl[i] = gd;
         sBias += gd;

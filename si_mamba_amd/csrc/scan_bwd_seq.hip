@@ -83,7 +83,7 @@ __device__ __forceinline__ void bs_store4(T* __restrict__ base, unsigned boff, c
 // softplus of x handed over as x * log2(e); see scan_fwd_seq.hip
 __device__ __forceinline__ float bs_softplus_log2(float x2) {
   const float e = fast_exp2(x2);
-  float sp = fast_log2(1.f + e) * kLn2;
+  float sp = log1p_exp(e);
   sp = (x2 < -15.f * kLog2e) ? e : sp;
   return (x2 > 20.f * kLog2e) ? x2 * kLn2 : sp;
 }
@@ -425,6 +425,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
       // (2) the adjoint, right to left
       {
         float d4[4], u4[4], y4[4];
+        float hin[4] = {0.f, 0.f, 0.f, 0.f};                 // the state that entered the segment, re-read for step 0
 #ifndef SIMAMBA_BWDSEQ_NOPREFETCH
         float4 b4n = *reinterpret_cast<const float4*>(bcp + (kBsSeg - 1) * 32);
         float4 c4n = *reinterpret_cast<const float4*>(bcp + (kBsSeg - 1) * 32 + 16);
@@ -443,6 +444,10 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
           // the state entering the next (left) segment is requested once half of the h registers are free again:
           // the second half of this pass covers its latency, and nothing older is pending in the memory queue
           if (i == kBsSeg / 2 - 1) load_state(ts - kBsSeg);
+          if (i == 1 && ts > 0) {                            // one step ahead of its use (earlier costs spills); a cache hit
+            const float4 h4 = *reinterpret_cast<const float4*>(ckl + static_cast<size_t>(ts / kBsSeg - 1) * D * kMaxState);
+            hin[0] = h4.x; hin[1] = h4.y; hin[2] = h4.z; hin[3] = h4.w;
+          }
 #ifndef SIMAMBA_BWDSEQ_NOPREFETCH
           const float vB[4] = {b4n.x, b4n.y, b4n.z, b4n.w};
           const float vC[4] = {c4n.x, c4n.y, c4n.z, c4n.w};
@@ -467,9 +472,11 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
             const float g = fmaf(vC[j], dy, ga[j]);          // g_t = a_{t+1} g_{t+1} + C_t dy_t
             const float a = fast_exp2(dl * A2[j]);
             ga[j] = g * a;
-            // g_t a_t h_{t-1}; at the segment's first step a_t h_{t-1} = h_t - x_t B_t (the recurrence itself), so the
-            // state that entered the segment need not stay in registers through both passes
-            const float qv = (i > 0) ? ga[j] * H[i > 0 ? i - 1 : 0][j] : g * fmaf(-xx, vB[j], H[0][j]);
+            // g_t a_t h_{t-1}.  At the segment's first step h_{t-1} is the state that entered the segment: it does not
+            // stay in registers through both passes, and it is not recovered as h_t - x_t B_t either -- for a fast
+            // decay a_t h_{t-1} is 1e-9 .. 0 of h_t and that difference is the rounding of h_t (dA of such a channel
+            // came out 1e8 times its value) -- but read again from the forward's checkpoint a few steps ahead
+            const float qv = ga[j] * ((i > 0) ? H[i > 0 ? i - 1 : 0][j] : hin[j]);
             dda = fmaf(A2[j], qv, dda);
             dAacc[j] = fmaf(dl, qv, dAacc[j]);
             dxs = fmaf(g, vB[j], dxs);
@@ -516,8 +523,8 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
         float dd[4], dsum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          // d softplus(x)/dx = sigmoid(x) = 1 - exp(-softplus(x)); padded steps (delta = 0) carry no gradient
-          dd[i] = t2[i] * (1.f - fast_exp2(-dl[i] * kLog2e));
+          // d softplus(x)/dx = sigmoid(x), from softplus(x); padded steps (delta = 0) carry no gradient
+          dd[i] = t2[i] * softplus_grad_from_sp(dl[i]);
           dsum += dd[i];
         }
         const unsigned ro = row_off(l, j) + t0 * kEsz;

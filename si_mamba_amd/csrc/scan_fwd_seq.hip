@@ -114,7 +114,7 @@ __device__ __forceinline__ void store4(T* __restrict__ base, unsigned boff, cons
 // 1 + e loses.  x2 = -inf-like (-1e30 from a padded pack) gives e = 0 and exactly 0.
 __device__ __forceinline__ float softplus_log2(float x2) {
   const float e = fast_exp2(x2);
-  float sp = fast_log2(1.f + e) * kLn2;
+  float sp = log1p_exp(e);
   sp = (x2 < -15.f * kLog2e) ? e : sp;
   return (x2 > 20.f * kLog2e) ? x2 * kLn2 : sp;
 }
