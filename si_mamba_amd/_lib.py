@@ -223,24 +223,39 @@ def kernel_times():
     return out
 
 
-_scan_variant = [SCAN_AUTO]
+class _Override:
+    """A module-level one-element list (``cell``, read through ``[0]``) and the context manager that sets it for a block;
+    ``coerce`` maps the argument to the value stored."""
+    cell = None
+    coerce = bool
 
-
-class scan_variant:
-    """Context manager for benchmarks and parity tests: the forward-scan kernel the Python ops request from the
-    library inside the block (an explicit argument of simamba_selective_scan_fwd -- the library itself holds no
-    state and reads no environment).  Production code never enters it: SCAN_AUTO lets the library choose."""
-
-    def __init__(self, variant):
-        self.v, self.prev = int(variant), None
+    def __init__(self, on):
+        self.v, self.prev = self.coerce(on), None
 
     def __enter__(self):
-        self.prev, _scan_variant[0] = _scan_variant[0], self.v
+        self.prev, self.cell[0] = self.cell[0], self.v
         return self
 
     def __exit__(self, *exc):
-        _scan_variant[0] = self.prev
+        self.cell[0] = self.prev
         return False
+
+
+def _tristate(on):
+    return None if on is None else bool(on)
+
+
+_scan_variant = [SCAN_AUTO]
+
+
+class scan_variant(_Override):
+    """Context manager for benchmarks and parity tests: the forward-scan kernel the Python ops request from the
+    library inside the block (an explicit argument of simamba_selective_scan_fwd -- the library itself holds no
+    state and reads no environment).  Production code never enters it: SCAN_AUTO lets the library choose."""
+    cell, coerce = _scan_variant, int
+
+    def __init__(self, variant):
+        super().__init__(variant)
 
 
 def current_scan_variant():
@@ -250,40 +265,26 @@ def current_scan_variant():
 _scan_ckpt = [0]
 
 
-class scan_ckpt:
+class scan_ckpt(_Override):
     """Context manager for benchmarks and parity tests: the checkpoint layout (CKPT_ROW / CKPT_SEQ, i.e. the backward
     kernel) the Python ops request instead of the library's own choice.  Production code never enters it."""
+    cell, coerce = _scan_ckpt, int
 
     def __init__(self, step):
-        self.v, self.prev = int(step), None
-
-    def __enter__(self):
-        self.prev, _scan_ckpt[0] = _scan_ckpt[0], self.v
-        return self
-
-    def __exit__(self, *exc):
-        _scan_ckpt[0] = self.prev
-        return False
+        super().__init__(step)
 
 
 _spectral_large_g = [False]
 
 
-class spectral_large_g:
+class spectral_large_g(_Override):
     """Context manager for parity tests and benchmarks: top-k eigenpairs through the large-G kernel
     (simamba_laplacian_topk_ex with SPEC_LARGE_G) at G <= 128 too, where the library otherwise runs the LDS-resident
     tridiagonal kernel.  Production code never enters it: above 128 patches the large-G kernel is the only route."""
+    cell = _spectral_large_g
 
     def __init__(self, on=True):
-        self.v, self.prev = bool(on), None
-
-    def __enter__(self):
-        self.prev, _spectral_large_g[0] = _spectral_large_g[0], self.v
-        return self
-
-    def __exit__(self, *exc):
-        _spectral_large_g[0] = self.prev
-        return False
+        super().__init__(on)
 
 
 def spectral_large_g_forced():
@@ -298,22 +299,11 @@ def count(name):
     counters[name] = counters.get(name, 0) + 1
 
 
-
-class scan_fuse_dt:
+class scan_fuse_dt(_Override):
     """Context manager for benchmarks and parity tests: force the mixer to let the scan kernels form delta themselves
     (simamba_selective_scan_dt_fwd / _bwd) wherever they can (True), or to materialise it as upstream does (False).
     Production never enters it and gets the measured default of fuse_dt_enabled()."""
-
-    def __init__(self, on):
-        self.v, self.prev = (None if on is None else bool(on)), None
-
-    def __enter__(self):
-        self.prev, _fuse_dt[0] = _fuse_dt[0], self.v
-        return self
-
-    def __exit__(self, *exc):
-        _fuse_dt[0] = self.prev
-        return False
+    cell, coerce = _fuse_dt, staticmethod(_tristate)
 
 
 def fuse_dt_enabled(dtype):
@@ -330,40 +320,20 @@ _fuse_out_norm = [True]
 _hand_in_proj = [None]   # None: the measured default (in_proj_hand_enabled); True / False: forced
 
 
-class fuse_out_norm:
+class fuse_out_norm(_Override):
     """Context manager for benchmarks and parity tests: let MixerModel.forward apply out_proj fused with the next block's
     add + LayerNorm (out_norm.py; the default wherever the kernel's shapes apply) or op by op as the reference does."""
-
-    def __init__(self, on):
-        self.v, self.prev = bool(on), None
-
-    def __enter__(self):
-        self.prev, _fuse_out_norm[0] = _fuse_out_norm[0], self.v
-        return self
-
-    def __exit__(self, *exc):
-        _fuse_out_norm[0] = self.prev
-        return False
+    cell = _fuse_out_norm
 
 
 def fuse_out_norm_enabled():
     return _fuse_out_norm[0]
 
 
-class hand_in_proj:
+class hand_in_proj(_Override):
     """Context manager for benchmarks and parity tests: in_proj through the hand-written bf16 kernel
     (simamba_in_proj_fwd) wherever its shapes apply (True) or through the library GEMM (False)."""
-
-    def __init__(self, on):
-        self.v, self.prev = (None if on is None else bool(on)), None
-
-    def __enter__(self):
-        self.prev, _hand_in_proj[0] = _hand_in_proj[0], self.v
-        return self
-
-    def __exit__(self, *exc):
-        _hand_in_proj[0] = self.prev
-        return False
+    cell, coerce = _hand_in_proj, staticmethod(_tristate)
 
 
 def in_proj_hand_enabled(workgroups, dtype=None):
@@ -450,22 +420,12 @@ def set_deterministic(on):
     fixed-order sum instead of float atomics; bitwise reproducible gradients).  ``True`` / ``False`` force it on / off,
     ``None`` (the default) follows ``torch.use_deterministic_algorithms``.  ``torch.backends.cudnn.deterministic`` is
     not consulted."""
-    _deterministic[0] = None if on is None else bool(on)
+    _deterministic[0] = _tristate(on)
 
 
-class deterministic:
+class deterministic(_Override):
     """Context manager form of set_deterministic: ``with deterministic(True): loss.backward()``."""
-
-    def __init__(self, on):
-        self.v, self.prev = (None if on is None else bool(on)), None
-
-    def __enter__(self):
-        self.prev, _deterministic[0] = _deterministic[0], self.v
-        return self
-
-    def __exit__(self, *exc):
-        _deterministic[0] = self.prev
-        return False
+    cell, coerce = _deterministic, staticmethod(_tristate)
 
 
 def deterministic_enabled():
@@ -477,11 +437,15 @@ def deterministic_enabled():
     return torch.are_deterministic_algorithms_enabled()
 
 
-def bwd_flags_workspace(n_floats, device):
-    """(flags, workspace or None, its size in floats) for an *_ex backward call; ``n_floats`` from the library's
-    *_workspace_floats() for BWD_DETERMINISTIC (a negative value is an argument error the call itself reports).  The
-    workspace comes from torch's caching allocator, so the route is captured by torch.cuda.graph like any other."""
+def det_args(workspace_query, *dims, device):
+    """(flags, workspace or None, its size in floats) for an *_ex backward call: (0, None, 0) unless
+    deterministic_enabled(), else BWD_DETERMINISTIC and ``workspace_query(*dims, BWD_DETERMINISTIC)`` floats (the
+    library's *_workspace_floats(); a negative value is an argument error the call itself reports).  The workspace
+    comes from torch's caching allocator, so the route is captured by torch.cuda.graph like any other."""
+    if not deterministic_enabled():
+        return 0, None, 0
     import torch
+    n_floats = workspace_query(*dims, BWD_DETERMINISTIC)
     if n_floats <= 0:
         return BWD_DETERMINISTIC, None, 0
     return BWD_DETERMINISTIC, torch.empty(n_floats, device=device, dtype=torch.float32), n_floats

@@ -48,10 +48,8 @@ class CausalConv1dFn(torch.autograd.Function):
         dx = torch.empty(batch, dim, L, device=xc.device, dtype=xc.dtype)
         dw = torch.empty_like(wc)
         db = torch.empty(dim, device=xc.device, dtype=torch.float32) if bc is not None else None
-        flags, ws, nws = 0, None, 0
-        if _lib.deterministic_enabled():            # partials + fixed-order sum instead of float atomics
-            flags, ws, nws = _lib.bwd_flags_workspace(
-                lib.simamba_causal_conv1d_bwd_workspace_floats(batch, dim, L, W, _lib.BWD_DETERMINISTIC), xc.device)
+        # deterministic: partials + fixed-order sum instead of float atomics
+        flags, ws, nws = _lib.det_args(lib.simamba_causal_conv1d_bwd_workspace_floats, batch, dim, L, W, device=xc.device)
         _lib.count("conv1d_bwd_det" if flags else "conv1d_bwd_atomic")
         with torch.cuda.device(xc.device), _lib.timed("conv1d_bwd", xc.device):
             rc = lib.simamba_causal_conv1d_bwd_ex(_lib.ptr(xc), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(dout),

@@ -14,7 +14,7 @@
 // atomics; the accumulator pointers then point into the caller's workspace (det_layout below): dB | dC per workgroup
 // column into the slab [group][tensor][batch][N][L] (p.dC = p.dB + batch * N * L), dA / dD / ddelta_bias per (chunk,
 // sample, row).  det_reduce.hip sums them in a fixed order.
-#include "scan_common.h"
+#include "scan_host.h"
 #include "scan_xlane.h"
 #include "det_reduce.h"
 
@@ -280,30 +280,20 @@ static size_t bwd_smem_bytes(int kItems, int passes) {
                           kRowsPerPass * passes + kRowsPerPass * kMaxState);
 }
 
-template <typename T>
-static int launch_bwd(const ScanArgs& a, hipStream_t s, bool det) {
+template <typename T, bool kDet>
+static void launch_bwd_items(const ScanArgs& a, hipStream_t s) {
   dim3 grid((a.dim + kRowsPerPass * a.passes - 1) / (kRowsPerPass * a.passes), a.batch);
-  if (det) {
-    if (a.seqlen <= 64)
-      hipLaunchKernelGGL((scan_bwd_kernel<T, 4, true>), grid, dim3(kScanThreads), bwd_smem_bytes(4, a.passes), s, a);
-    else
-      hipLaunchKernelGGL((scan_bwd_kernel<T, 8, true>), grid, dim3(kScanThreads), bwd_smem_bytes(8, a.passes), s, a);
-    return static_cast<int>(hipGetLastError());
-  }
-  if (a.seqlen <= 64) {
-    hipLaunchKernelGGL((scan_bwd_kernel<T, 4>), grid, dim3(kScanThreads), bwd_smem_bytes(4, a.passes), s, a);
-  } else {
-    hipLaunchKernelGGL((scan_bwd_kernel<T, 8>), grid, dim3(kScanThreads), bwd_smem_bytes(8, a.passes), s, a);
-  }
-  return static_cast<int>(hipGetLastError());
+  if (a.seqlen <= 64)
+    hipLaunchKernelGGL((scan_bwd_kernel<T, 4, kDet>), grid, dim3(kScanThreads), bwd_smem_bytes(4, a.passes), s, a);
+  else
+    hipLaunchKernelGGL((scan_bwd_kernel<T, 8, kDet>), grid, dim3(kScanThreads), bwd_smem_bytes(8, a.passes), s, a);
 }
 
-struct BwdSeqArgs;
-bool scan_bwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, int vec, long long z_bs, long long dz_bs,
-                     bool has_z, int bc_mode, long long bc_ns, long long bc_ts);
-int scan_bwd_seq_dispatch(const ScanArgs& a, int io_dtype, int bc_mode, hipStream_t s, const void* dt, const void* wdt,
-                          long long dt_bs, long long dt_ts, int dt_rank, bool det);
-int scan_fwd_seq_bc_mode(const void* B, const void* C, int io_dtype, long long bc_bs, long long bc_ns, long long bc_ts);
+template <typename T>
+static int launch_bwd(const ScanArgs& a, hipStream_t s, bool det) {
+  if (det) launch_bwd_items<T, true>(a, s); else launch_bwd_items<T, false>(a, s);
+  return static_cast<int>(hipGetLastError());
+}
 
 // channels per workgroup of the row-scan backward = 16 * passes (the more, the fewer dB/dC atomics reach HBM; measured
 // at (64,768,1024,16): 134 MB of flush traffic at passes = 3, 18 % on top of the 604 MB of gradient stores); but keep
@@ -349,16 +339,14 @@ using namespace simamba;
 
 extern "C" long long simamba_scan_bwd_workspace_floats(int batch, int dim, int seqlen, int dstate, int ckpt_step,
                                                        int flags) {
-  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  int rc;
+  if ((rc = scan_check_flags(flags))) return rc;
   if (!flags) return 0;
-  if (batch < 0 || dim <= 0 || seqlen < 0 || batch > 65535) return SIMAMBA_E_SHAPE;
-  if (dstate < 1 || dstate > kMaxState) return SIMAMBA_E_DSTATE;
-  if (ckpt_step == 0) ckpt_step = SIMAMBA_SCAN_CKPT_ROW;
-  if (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) return SIMAMBA_E_VARIANT;
+  if ((rc = scan_check_shape(batch, dim, seqlen)) || (rc = scan_check_dstate(dstate)) ||
+      (rc = scan_check_ckpt(ckpt_step)))
+    return rc;
   return det_layout(batch, dim, seqlen, dstate, ckpt_step).total;
 }
-
-static bool aligned16b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // the fixed-order sum pass of the deterministic form: partials (a.dA ... in the workspace) -> the caller's spans
 static int scan_det_sum(const DetLayout& wl, const ScanArgs& a, float* dA, float* dB, float* dC, float* dD,
@@ -386,23 +374,21 @@ static int scan_bwd_impl(const void* u, const void* delta, const float* A, const
                          long long bc_tstride, int ckpt_step, void* stream, const void* dt, const void* wdt,
                          long long dt_bs, long long dt_ts, int dt_rank, int flags, float* workspace,
                          long long workspace_floats) {
-  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  int rc;
+  if ((rc = scan_check_flags(flags)) || (rc = scan_check_args(batch, dim, seqlen, dstate, io_dtype, ckpt_step)))
+    return rc;
   const bool det = flags != 0;
-  if (batch < 0 || dim <= 0 || seqlen < 0 || batch > 65535) return SIMAMBA_E_SHAPE;
-  if (ckpt_step == 0) ckpt_step = SIMAMBA_SCAN_CKPT_ROW;
-  if (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) return SIMAMBA_E_VARIANT;
-  if (dstate < 1 || dstate > kMaxState) return SIMAMBA_E_DSTATE;
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
   if (!A || !dA) return SIMAMBA_E_NULLPTR;
   if (batch > 0 && seqlen > 0) {
     if (!u || (!delta && !dt) || !B || !C || !dout || !du || !ddelta || !dB || !dC) return SIMAMBA_E_NULLPTR;
     if ((z != nullptr) != (dz != nullptr)) return SIMAMBA_E_NULLPTR;
   }
-  const int nchunks = simamba_scan_num_chunks(seqlen);
-  if (ckpt_step == SIMAMBA_SCAN_CKPT_SEQ ? (seqlen > 16 && !x_ckpt) : (nchunks > 1 && !x_ckpt)) return SIMAMBA_E_NULLPTR;
+  const ScanOperands o = scan_operands(dim, seqlen, dstate, io_dtype, addr_or({u, delta, dout, du, ddelta, z, dz}),
+                                       z != nullptr, z_bstride, dz_bstride, bc_bstride, bc_nstride, bc_tstride);
+  if (ckpt_step == SIMAMBA_SCAN_CKPT_SEQ ? (seqlen > 16 && !x_ckpt) : (o.nchunks > 1 && !x_ckpt)) return SIMAMBA_E_NULLPTR;
   const DetLayout wl = det_layout(batch, dim, seqlen, dstate, ckpt_step);
   if (det && wl.total > 0 && (!workspace || workspace_floats < wl.total)) return SIMAMBA_E_WORKSPACE;
-  if (det && (reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return SIMAMBA_E_ALIGN;
+  if (det && !aligned16(workspace)) return SIMAMBA_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e;
   // The five accumulators are zeroed here (the kernel adds into them).  Never a byte outside the five spans:
@@ -444,30 +430,22 @@ static int scan_bwd_impl(const void* u, const void* delta, const float* A, const
     a.ddelta_bias = ddelta_bias ? workspace + wl.bias : nullptr;
   }
   a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.dstate = dstate;
-  a.nchunks = nchunks;
+  a.nchunks = o.nchunks;
   a.softplus = delta_softplus;
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  a.z_bs = z_bstride ? z_bstride : static_cast<long long>(dim) * seqlen;
-  a.dz_bs = dz_bstride ? dz_bstride : static_cast<long long>(dim) * seqlen;
-  if (!bc_bstride && !bc_nstride && !bc_tstride) {
-    bc_bstride = static_cast<long long>(dstate) * seqlen; bc_nstride = seqlen; bc_tstride = 1;
-  }
-  a.bc_bs = bc_bstride; a.bc_ns = bc_nstride; a.bc_ts = bc_tstride;
-  a.vec = ((seqlen * esz) % 16 == 0) && aligned16b(u) && (dt || aligned16b(delta)) && aligned16b(dout) &&
-          aligned16b(du) && aligned16b(ddelta) &&
-          (!z || (aligned16b(z) && aligned16b(dz) && (a.z_bs * esz) % 16 == 0 && (a.dz_bs * esz) % 16 == 0));
+  a.z_bs = o.z_bs; a.dz_bs = o.dz_bs; a.bc_bs = o.bc_bs; a.bc_ns = o.bc_ns; a.bc_ts = o.bc_ts;
+  a.vec = o.vec;
   if (ckpt_step == SIMAMBA_SCAN_CKPT_SEQ) {
     const int bc_mode = scan_fwd_seq_bc_mode(B, C, io_dtype, a.bc_bs, a.bc_ns, a.bc_ts);
     if (!scan_bwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, a.vec, a.z_bs, a.dz_bs, z != nullptr, bc_mode,
                          a.bc_ns, a.bc_ts) ||
-        (reinterpret_cast<uintptr_t>(A) & 15u) != 0 || (x_ckpt && (reinterpret_cast<uintptr_t>(x_ckpt) & 15u) != 0))
+        !aligned16(A) || !aligned16(x_ckpt))
       return SIMAMBA_E_VARIANT;
-    const int rc = scan_bwd_seq_dispatch(a, io_dtype, bc_mode, s, dt, wdt, dt_bs, dt_ts, dt_rank, det);
+    rc = scan_bwd_seq_dispatch(a, io_dtype, bc_mode, s, dt, wdt, dt_bs, dt_ts, dt_rank, det);
     return (rc || !det) ? rc : scan_det_sum(wl, a, dA, dB, dC, dD, ddelta_bias, s);
   }
   if (dt) return SIMAMBA_E_VARIANT;                          // only the sequential kernel forms delta itself
   a.passes = bwd_passes(batch, dim);
-  const int rc = io_dtype == SIMAMBA_F32 ? launch_bwd<float>(a, s, det) : launch_bwd<bf16_t>(a, s, det);
+  rc = io_dtype == SIMAMBA_F32 ? launch_bwd<float>(a, s, det) : launch_bwd<bf16_t>(a, s, det);
   return (rc || !det) ? rc : scan_det_sum(wl, a, dA, dB, dC, dD, ddelta_bias, s);
 }
 
@@ -510,23 +488,17 @@ extern "C" int simamba_selective_scan_dt_bwd_ex(const void* u, const void* xdbl,
                                                 int dt_rank, int io_dtype, long long z_bstride, long long dz_bstride,
                                                 long long xdbl_bstride, long long xdbl_tstride, int flags,
                                                 float* workspace, long long workspace_floats, void* stream) {
-  if (flags & ~SIMAMBA_BWD_DETERMINISTIC) return SIMAMBA_E_VARIANT;
+  int rc;
+  if ((rc = scan_check_flags(flags))) return rc;
   if (dstate != kMaxState) return SIMAMBA_E_DSTATE;
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  const int pack = io_dtype == SIMAMBA_F32 ? 4 : 8;
-  if (dt_rank < pack || dt_rank > 24 || dt_rank % pack) return SIMAMBA_E_SHAPE;
+  if ((rc = scan_check_dtype(io_dtype)) || (rc = scan_check_dt_rank(dt_rank, io_dtype))) return rc;
   if (batch > 0 && seqlen > 0 && (!xdbl || !wdt || !z)) return SIMAMBA_E_NULLPTR;
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  const long long S = dt_rank + 2 * kMaxState;
-  const long long xb = xdbl_bstride ? xdbl_bstride : S * seqlen, xt = xdbl_tstride ? xdbl_tstride : S;
-  if (!aligned16b(xdbl) || !aligned16b(wdt) || (xb * esz) % 16 || (xt * esz) % 16 || (dt_rank * esz) % 16 ||
-      static_cast<long long>(batch) * xb >= (1ll << 30))
-    return SIMAMBA_E_VARIANT;
-  const char* Bp = static_cast<const char*>(xdbl) + static_cast<size_t>(dt_rank) * esz;
-  const char* Cp = Bp + kMaxState * esz;
-  return scan_bwd_impl(u, nullptr, A, Bp, Cp, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD, dz,
-                       ddelta_bias, batch, dim, seqlen, dstate, io_dtype, 1, z_bstride, dz_bstride, xb, 1, xt,
-                       SIMAMBA_SCAN_CKPT_SEQ, stream, xdbl, wdt, xb, xt, dt_rank, flags, workspace, workspace_floats);
+  const XdblOperands x = scan_xdbl_operands(xdbl, wdt, batch, seqlen, dt_rank, io_dtype, xdbl_bstride, xdbl_tstride);
+  if (!x.ok) return SIMAMBA_E_VARIANT;
+  return scan_bwd_impl(u, nullptr, A, x.B, x.C, D, z, delta_bias, dout, x_ckpt, du, ddelta, dA, dB, dC, dD, dz,
+                       ddelta_bias, batch, dim, seqlen, dstate, io_dtype, 1, z_bstride, dz_bstride, x.bs, 1, x.ts,
+                       SIMAMBA_SCAN_CKPT_SEQ, stream, xdbl, wdt, x.bs, x.ts, dt_rank, flags, workspace,
+                       workspace_floats);
 }
 
 extern "C" int simamba_selective_scan_dt_bwd(const void* u, const void* xdbl, const void* wdt, const float* A,

@@ -30,7 +30,8 @@
 // two-lanes-per-channel form would leave 1536 waves on 1024 SIMDs).  Registers <= 168 (3 waves per SIMD), LDS
 // 52.5 KB per workgroup (3 per CU).
 // Algorithmic HBM bytes: 7*B*D*L*s + 2*B*N*L*(s+4) + the checkpoints B*D*L*4 (read) + small.
-#include "scan_common.h"
+#include "scan_host.h"
+#include "scan_seq_common.h"
 #include "scan_xlane.h"
 
 namespace simamba {
@@ -38,16 +39,15 @@ namespace simamba {
 #ifndef SIMAMBA_BWDSEQ_OCC
 #define SIMAMBA_BWDSEQ_OCC 3                   // waves per SIMD the register allocation is held to
 #endif
-constexpr int kBsTC = 32;                  // steps per chunk: one 128-byte line of an fp32 row
 constexpr int kBsSeg = 16;                 // steps per segment = distance of the forward's checkpoints
 constexpr int kBsR = 16;                   // channels per wave
 constexpr int kBsWaves = 4;
 constexpr int kBsThreads = 64 * kBsWaves;
 constexpr int kBsCh = kBsR * kBsWaves;     // channels per workgroup
-constexpr int kBsTile = kBsR * kBsTC;      // floats per tile
+constexpr int kBsTile = kBsR * kSeqTC;     // floats per tile
 constexpr int kBsPPitch = 33;              // dB | dC partial tile [32 steps][32 + 1]
-constexpr int kBsWaveFloats = 4 * kBsTile + kBsTC * kBsPPitch;
-constexpr int kBsSmemFloats = kBsWaves * kBsWaveFloats + kBsTC * 32;
+constexpr int kBsWaveFloats = 4 * kBsTile + kSeqTC * kBsPPitch;
+constexpr int kBsSmemFloats = kBsWaves * kBsWaveFloats + kSeqTC * 32;
 
 struct BwdSeqArgs {
   const void* u; const void* delta; const void* z; const void* dout;
@@ -65,30 +65,6 @@ struct BwdSeqArgs {
   long long z_bs, dz_bs;
   long long bc_bs, bc_ns, bc_ts;
 };
-
-template <typename T>
-__device__ __forceinline__ void bs_load4(const T* __restrict__ base, unsigned boff, float (&v)[4]) {
-  const Pack<T, 4> pk = *reinterpret_cast<const Pack<T, 4>*>(reinterpret_cast<const char*>(base) + boff);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = to_f32<T>(pk.v[i]);
-}
-template <typename T>
-__device__ __forceinline__ void bs_store4(T* __restrict__ base, unsigned boff, const float (&v)[4]) {
-  Pack<T, 4> pk;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) pk.v[i] = from_f32<T>(v[i]);
-  *reinterpret_cast<Pack<T, 4>*>(reinterpret_cast<char*>(base) + boff) = pk;
-}
-
-// softplus of x handed over as x * log2(e); see scan_fwd_seq.hip
-__device__ __forceinline__ float bs_softplus_log2(float x2) {
-  const float e = fast_exp2(x2);
-  float sp = log1p_exp(e);
-  sp = (x2 < -15.f * kLog2e) ? e : sp;
-  return (x2 > 20.f * kLog2e) ? x2 * kLn2 : sp;
-}
-
-__device__ __forceinline__ int bs_tile_off(int row, int g) { return row * kBsTC + 4 * (g ^ ((row >> 1) & 7)); }
 
 // The last two stages of the channel reduction, inside a 16-lane row (4 channels = 4 banks of 4 lanes), in one block.
 // Channel bit 1 (lanes 8 apart), transposing: banks 0,1 end with w0 summed over the pair, banks 2,3 with w1 -- two
@@ -128,9 +104,6 @@ __device__ __forceinline__ void bs_quad_sum2(float& a, float& b) {
       : "+v"(a), "+v"(b));
 }
 
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
-using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
-
 // kDet: the deterministic form (SIMAMBA_BWD_DETERMINISTIC).  No float atomics: dA / dB / dC / dD / ddelta_bias then
 // point at the partial buffers of the caller's workspace (scan_bwd.hip, det_layout) and every workgroup STORES its
 // partials -- dB | dC into the slab [tile][tensor][batch][16][L] (p.dC = p.dB + batch * 16 * L), dA into (batch, dim, 16),
@@ -167,13 +140,13 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
   float dAacc[4] = {0.f, 0.f, 0.f, 0.f};
   float dDacc = 0.f;
   const int sw = (ch >> 1) & 7;
-  const int trow = ch * kBsTC;
+  const int trow = ch * kSeqTC;
   // element f of a dB | dC row that this lane's finished sum belongs to (see the reduction below)
   const int pf = (r4 >> 1) * 16 + 4 * pq + 2 * (r4 & 1) + (cq >> 1);
   const float* ckl = p.ckpt + (static_cast<size_t>(b) * p.nck * D + dch) * kMaxState + 4 * pq;   // + block * D * 16
   // kDet: ddelta_bias sums of the wave's 16 rows, row r at tDb[r * kBsPPitch] (column 32 of tP, never read or written
   // by the dB | dC partials)
-  float* tDb = smem + wave * kBsWaveFloats + 4 * kBsTile + kBsTC;
+  float* tDb = smem + wave * kBsWaveFloats + 4 * kBsTile + kSeqTC;
   if (kDet && lane < kBsR) tDb[lane * kBsPPitch] = 0.f;
 
   // ---- phase A / C identity: pack pk = lane + 64 j covers row pk / 8, steps 4 (pk % 8) .. + 4 ----------------
@@ -215,7 +188,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
     const int t = (t0 + bc_tl < L) ? t0 + bc_tl : 0;         // beyond the sequence: step 0 (multiplied away)
     const unsigned o = static_cast<unsigned>(bc_n * static_cast<int>(p.bc_ns) + t * static_cast<int>(p.bc_ts)) * kEsz;
     float vb[4], vc[4];                                      // both tensors from uniform bases, one kept
-    if (isC) bs_load4<T>(Cgp, o, vc); else bs_load4<T>(Bgp, o, vb);
+    if (isC) load4<T>(Cgp, o, vc); else load4<T>(Bgp, o, vb);
 #pragma unroll
     for (int k = 0; k < 4; ++k) bcv[k] = isC ? vc[k] : vb[k];
   };
@@ -270,7 +243,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
         uint4 a8 = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(dtrow) + kc);
         const uint4 w8 = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(wrow) + kc);
         if (8 * mk >= p.dt_rank) a8 = make_uint4(0u, 0u, 0u, 0u);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a8), __builtin_bit_cast(bf16x8_t, w8),
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a8), __builtin_bit_cast(bf16x8, w8),
                                                       acc, 0, 0, 0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[e] = bf16_to_f32(f32_to_bf16(acc[e]));
@@ -291,19 +264,19 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const unsigned ro = row_off(l, j) + to;
-      if (!kDt) bs_load4<T>(dg, ro, dv[j]);
-      bs_load4<T>(ug, ro, uv[j]);
-      bs_load4<T>(gg, ro, gv[j]);
-      if (kHasZ) bs_load4<T>(zg, ro + zdelta, zv[j]);
+      if (!kDt) load4<T>(dg, ro, dv[j]);
+      load4<T>(ug, ro, uv[j]);
+      load4<T>(gg, ro, gv[j]);
+      if (kHasZ) load4<T>(zg, ro + zdelta, zv[j]);
       if (!kDt) biasA[j] = p.delta_bias ? p.delta_bias[d0w + (l >> 3) + 8 * j] : 0.f;
     }
     if (kDt) form_delta(t0, l);
     load_state(t0 + kBsSeg);
   };
 
-  const int nchunks = (L + kBsTC - 1) / kBsTC;
+  const int nchunks = (L + kSeqTC - 1) / kSeqTC;
   {
-    const int t0 = (nchunks - 1) * kBsTC;
+    const int t0 = (nchunks - 1) * kSeqTC;
     const int l = lane_now();
     issue_bc(t0, wave * 64 + l);
     issue_loads(t0, l);
@@ -311,7 +284,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
   }
 
   for (int c = nchunks - 1; c >= 0; --c) {
-    const int t0 = c * kBsTC;
+    const int t0 = c * kSeqTC;
     __syncthreads();            // tBC of this chunk is complete; every wave is done with the previous chunk's tP
 
     // ---- phase A: per-element transcendentals in the load layout, into the tiles ----------------------------
@@ -326,8 +299,8 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
           const float b2 = (t0 + 4 * qm < L) ? biasA[0] * kLog2e : -1e30f;
           float dl[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) dl[i] = bs_softplus_log2(fmaf(dv[tile][i], kLog2e, b2));
-          *reinterpret_cast<float4*>(tD + bs_tile_off(mc, qm)) = make_float4(dl[0], dl[1], dl[2], dl[3]);
+          for (int i = 0; i < 4; ++i) dl[i] = softplus_log2(fmaf(dv[tile][i], kLog2e, b2));
+          *reinterpret_cast<float4*>(tD + tile_off(mc, qm)) = make_float4(dl[0], dl[1], dl[2], dl[3]);
         }
       }
 #pragma unroll
@@ -336,7 +309,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
         float dl[4], dyv[4], dzw[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          if (!kDt) dl[i] = bs_softplus_log2(fmaf(dv[j][i], kLog2e, b2));
+          if (!kDt) dl[i] = softplus_log2(fmaf(dv[j][i], kLog2e, b2));
           const float go = in_seq ? gv[j][i] : 0.f;
           if (kHasZ) {
             const float z = zv[j][i], sg = sigmoid_f(z);
@@ -346,7 +319,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
             dyv[i] = go;
           }
         }
-        const int to_ = bs_tile_off((l >> 3) + 8 * j, l & 7);
+        const int to_ = tile_off((l >> 3) + 8 * j, l & 7);
         if (!kDt) *reinterpret_cast<float4*>(tD + to_) = make_float4(dl[0], dl[1], dl[2], dl[3]);
         *reinterpret_cast<float4*>(tU + to_) = make_float4(uv[j][0], uv[j][1], uv[j][2], uv[j][3]);
         *reinterpret_cast<float4*>(tY + to_) = make_float4(dyv[0], dyv[1], dyv[2], dyv[3]);
@@ -513,7 +486,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
       const bool in_seq = t0 + 4 * (l & 7) < L;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int to_ = bs_tile_off((l >> 3) + 8 * j, l & 7);
+        const int to_ = tile_off((l >> 3) + 8 * j, l & 7);
         const float4 a4 = *reinterpret_cast<const float4*>(tU + to_);
         const float4 t4 = *reinterpret_cast<const float4*>(tY + to_);
         const float4 d4 = *reinterpret_cast<const float4*>(tD + to_);
@@ -529,12 +502,12 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
         }
         const unsigned ro = row_off(l, j) + t0 * kEsz;
         if (in_seq) {
-          bs_store4<T>(dug, ro, duv);
-          bs_store4<T>(ddg, ro, dd);
+          store4<T>(dug, ro, duv);
+          store4<T>(ddg, ro, dd);
           if (kHasZ) {
             const float4 z4 = *reinterpret_cast<const float4*>(tZ + to_);
             const float dzv[4] = {z4.x, z4.y, z4.z, z4.w};
-            bs_store4<T>(dzg, ro + dzdelta, dzv);
+            store4<T>(dzg, ro + dzdelta, dzv);
           }
         }
         // ddelta_bias: this chunk's sum over the row's 8 packs, one atomic per row and chunk
@@ -554,7 +527,7 @@ __global__ __launch_bounds__(kBsThreads, SIMAMBA_BWDSEQ_OCC) void scan_bwd_seq_k
       // in order); they land during the flush below and under the other two waves of this SIMD
       // (unconditional: on the last iteration chunk 0 is simply read again -- a load under `if (c > 0)` would keep the
       // PREVIOUS values of these 44 registers alive through all of phase B, which is exactly where none are free)
-      const int tn = c > 0 ? t0 - kBsTC : 0;
+      const int tn = c > 0 ? t0 - kSeqTC : 0;
       issue_loads(tn, l);
       issue_bc(tn, wave * 64 + l);
     }
@@ -614,6 +587,23 @@ bool scan_bwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, i
          bc_ns >= 0 && bc_ts >= 0 && (kMaxState - 1) * bc_ns + (seqlen - 1) * bc_ts < (1ll << 30);
 }
 
+// kDt: the mixer's form (gated, delta formed in the kernel); kDet: partial buffers in place of the accumulators
+template <typename T, bool kDt, bool kDet>
+static void launch_bwd_seq(const BwdSeqArgs& a, hipStream_t s) {
+  dim3 grid(a.dim / kBsCh, a.batch);
+  if constexpr (kDt)
+    hipLaunchKernelGGL((scan_bwd_seq_kernel<T, true, true, kDet>), grid, dim3(kBsThreads), 0, s, a);
+  else if (a.z)
+    hipLaunchKernelGGL((scan_bwd_seq_kernel<T, true, false, kDet>), grid, dim3(kBsThreads), 0, s, a);
+  else
+    hipLaunchKernelGGL((scan_bwd_seq_kernel<T, false, false, kDet>), grid, dim3(kBsThreads), 0, s, a);
+}
+template <bool kDet>
+static void launch_bwd_seq(const BwdSeqArgs& a, bool f32, hipStream_t s) {
+  if (a.dt) { if (f32) launch_bwd_seq<float, true, kDet>(a, s); else launch_bwd_seq<bf16_t, true, kDet>(a, s); }
+  else if (f32) launch_bwd_seq<float, false, kDet>(a, s); else launch_bwd_seq<bf16_t, false, kDet>(a, s);
+}
+
 int scan_bwd_seq_dispatch(const ScanArgs& sa, int io_dtype, int bc_mode, hipStream_t s, const void* dt, const void* wdt,
                           long long dt_bs, long long dt_ts, int dt_rank, bool det) {
   BwdSeqArgs a{};
@@ -626,32 +616,8 @@ int scan_bwd_seq_dispatch(const ScanArgs& sa, int io_dtype, int bc_mode, hipStre
   a.bc_mode = bc_mode;
   a.z_bs = sa.z_bs; a.dz_bs = sa.dz_bs; a.bc_bs = sa.bc_bs; a.bc_ns = sa.bc_ns; a.bc_ts = sa.bc_ts;
   a.dt = dt; a.wdt = wdt; a.dt_bs = dt_bs; a.dt_ts = dt_ts; a.dt_rank = dt_rank;
-  dim3 grid(a.dim / kBsCh, a.batch);
-  if (det) {                                                 // partial buffers in place of the accumulators
-    if (a.dt) {
-      if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true, true, true>), grid, dim3(kBsThreads), 0, s, a);
-      else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true, true, true>), grid, dim3(kBsThreads), 0, s, a);
-    } else if (io_dtype == SIMAMBA_F32) {
-      if (a.z) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true, false, true>), grid, dim3(kBsThreads), 0, s, a);
-      else hipLaunchKernelGGL((scan_bwd_seq_kernel<float, false, false, true>), grid, dim3(kBsThreads), 0, s, a);
-    } else {
-      if (a.z) hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true, false, true>), grid, dim3(kBsThreads), 0, s, a);
-      else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, false, false, true>), grid, dim3(kBsThreads), 0, s, a);
-    }
-    return static_cast<int>(hipGetLastError());
-  }
-  if (a.dt) {                                                // the mixer's form: gated, delta formed in the kernel
-    if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true, true>), grid, dim3(kBsThreads), 0, s, a);
-    else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true, true>), grid, dim3(kBsThreads), 0, s, a);
-    return static_cast<int>(hipGetLastError());
-  }
-  if (io_dtype == SIMAMBA_F32) {
-    if (a.z) hipLaunchKernelGGL((scan_bwd_seq_kernel<float, true>), grid, dim3(kBsThreads), 0, s, a);
-    else hipLaunchKernelGGL((scan_bwd_seq_kernel<float, false>), grid, dim3(kBsThreads), 0, s, a);
-  } else {
-    if (a.z) hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, true>), grid, dim3(kBsThreads), 0, s, a);
-    else hipLaunchKernelGGL((scan_bwd_seq_kernel<bf16_t, false>), grid, dim3(kBsThreads), 0, s, a);
-  }
+  const bool f32 = io_dtype == SIMAMBA_F32;
+  if (det) launch_bwd_seq<true>(a, f32, s); else launch_bwd_seq<false>(a, f32, s);
   return static_cast<int>(hipGetLastError());
 }
 

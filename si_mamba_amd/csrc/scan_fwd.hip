@@ -4,7 +4,7 @@
 // models/block.py:72.  Algorithmic HBM bytes: 4*B*D*L*s (u, delta, z, out) + 2*B*N*L*s (B, C)
 // + small; the (B_t, C_t) tile is re-read from L2 once per 16*R channels.
 #include <cstdlib>
-#include "scan_common.h"
+#include "scan_host.h"
 
 namespace simamba {
 
@@ -158,18 +158,6 @@ static int launch_fwd(const ScanArgs& a, hipStream_t s) {
   return static_cast<int>(hipGetLastError());
 }
 
-int scan_fwd_seq_dispatch(const void* u, const void* delta, const float* A, const void* B, const void* C, const float* D,
-                          const void* z, const float* delta_bias, void* out, float* x_ckpt, int ckpt_step,
-                          float* last_state,
-                          int batch, int dim, int seqlen, int io_dtype, long long z_bs,
-                          long long bc_bs, long long bc_ns, long long bc_ts, int nchunks128, int lpc, hipStream_t s,
-                          const void* dt = nullptr, const void* wdt = nullptr, long long dt_bs = 0, long long dt_ts = 0,
-                          int dt_rank = 0);
-int scan_fwd_seq_bc_mode(const void* B, const void* C, int io_dtype, long long bc_bs, long long bc_ns, long long bc_ts);
-int scan_fwd_seq_mix_c4(int batch, int dim);
-bool scan_bwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, int vec, long long z_bs, long long dz_bs,
-                     bool has_z, int bc_mode, long long bc_ns, long long bc_ts);
-
 // Kernel choice when the caller leaves it to the library (variant == SIMAMBA_SCAN_AUTO).  The lanes-per-channel
 // kernel (scan_fwd_seq.hip) issues 5 VALU per (row, step, state) against ~7 for the row-scan kernel, but a wave
 // covers 64 / lpc whole rows: it needs rows / (64 / lpc) waves to give every one of the 1024 SIMDs its 3 waves.
@@ -207,8 +195,7 @@ extern "C" int simamba_scan_fwd_auto_variant(int batch, int dim) {
 extern "C" int simamba_scan_ckpt_step(int batch, int dim, int seqlen, int dstate, int io_dtype) {
   if (batch <= 0 || dim <= 0 || seqlen <= 0) return SIMAMBA_SCAN_CKPT_ROW;
   const long long rows = static_cast<long long>(batch) * dim;
-  const int pack = io_dtype == SIMAMBA_F32 ? 4 : 8;
-  if (dstate == kMaxState && dim % 64 == 0 && seqlen % pack == 0 && rows * seqlen < (1ll << 30) &&
+  if (dstate == kMaxState && dim % 64 == 0 && seqlen % scan_pack(io_dtype) == 0 && rows * seqlen < (1ll << 30) &&
       auto_variant(rows, batch, dim) != SIMAMBA_SCAN_ROWSCAN)
     return SIMAMBA_SCAN_CKPT_SEQ;
   return SIMAMBA_SCAN_CKPT_ROW;
@@ -222,51 +209,42 @@ extern "C" long long simamba_scan_ckpt_floats(int batch, int dim, int seqlen, in
   return nc <= 1 ? 0 : static_cast<long long>(batch) * dim * nc * dstate;
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // What the lanes-per-channel forward assumes beyond the argument checks of simamba_selective_scan_fwd: 16 states,
 // softplus on (the only form the reference's mixer uses), pack-aligned rows (`vec`) and B / C, 32-bit byte offsets.
 // One statement of it for the entry point and for simamba_scan_seq_applicable.
-static bool scan_fwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, int vec, const void* A,
-                            const void* B, const void* C, int io_dtype, long long z_bs, long long bc_bs, long long bc_ns,
-                            long long bc_ts) {
+static bool scan_fwd_seq_ok(int batch, int dim, int seqlen, int dstate, int softplus, const ScanOperands& o,
+                            const void* A, const void* B, const void* C, int io_dtype) {
   const long long rows = static_cast<long long>(batch) * dim;
-  return dstate == kMaxState && softplus && vec && rows * seqlen < (1ll << 30) &&
-         scan_fwd_seq_bc_mode(B, C, io_dtype, bc_bs, bc_ns, bc_ts) != 0 &&
-         static_cast<long long>(batch) * z_bs < (1ll << 30) &&
-         (reinterpret_cast<uintptr_t>(A) & 15u) == 0 && bc_ns >= 0 && bc_ts >= 0 &&
-         (kMaxState - 1) * bc_ns + (seqlen - 1) * bc_ts < (1ll << 30);
+  return dstate == kMaxState && softplus && o.vec && rows * seqlen < (1ll << 30) &&
+         scan_fwd_seq_bc_mode(B, C, io_dtype, o.bc_bs, o.bc_ns, o.bc_ts) != 0 &&
+         static_cast<long long>(batch) * o.z_bs < (1ll << 30) && aligned16(A) && o.bc_ns >= 0 && o.bc_ts >= 0 &&
+         (kMaxState - 1) * o.bc_ns + (seqlen - 1) * o.bc_ts < (1ll << 30);
 }
 
 // Launch-free statement of what a CKPT_SEQ forward / backward pair accepts (include/simamba.h).  Addresses are only
-// examined for alignment.  Built from the same predicates the two entry points evaluate: scan_fwd_seq_ok above, and
-// scan_fwd_seq_bc_mode + scan_bwd_seq_ok + the A / x_ckpt alignment test of scan_bwd_impl (scan_bwd.hip).
+// examined for alignment.  The operands go through scan_operands like those of the two entry points, then through the
+// predicates those evaluate: scan_fwd_seq_ok above, and scan_fwd_seq_bc_mode + scan_bwd_seq_ok of scan_bwd_impl
+// (scan_bwd.hip; its A test is the forward's, and x_ckpt is part of `act_addr_or`).
 extern "C" int simamba_scan_seq_applicable(int batch, int dim, int seqlen, int dstate, int io_dtype,
                                            int delta_softplus, int has_z, size_t act_addr_or, size_t A_addr,
                                            size_t B_addr, size_t C_addr, long long z_bstride, long long dz_bstride,
                                            long long bc_bstride, long long bc_nstride, long long bc_tstride) {
-  if (batch <= 0 || dim <= 0 || seqlen <= 0 || batch > 65535) return 0;
-  if (dstate < 1 || dstate > kMaxState) return 0;
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return 0;
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  const long long z_bs = z_bstride ? z_bstride : static_cast<long long>(dim) * seqlen;
-  const long long dz_bs = dz_bstride ? dz_bstride : static_cast<long long>(dim) * seqlen;
-  if (!bc_bstride && !bc_nstride && !bc_tstride) {
-    bc_bstride = static_cast<long long>(dstate) * seqlen; bc_nstride = seqlen; bc_tstride = 1;
-  }
-  // ScanArgs::vec of both entry points: every activation operand (and x_ckpt) on a 16-byte boundary, rows whole packs
-  const int vec = ((seqlen * esz) % 16 == 0) && (act_addr_or & 15u) == 0 &&
-                  (!has_z || ((z_bs * esz) % 16 == 0 && (dz_bs * esz) % 16 == 0));
+  if (batch <= 0 || seqlen <= 0 || scan_check_shape(batch, dim, seqlen) || scan_check_dstate(dstate) ||
+      scan_check_dtype(io_dtype))
+    return 0;
+  const ScanOperands o = scan_operands(dim, seqlen, dstate, io_dtype, act_addr_or, has_z != 0, z_bstride, dz_bstride,
+                                       bc_bstride, bc_nstride, bc_tstride);
   const void* A = reinterpret_cast<const void*>(A_addr);
   const void* B = reinterpret_cast<const void*>(B_addr);
   const void* C = reinterpret_cast<const void*>(C_addr);
-  if (!scan_fwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, vec, A, B, C, io_dtype, z_bs, bc_bstride,
-                       bc_nstride, bc_tstride))
-    return 0;
-  const int bc_mode = scan_fwd_seq_bc_mode(B, C, io_dtype, bc_bstride, bc_nstride, bc_tstride);
-  return scan_bwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, vec, z_bs, dz_bs, has_z != 0, bc_mode,
-                         bc_nstride, bc_tstride) ? 1 : 0;
+  if (!scan_fwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, o, A, B, C, io_dtype)) return 0;
+  const int bc_mode = scan_fwd_seq_bc_mode(B, C, io_dtype, o.bc_bs, o.bc_ns, o.bc_ts);
+  return scan_bwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, o.vec, o.z_bs, o.dz_bs, has_z != 0, bc_mode,
+                         o.bc_ns, o.bc_ts) ? 1 : 0;
 }
+
+// lanes per channel of a forward variant, as scan_fwd_seq_dispatch takes it
+static int variant_lpc(int v) { return v == SIMAMBA_SCAN_MIX ? 6 : v == SIMAMBA_SCAN_LPC2 ? 2 : 4; }
 
 extern "C" int simamba_selective_scan_fwd(const void* u, const void* delta, const float* A, const void* B,
                                           const void* C, const float* D, const void* z,
@@ -275,36 +253,25 @@ extern "C" int simamba_selective_scan_fwd(const void* u, const void* delta, cons
                                           int io_dtype, int delta_softplus, long long z_bstride,
                                           long long bc_bstride, long long bc_nstride, long long bc_tstride,
                                           int ckpt_step, int variant, void* stream) {
-  if (batch < 0 || dim <= 0 || seqlen < 0 || batch > 65535) return SIMAMBA_E_SHAPE;
-  if (ckpt_step == 0) ckpt_step = SIMAMBA_SCAN_CKPT_ROW;
-  if (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) return SIMAMBA_E_VARIANT;
-  if (dstate < 1 || dstate > kMaxState) return SIMAMBA_E_DSTATE;
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (const int rc = scan_check_args(batch, dim, seqlen, dstate, io_dtype, ckpt_step)) return rc;
   if (batch == 0 || seqlen == 0) return SIMAMBA_OK;   // nothing to do (empty tensors carry NULL data)
   if (!u || !delta || !A || !B || !C || !out) return SIMAMBA_E_NULLPTR;
+  const ScanOperands o = scan_operands(dim, seqlen, dstate, io_dtype, addr_or({u, delta, out, z}), z != nullptr,
+                                       z_bstride, 0, bc_bstride, bc_nstride, bc_tstride);
   ScanArgs a{};
   a.u = u; a.delta = delta; a.A = A; a.B = B; a.C = C; a.D = D; a.z = z; a.delta_bias = delta_bias;
   a.out = out; a.x_ckpt = x_ckpt; a.last_state = last_state;
   a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.dstate = dstate;
-  a.nchunks = simamba_scan_num_chunks(seqlen);
+  a.nchunks = o.nchunks;
   a.softplus = delta_softplus;
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  a.z_bs = z_bstride ? z_bstride : static_cast<long long>(dim) * seqlen;
-  if (!bc_bstride && !bc_nstride && !bc_tstride) {
-    bc_bstride = static_cast<long long>(dstate) * seqlen; bc_nstride = seqlen; bc_tstride = 1;
-  }
-  a.bc_bs = bc_bstride; a.bc_ns = bc_nstride; a.bc_ts = bc_tstride;
-  a.vec = ((seqlen * esz) % 16 == 0) && aligned16(u) && aligned16(delta) && aligned16(out) &&
-          (!z || (aligned16(z) && (a.z_bs * esz) % 16 == 0));
+  a.z_bs = o.z_bs; a.bc_bs = o.bc_bs; a.bc_ns = o.bc_ns; a.bc_ts = o.bc_ts;
+  a.vec = o.vec;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (variant != SIMAMBA_SCAN_AUTO && variant != SIMAMBA_SCAN_ROWSCAN && variant != SIMAMBA_SCAN_LPC2 &&
       variant != SIMAMBA_SCAN_LPC4 && variant != SIMAMBA_SCAN_MIX)
     return SIMAMBA_E_VARIANT;
   const long long rows = static_cast<long long>(batch) * dim;
-  // what the lanes-per-channel kernel assumes: 16 states, softplus on (the only form the reference's mixer uses),
-  // pack-aligned rows and B / C, 32-bit byte offsets
-  const bool seq_ok = scan_fwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, a.vec, A, B, C, io_dtype, a.z_bs,
-                                      a.bc_bs, a.bc_ns, a.bc_ts);
+  const bool seq_ok = scan_fwd_seq_ok(batch, dim, seqlen, dstate, delta_softplus, o, A, B, C, io_dtype);
   int v = variant == SIMAMBA_SCAN_AUTO ? auto_variant(rows, batch, dim) : variant;
   // 16-step checkpoints are written by the lanes-per-channel kernels only (four lanes per channel where two would
   // leave the chip short of waves)
@@ -319,8 +286,8 @@ extern "C" int simamba_selective_scan_fwd(const void* u, const void* delta, cons
   }
   if (v != SIMAMBA_SCAN_ROWSCAN)
     return scan_fwd_seq_dispatch(u, delta, A, B, C, D, z, delta_bias, out, x_ckpt, ckpt_step, last_state, batch, dim, seqlen,
-                                 io_dtype, a.z_bs, a.bc_bs, a.bc_ns, a.bc_ts, a.nchunks,
-                                 v == SIMAMBA_SCAN_MIX ? 6 : v == SIMAMBA_SCAN_LPC2 ? 2 : 4, s);
+                                 io_dtype, a.z_bs, a.bc_bs, a.bc_ns, a.bc_ts, a.nchunks, variant_lpc(v), s,
+                                 nullptr, nullptr, 0, 0, 0);
   // channels per workgroup: amortise the (B_t,C_t) staging, but keep >= ~3 workgroups per CU
   int passes = 4;
   while (passes > 1 && static_cast<long long>(batch) * ((dim + 16 * passes - 1) / (16 * passes)) < 768) passes >>= 1;
@@ -337,30 +304,23 @@ extern "C" int simamba_selective_scan_dt_fwd(const void* u, const void* xdbl, co
                                              int dstate, int dt_rank, int io_dtype, long long z_bstride,
                                              long long xdbl_bstride, long long xdbl_tstride, int ckpt_step, int variant,
                                              void* stream) {
-  if (batch < 0 || dim <= 0 || seqlen < 0 || batch > 65535) return SIMAMBA_E_SHAPE;
+  int rc;
+  if ((rc = scan_check_shape(batch, dim, seqlen))) return rc;
   if (dstate != kMaxState) return SIMAMBA_E_DSTATE;
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (ckpt_step == 0) ckpt_step = SIMAMBA_SCAN_CKPT_ROW;
-  if (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) return SIMAMBA_E_VARIANT;
+  if ((rc = scan_check_dtype(io_dtype)) || (rc = scan_check_ckpt(ckpt_step))) return rc;
   if (variant != SIMAMBA_SCAN_AUTO && variant != SIMAMBA_SCAN_LPC2 && variant != SIMAMBA_SCAN_LPC4 &&
       variant != SIMAMBA_SCAN_MIX)
     return SIMAMBA_E_VARIANT;                               // the row-scan kernel reads a delta tensor
-  const int pack = io_dtype == SIMAMBA_F32 ? 4 : 8;
-  if (dt_rank < pack || dt_rank > 24 || dt_rank % pack) return SIMAMBA_E_SHAPE;
+  if ((rc = scan_check_dt_rank(dt_rank, io_dtype))) return rc;
   if (batch == 0 || seqlen == 0) return SIMAMBA_OK;
   if (!u || !xdbl || !wdt || !A || !z || !out) return SIMAMBA_E_NULLPTR;
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  const long long S = dt_rank + 2 * kMaxState;
-  const long long xb = xdbl_bstride ? xdbl_bstride : S * seqlen, xt = xdbl_tstride ? xdbl_tstride : S;
-  const long long zb = z_bstride ? z_bstride : static_cast<long long>(dim) * seqlen;
+  const XdblOperands x = scan_xdbl_operands(xdbl, wdt, batch, seqlen, dt_rank, io_dtype, xdbl_bstride, xdbl_tstride);
+  const ScanOperands o = scan_operands(dim, seqlen, dstate, io_dtype, addr_or({u, out, z}), true, z_bstride, 0, x.bs, 1,
+                                       x.ts);
   const long long rows = static_cast<long long>(batch) * dim;
-  const char* Bp = static_cast<const char*>(xdbl) + static_cast<size_t>(dt_rank) * esz;
-  const char* Cp = Bp + kMaxState * esz;
-  const bool ok = ((seqlen * esz) % 16 == 0) && aligned16(u) && aligned16(out) && aligned16(z) && aligned16(xdbl) &&
-                  aligned16(wdt) && aligned16(A) && (zb * esz) % 16 == 0 && (xb * esz) % 16 == 0 &&
-                  (xt * esz) % 16 == 0 && (dt_rank * esz) % 16 == 0 && rows * seqlen < (1ll << 30) &&
-                  static_cast<long long>(batch) * zb < (1ll << 30) && static_cast<long long>(batch) * xb < (1ll << 30) &&
-                  scan_fwd_seq_bc_mode(Bp, Cp, io_dtype, xb, 1, xt) == 2;
+  const bool ok = o.vec && x.ok && aligned16(A) && rows * seqlen < (1ll << 30) &&
+                  static_cast<long long>(batch) * o.z_bs < (1ll << 30) &&
+                  scan_fwd_seq_bc_mode(x.B, x.C, io_dtype, x.bs, 1, x.ts) == 2;
   if (!ok) return SIMAMBA_E_VARIANT;
   int v = variant;
   if (v == SIMAMBA_SCAN_AUTO) {
@@ -368,8 +328,7 @@ extern "C" int simamba_selective_scan_dt_fwd(const void* u, const void* xdbl, co
     if (v == SIMAMBA_SCAN_ROWSCAN) v = SIMAMBA_SCAN_LPC4;   // too few rows for two lanes per channel
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return scan_fwd_seq_dispatch(u, nullptr, A, Bp, Cp, D, z, delta_bias, out, x_ckpt, ckpt_step, last_state, batch, dim,
-                               seqlen, io_dtype, zb, xb, 1, xt, simamba_scan_num_chunks(seqlen),
-                               v == SIMAMBA_SCAN_MIX ? 6 : v == SIMAMBA_SCAN_LPC2 ? 2 : 4, s,
-                               xdbl, wdt, xb, xt, dt_rank);
+  return scan_fwd_seq_dispatch(u, nullptr, A, x.B, x.C, D, z, delta_bias, out, x_ckpt, ckpt_step, last_state, batch, dim,
+                               seqlen, io_dtype, o.z_bs, x.bs, 1, x.ts, o.nchunks, variant_lpc(v), s,
+                               xdbl, wdt, x.bs, x.ts, dt_rank);
 }

@@ -25,11 +25,11 @@
 //     with 1 - 2 DPP quad adds per step;
 //   * y_t overwrites u_t in the tile; phase C (same lane <-> pack map as A): y * silu(z), 16-byte stores;
 //   * the next chunk's delta / u loads are issued right after phase A and fly during the whole recurrence.
-#include "scan_common.h"
+#include "scan_host.h"
+#include "scan_seq_common.h"
 
 namespace simamba {
 
-constexpr int kSeqTC = 32;                 // timesteps per chunk: one 128-byte line of an fp32 row
 #ifndef SIMAMBA_SEQ_WAVES
 #define SIMAMBA_SEQ_WAVES 1
 #endif
@@ -85,43 +85,6 @@ SIMAMBA_QUAD_OPS(0, "[0,2,0,2]")
 SIMAMBA_QUAD_OPS(1, "[1,3,1,3]")
 #undef SIMAMBA_QUAD_OPS
 
-// One aligned 4-element pack per lane (16 B fp32 / 8 B bf16).  The dispatcher only takes this kernel when
-// rows are pack-aligned (L % 4 == 0 for fp32, L % 8 == 0 for bf16), so a pack is either entirely inside the
-// sequence or entirely outside.  A pack beyond the end of the sequence (last chunk of a ragged L) re-reads the
-// FIRST pack of its own row -- valid memory, finite whenever the row is -- and is neutralised once per pack, not
-// per element: its delta gets a bias of -1e30, which softplus maps to exactly 0 (a_t = 1, x_t = 0: the state
-// passes through), and its outputs are not stored.  No per-element guards, no divergent branches.
-// Addressing is "uniform base pointer + 32-bit BYTE offset" throughout (the dispatcher guarantees every tensor
-// spans < 4 GiB): global_load/store then take the base in SGPRs and one VGPR of offset, instead of a 64-bit
-// VGPR address per access that the compiler hoists out of the chunk loop and spills.
-template <typename T>
-__device__ __forceinline__ void load4(const T* __restrict__ base, unsigned boff, float (&v)[4]) {
-  const Pack<T, 4> pk = *reinterpret_cast<const Pack<T, 4>*>(reinterpret_cast<const char*>(base) + boff);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = to_f32<T>(pk.v[i]);
-}
-template <typename T>
-__device__ __forceinline__ void store4(T* __restrict__ base, unsigned boff, const float (&v)[4]) {
-  Pack<T, 4> pk;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) pk.v[i] = from_f32<T>(v[i]);
-  *reinterpret_cast<Pack<T, 4>*>(reinterpret_cast<char*>(base) + boff) = pk;
-}
-
-// softplus(x) with x handed over as x2 = x * log2(e) (the caller folds the scale into one fma with the bias):
-// 2 transcendentals + 7 plain ops, branch-free.  Above torch's threshold (x > 20) the result is x itself (and the
-// exp2 overflow beyond x ~ 88 never shows); below -15 the series log(1 + e) = e keeps the relative accuracy that
-// 1 + e loses.  x2 = -inf-like (-1e30 from a padded pack) gives e = 0 and exactly 0.
-__device__ __forceinline__ float softplus_log2(float x2) {
-  const float e = fast_exp2(x2);
-  float sp = log1p_exp(e);
-  sp = (x2 < -15.f * kLog2e) ? e : sp;
-  return (x2 > 20.f * kLog2e) ? x2 * kLn2 : sp;
-}
-
-// float offset of 16-byte column group g (0..7) of a tile row
-__device__ __forceinline__ int tile_off(int row, int g) { return row * kSeqTC + 4 * (g ^ ((row >> 1) & 7)); }
-
 template <int kLPC> struct SeqCfg {
   static constexpr int NS = kMaxState / kLPC;    // states per lane
   static constexpr int R = 64 / kLPC;            // channels per wave
@@ -132,9 +95,6 @@ template <int kLPC> struct SeqCfg {
 };
 
 // One wave's work: channels ch_base .. ch_base + R of sample b, the whole sequence.  tD: the wave's LDS tiles.
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
 template <typename T, bool kHasZ, int kLPC, bool kDt = false>
 __device__ __forceinline__ void seq_body(const SeqArgs& p, const int b, const int ch_base, float* tD) {
   typedef SeqCfg<kLPC> Cfg;
@@ -505,22 +465,30 @@ template <typename T, int kLPC>
 static void launch_seq_lpc(const SeqArgs& a, hipStream_t s) {
   const int ch_per_wg = (kSeqThreads / 64) * SeqCfg<kLPC>::R;
   dim3 grid((a.dim + ch_per_wg - 1) / ch_per_wg, a.batch);
-  if (a.dt) {                                              // the mixer's form: gated, delta formed in the kernel
+  if (a.dt)                                                // the mixer's form: gated, delta formed in the kernel
     hipLaunchKernelGGL((scan_fwd_seq_kernel<T, true, kLPC, true>), grid, dim3(kSeqThreads), 0, s, a);
-    return;
-  }
-  if (a.z)
+  else if (a.z)
     hipLaunchKernelGGL((scan_fwd_seq_kernel<T, true, kLPC>), grid, dim3(kSeqThreads), 0, s, a);
   else
     hipLaunchKernelGGL((scan_fwd_seq_kernel<T, false, kLPC>), grid, dim3(kSeqThreads), 0, s, a);
+}
+
+template <typename T, bool kDt>
+static void launch_seq_mix(const SeqArgs& a, hipStream_t s) {
+  const unsigned grid = static_cast<unsigned>(a.batch) * ((a.dim - a.mix_c4) / SeqCfg<2>::R + a.mix_c4 / SeqCfg<4>::R);
+  if constexpr (kDt)
+    hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<T, true, true>), dim3(grid), dim3(64), 0, s, a);
+  else if (a.z)
+    hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<T, true>), dim3(grid), dim3(64), 0, s, a);
+  else
+    hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<T, false>), dim3(grid), dim3(64), 0, s, a);
 }
 
 // How this kernel would read B and C: 1 = 16-byte (fp32) / 8-byte (bf16) packs along time (t is the unit-stride axis),
 // 2 = packs along the state (n is: the mixer's x_proj output), 0 = neither keeps a pack aligned -- such operands go
 // to the row-scan kernel, which gathers element by element.
 int scan_fwd_seq_bc_mode(const void* B, const void* C, int io_dtype, long long bc_bs, long long bc_ns, long long bc_ts) {
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  const uintptr_t pm = 4 * esz - 1;
+  const uintptr_t pm = 4 * scan_esz(io_dtype) - 1;
   if (((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & pm) != 0 || bc_bs % 4 != 0) return 0;
   if (bc_ts == 1 && bc_ns % 4 == 0) return 1;
   if (bc_ns == 1 && bc_ts % 4 == 0) return 2;
@@ -564,25 +532,13 @@ int scan_fwd_seq_dispatch(const void* u, const void* delta, const float* A, cons
   a.bc_bs = bc_bs; a.bc_ns = bc_ns; a.bc_ts = bc_ts;
   a.bc_mode = scan_fwd_seq_bc_mode(B, C, io_dtype, bc_bs, bc_ns, bc_ts);
   if (a.bc_mode == 0) return SIMAMBA_E_VARIANT;
+  const bool f32 = io_dtype == SIMAMBA_F32;
   if (lpc == 6) {
     a.mix_c4 = scan_fwd_seq_mix_c4(batch, dim);
     if (a.mix_c4 == 0) return SIMAMBA_E_VARIANT;
-    const unsigned grid = static_cast<unsigned>(batch) * ((dim - a.mix_c4) / SeqCfg<2>::R + a.mix_c4 / SeqCfg<4>::R);
-    if (a.dt) {
-      if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<float, true, true>), dim3(grid), dim3(64), 0, s, a);
-      else hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<bf16_t, true, true>), dim3(grid), dim3(64), 0, s, a);
-      return static_cast<int>(hipGetLastError());
-    }
-    if (io_dtype == SIMAMBA_F32) {
-      if (z) hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<float, true>), dim3(grid), dim3(64), 0, s, a);
-      else hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<float, false>), dim3(grid), dim3(64), 0, s, a);
-    } else {
-      if (z) hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<bf16_t, true>), dim3(grid), dim3(64), 0, s, a);
-      else hipLaunchKernelGGL((scan_fwd_seq_mix_kernel<bf16_t, false>), dim3(grid), dim3(64), 0, s, a);
-    }
-    return static_cast<int>(hipGetLastError());
-  }
-  if (io_dtype == SIMAMBA_F32) {
+    if (a.dt) { if (f32) launch_seq_mix<float, true>(a, s); else launch_seq_mix<bf16_t, true>(a, s); }
+    else if (f32) launch_seq_mix<float, false>(a, s); else launch_seq_mix<bf16_t, false>(a, s);
+  } else if (f32) {
     if (lpc == 2) launch_seq_lpc<float, 2>(a, s); else launch_seq_lpc<float, 4>(a, s);
   } else {
     if (lpc == 2) launch_seq_lpc<bf16_t, 2>(a, s); else launch_seq_lpc<bf16_t, 4>(a, s);

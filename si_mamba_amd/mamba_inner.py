@@ -287,13 +287,10 @@ class MambaInnerFn(torch.autograd.Function):
         dA, dB, dC, dD, dbias = _lib.scan_bwd_accumulators(Bsz, Dm, L, N, Df is not None, bf is not None, dev)
         Bv, Cv = x_dbl[:, :, R:R + N], x_dbl[:, :, R + N:]
         z, dz = xz[:, Dm:], dxz[:, Dm:]
-        det = _lib.deterministic_enabled()          # partials + fixed-order sums instead of float atomics
-        flags, ws, nws = 0, None, 0
-        if det:
-            flags, ws, nws = _lib.bwd_flags_workspace(
-                lib.simamba_scan_bwd_workspace_floats(Bsz, Dm, L, N, _lib.CKPT_SEQ if ctx.dtw_k is not None
-                                                      else ctx.ckpt_step, _lib.BWD_DETERMINISTIC), dev)
-        _lib.count("scan_bwd_det" if det else "scan_bwd_atomic")
+        # deterministic: partials + fixed-order sums instead of float atomics
+        flags, ws, nws = _lib.det_args(lib.simamba_scan_bwd_workspace_floats, Bsz, Dm, L, N,
+                                       _lib.CKPT_SEQ if ctx.dtw_k is not None else ctx.ckpt_step, device=dev)
+        _lib.count("scan_bwd_det" if flags else "scan_bwd_atomic")
         with torch.cuda.device(dev), _lib.timed("scan_bwd", dev):
             if ctx.dtw_k is not None:
                 rc = lib.simamba_selective_scan_dt_bwd_ex(
@@ -330,11 +327,8 @@ class MambaInnerFn(torch.autograd.Function):
         dconv = torch.empty(Dm * W + (Dm if cb is not None else 0), **f32)
         dcw = dconv[:Dm * W].view(Dm, W)
         dcb = dconv[Dm * W:] if cb is not None else None
-        flags, ws, nws = 0, None, 0
-        if det:
-            flags, ws, nws = _lib.bwd_flags_workspace(
-                lib.simamba_causal_conv1d_bwd_workspace_floats(Bsz, Dm, L, W, _lib.BWD_DETERMINISTIC), dev)
-        _lib.count("conv1d_bwd_det" if det else "conv1d_bwd_atomic")
+        flags, ws, nws = _lib.det_args(lib.simamba_causal_conv1d_bwd_workspace_floats, Bsz, Dm, L, W, device=dev)
+        _lib.count("conv1d_bwd_det" if flags else "conv1d_bwd_atomic")
         with torch.cuda.device(dev), _lib.timed("conv1d_bwd", dev):
             rc = lib.simamba_causal_conv1d_bwd_ex(xz.data_ptr(), cw.data_ptr(), _lib.ptr(cb), du.data_ptr(),
                                                   dxz.data_ptr(), dcw.data_ptr(), _lib.ptr(dcb),

@@ -100,10 +100,9 @@ class SelectiveScanFn(torch.autograd.Function):
         dz = torch.empty_like(uc) if zc is not None else None
         dA, dB, dC, dD, dbias = _lib.scan_bwd_accumulators(batch, dim, L, N, Dc is not None, bc is not None,
                                                            uc.device)
-        flags, ws, nws = 0, None, 0
-        if _lib.deterministic_enabled():            # partials + fixed-order sum instead of float atomics
-            flags, ws, nws = _lib.bwd_flags_workspace(
-                lib.simamba_scan_bwd_workspace_floats(batch, dim, L, N, ctx.ckpt_step, _lib.BWD_DETERMINISTIC), uc.device)
+        # deterministic: partials + fixed-order sum instead of float atomics
+        flags, ws, nws = _lib.det_args(lib.simamba_scan_bwd_workspace_floats, batch, dim, L, N, ctx.ckpt_step,
+                                       device=uc.device)
         _lib.count("scan_bwd_det" if flags else "scan_bwd_atomic")
         with torch.cuda.device(uc.device), _lib.timed("scan_bwd", uc.device):
             rc = lib.simamba_selective_scan_bwd_ex(

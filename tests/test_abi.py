@@ -56,6 +56,89 @@ def test_version_strerror_and_chunks():
     assert b"variant" in lib.simamba_strerror(-9)
 
 
+# The *_ex scan backward, the dt pair and the workspace query.  Every row states what it changes in a call that would
+# otherwise be accepted, and the code the library answers; rows with two faults pin the order of the checks.  P is a
+# 16-byte aligned address that is never dereferenced: no row gets as far as a memset or a launch.  (An empty backward
+# problem that passes validation clears the caller's accumulators, a device call, so it has no row here; the rows with
+# batch == 0 show that the checks in front of that still run.)
+P, OFF = 1 << 20, (1 << 20) + 4
+_BWD_EX = dict(u=P, delta=P, A=P, B=P, C=P, D=None, z=None, delta_bias=None, dout=P, x_ckpt=P, du=P, ddelta=P, dA=P,
+               dB=P, dC=P, dD=None, dz=None, ddelta_bias=None, batch=2, dim=64, seqlen=32, dstate=16, io_dtype=0,
+               softplus=1, z_bs=0, dz_bs=0, bc_bs=0, bc_ns=0, bc_ts=0, ckpt_step=16, flags=1, workspace=P,
+               workspace_floats=1 << 40, stream=None)
+_DT_FWD = dict(u=P, xdbl=P, wdt=P, A=P, D=None, z=P, delta_bias=None, out=P, x_ckpt=None, last_state=None, batch=2,
+               dim=64, seqlen=32, dstate=16, dt_rank=8, io_dtype=0, z_bs=0, xdbl_bs=0, xdbl_ts=0, ckpt_step=0,
+               variant=0, stream=None)
+_DT_BWD_EX = dict(u=P, xdbl=P, wdt=P, A=P, D=None, z=P, delta_bias=None, dout=P, x_ckpt=P, du=P, ddelta=P, dA=P, dB=P,
+                  dC=P, dD=None, dz=P, ddelta_bias=None, batch=2, dim=64, seqlen=32, dstate=16, dt_rank=8, io_dtype=0,
+                  z_bs=0, dz_bs=0, xdbl_bs=0, xdbl_ts=0, flags=1, workspace=P, workspace_floats=1 << 40, stream=None)
+_WS = dict(batch=2, dim=64, seqlen=32, dstate=16, ckpt_step=16, flags=1)
+
+SCAN_ROWS = [
+    # ---- simamba_selective_scan_bwd_ex -----------------------------------------------------------------------------
+    ("simamba_selective_scan_bwd_ex", _BWD_EX, [
+        (dict(dim=0), -2), (dict(batch=65536), -2), (dict(seqlen=-1), -2),                    # shape
+        (dict(dstate=17), -4), (dict(dstate=0), -4), (dict(io_dtype=7), -3),
+        (dict(ckpt_step=32), -9), (dict(flags=2), -9), (dict(flags=3), -9),
+        (dict(A=None), -1), (dict(dA=None), -1), (dict(u=None), -1), (dict(delta=None), -1), (dict(dC=None), -1),
+        (dict(z=P), -1), (dict(dz=P), -1),                                                    # z and dz go together
+        (dict(x_ckpt=None), -1), (dict(x_ckpt=None, ckpt_step=128, seqlen=132), -1),
+        (dict(workspace=None), -6), (dict(workspace_floats=64), -6), (dict(workspace=OFF), -8),
+        (dict(batch=0, dA=None), -1), (dict(seqlen=0, workspace=OFF), -8),                    # empty, and still checked
+        # what the sequential kernel cannot take (deterministic: nothing is cleared in front of this answer)
+        (dict(dim=32), -9), (dict(dstate=8), -9), (dict(softplus=0), -9), (dict(u=OFF), -9), (dict(ddelta=OFF), -9),
+        (dict(seqlen=30), -9), (dict(io_dtype=1, seqlen=36), -9), (dict(A=OFF), -9), (dict(x_ckpt=OFF), -9),
+        (dict(B=OFF), -9), (dict(bc_bs=514, bc_ns=32, bc_ts=1), -9), (dict(bc_bs=512, bc_ns=2, bc_ts=32), -9),
+        (dict(z=P, dz=OFF), -9), (dict(z=P, dz=P, z_bs=2050), -9), (dict(z=P, dz=P, dz_bs=1 << 29), -9),
+        (dict(batch=4096, dim=4096, seqlen=64), -9),                                          # rows * seqlen = 2^30
+        # two faults: flags, shape, ckpt_step, dstate, dtype, pointers, workspace size, workspace alignment, kernel
+        (dict(flags=2, dim=0), -9), (dict(dim=0, ckpt_step=32), -2), (dict(ckpt_step=32, dstate=17), -9),
+        (dict(dstate=17, io_dtype=7), -4), (dict(io_dtype=7, A=None), -3), (dict(u=None, workspace=None), -1),
+        (dict(workspace=OFF, workspace_floats=64), -6), (dict(workspace=OFF, dim=32), -8),
+    ]),
+    # ---- simamba_selective_scan_dt_fwd -----------------------------------------------------------------------------
+    ("simamba_selective_scan_dt_fwd", _DT_FWD, [
+        (dict(dim=0), -2), (dict(batch=65536), -2), (dict(dstate=8), -4), (dict(io_dtype=7), -3),
+        (dict(ckpt_step=32), -9), (dict(variant=1), -9), (dict(variant=3), -9),
+        (dict(dt_rank=6), -2), (dict(dt_rank=0), -2), (dict(dt_rank=28), -2),                 # fp32: packs of 4
+        (dict(io_dtype=1, seqlen=64, dt_rank=4), -2), (dict(io_dtype=1, seqlen=64, dt_rank=12), -2),   # bf16: of 8
+        (dict(u=None), -1), (dict(xdbl=None), -1), (dict(wdt=None), -1), (dict(z=None), -1), (dict(out=None), -1),
+        (dict(xdbl=OFF), -9), (dict(wdt=OFF), -9), (dict(u=OFF), -9), (dict(A=OFF), -9), (dict(seqlen=30), -9),
+        (dict(xdbl_bs=1 << 29), -9), (dict(xdbl_ts=42), -9), (dict(z_bs=2050), -9), (dict(z_bs=1 << 29), -9),
+        (dict(batch=4096, dim=4096, seqlen=64), -9),
+        (dict(batch=0), 0), (dict(seqlen=0, u=None, xdbl=None, out=None), 0),                 # empty problems
+        # two faults: shape, dstate, dtype, ckpt_step, variant, dt_rank, empty, pointers, the kernel's conditions
+        (dict(dim=0, dstate=8), -2), (dict(dstate=8, io_dtype=7), -4), (dict(io_dtype=7, ckpt_step=32), -3),
+        (dict(variant=1, dt_rank=6), -9), (dict(dt_rank=6, batch=0), -2), (dict(batch=0, xdbl=OFF), 0),
+        (dict(u=None, xdbl=OFF), -1),
+    ]),
+    # ---- simamba_selective_scan_dt_bwd_ex --------------------------------------------------------------------------
+    ("simamba_selective_scan_dt_bwd_ex", _DT_BWD_EX, [
+        (dict(flags=2), -9), (dict(dstate=8), -4), (dict(io_dtype=7), -3),
+        (dict(dt_rank=6), -2), (dict(dt_rank=28), -2),
+        (dict(io_dtype=1, seqlen=64, dt_rank=4), -2), (dict(io_dtype=1, seqlen=64, dt_rank=12), -2),
+        (dict(xdbl=None), -1), (dict(wdt=None), -1), (dict(z=None), -1),
+        (dict(xdbl=OFF), -9), (dict(wdt=OFF), -9), (dict(xdbl_bs=1 << 29), -9), (dict(xdbl_ts=42), -9),
+        (dict(dim=0), -2), (dict(batch=65536), -2), (dict(u=None), -1), (dict(dA=None), -1), (dict(dz=None), -1),
+        (dict(x_ckpt=None), -1), (dict(workspace=None), -6), (dict(workspace_floats=64), -6),
+        (dict(workspace=OFF), -8), (dict(batch=0, dA=None), -1), (dict(seqlen=0, workspace=OFF), -8),
+        (dict(dim=32), -9), (dict(u=OFF), -9), (dict(seqlen=30), -9), (dict(A=OFF), -9), (dict(dz_bs=2050), -9),
+        # two faults: flags, dstate, dtype, dt_rank, pointers, xdbl's layout -- all in front of the shape check
+        (dict(flags=2, dstate=8), -9), (dict(dstate=8, dim=0), -4), (dict(io_dtype=7, dt_rank=6), -3),
+        (dict(dt_rank=6, xdbl=None), -2), (dict(xdbl=None, wdt=OFF), -1), (dict(xdbl=OFF, dim=0), -9),
+        (dict(batch=0, xdbl=OFF), -9), (dict(dim=0, workspace=None), -2),
+    ]),
+    # ---- simamba_scan_bwd_workspace_floats -------------------------------------------------------------------------
+    ("simamba_scan_bwd_workspace_floats", _WS, [
+        (dict(flags=2), -9), (dict(flags=0), 0), (dict(flags=0, dim=0), 0),                   # no flag: no workspace
+        (dict(dim=0), -2), (dict(batch=65536), -2), (dict(dstate=17), -4), (dict(ckpt_step=32), -9),
+        (dict(batch=0), 0),
+        (dict(), 4352), (dict(ckpt_step=0, seqlen=200), 55808),
+        (dict(flags=2, dim=0), -9), (dict(dim=0, dstate=17), -2), (dict(dstate=17, ckpt_step=32), -4),
+    ]),
+]
+
+
 def test_argument_validation_precedes_any_launch():
     lib = _lib.load()
     n = None
@@ -75,6 +158,10 @@ def test_argument_validation_precedes_any_launch():
     assert lib.simamba_knn_graph(one, one, n, 0, 1, 16, 3, 16, 1.0, 0, n) == -7
     assert lib.simamba_spectral_topk(one, n, n, n, one, 8, 1, 16, 4, 1.0, 4, 0, n) == -6
     assert lib.simamba_argsort_rows(one, one, 1, 2048, n) == -2
+    for name, base, rows in SCAN_ROWS:
+        for change, want in rows:
+            assert set(change) <= set(base), change
+            assert getattr(lib, name)(*{**base, **change}.values()) == want, (name, change)
 
 
 def test_product_path_refuses_cpu_tensors():
