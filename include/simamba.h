@@ -390,6 +390,24 @@ int simamba_in_proj_fwd(const void* x, const void* w, void* xz, int batch, int L
  *   it), dweight, dbias (C) fp32 ; same partial scratch.
  * simamba_group_max_fwd/bwd: out[g][c] = max_r x[g][r][c] over r < n (first maximum; NaN propagates), idx the
  *   arg max as uint8 (n <= 256); backward routes dout to that row and writes zeros elsewhere (one pass).
+ *
+ * The same passes as separate stages, for batch statistics taken over the rows of several ranks (nn.SyncBatchNorm):
+ * the caller puts one collective between them each way.  Shapes, ld, gterm / group, dgterm / dgroup and the order of
+ * the argument checks (dtype, empty, shape, null pointers) are those of the two calls above.
+ * simamba_bn_stats_local: pass 1 and its fp64 finalize over this rank's rows.  stats : (3, C) fp64 with row stride
+ *   stats_ld (0 = C; a channel slice writes into the block of the whole layer): row 0 the row count, row 1 the mean,
+ *   row 2 M2 = sum (x + g - mean)^2 -- free of the rank's own shift, so blocks of different ranks merge.  Running
+ *   statistics are not touched.
+ * simamba_bn_stats_merge: stats : (world, 3, C) fp64 contiguous, the all-gather of the ranks' blocks (any C >= 1, the
+ *   whole layer in one call).  Merged in fp64 in rank order 0 .. world-1 with the pairwise update n = na + nb,
+ *   d = mb - ma, mean = ma + d nb / n, M2 = M2a + M2b + d^2 na nb / n: the same bits on every rank.  Writes mean,
+ *   invstd = 1 / sqrt(M2 / n + eps) (C) fp32, count (1) fp64 = n, and updates running_mean / running_var (non-NULL)
+ *   with `momentum`, running_var from the unbiased variance M2 / (n - 1) of the total count.
+ * simamba_bn_relu_apply: pass 2, y = relu((x + g - mean) * invstd * w + b), with the caller's mean / invstd.
+ * simamba_bn_relu_bwd_sums: the backward's pass 1 and its finalize: dbias = sum dy*mask and
+ *   dweight = sum dy*mask*xhat over THIS rank's rows, with the global mean / invstd.
+ * simamba_bn_relu_bwd_dx: the backward's pass 2 with sum_dweight / sum_dbias (C) fp32 summed over all ranks and
+ *   count (1) fp64, the row count of all ranks, read on the device (the buffer simamba_bn_stats_merge wrote).
  */
 int simamba_bn_relu_grid(long long rows);
 int simamba_bn_relu_fwd(const void* x, const float* gterm, int group, const float* weight, const float* bias,
@@ -400,6 +418,21 @@ int simamba_bn_relu_bwd(const void* dy, const void* x, const float* gterm, int g
                         const float* bias, const float* mean, const float* invstd, void* dx, float* dgterm,
                         int dgroup, float* dweight, float* dbias, float* partial, long long rows, int C,
                         long long ld, int io_dtype, int training, void* stream);
+int simamba_bn_stats_local(const void* x, const float* gterm, int group, double* stats, long long stats_ld,
+                           float* partial, long long rows, int C, long long ld, int io_dtype, void* stream);
+int simamba_bn_stats_merge(const double* stats, int world, float* running_mean, float* running_var, float momentum,
+                           float eps, float* mean, float* invstd, double* count, int C, void* stream);
+int simamba_bn_relu_apply(const void* x, const float* gterm, int group, const float* weight, const float* bias,
+                          const float* mean, const float* invstd, void* y, long long rows, int C, long long ld,
+                          int io_dtype, void* stream);
+int simamba_bn_relu_bwd_sums(const void* dy, const void* x, const float* gterm, int group, const float* weight,
+                             const float* bias, const float* mean, const float* invstd, float* dweight,
+                             float* dbias, float* partial, long long rows, int C, long long ld, int io_dtype,
+                             void* stream);
+int simamba_bn_relu_bwd_dx(const void* dy, const void* x, const float* gterm, int group, const float* weight,
+                           const float* bias, const float* mean, const float* invstd, const float* sum_dweight,
+                           const float* sum_dbias, const double* count, void* dx, float* dgterm, int dgroup,
+                           long long rows, int C, long long ld, int io_dtype, void* stream);
 int simamba_group_max_fwd(const void* x, void* out, unsigned char* idx, long long groups, int n, int C,
                           int io_dtype, void* stream);
 int simamba_group_max_bwd(const void* dout, const unsigned char* idx, void* dx, long long groups, int n, int C,

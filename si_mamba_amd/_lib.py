@@ -100,6 +100,12 @@ SIGNATURES = {
                                     _LL, c_int, _P]),
     "simamba_bn_relu_bwd": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _LL, c_int, _LL,
                                     c_int, c_int, _P]),
+    "simamba_bn_stats_local": (c_int, [_P, _P, c_int, _P, _LL, _P, _LL, c_int, _LL, c_int, _P]),
+    "simamba_bn_stats_merge": (c_int, [_P, c_int, _P, _P, c_float, c_float, _P, _P, _P, c_int, _P]),
+    "simamba_bn_relu_apply": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _LL, c_int, _LL, c_int, _P]),
+    "simamba_bn_relu_bwd_sums": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _LL, c_int, _LL, c_int, _P]),
+    "simamba_bn_relu_bwd_dx": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _LL, c_int, _LL,
+                                       c_int, _P]),
     "simamba_group_max_fwd": (c_int, [_P, _P, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_group_max_bwd": (c_int, [_P, _P, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_three_nn": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),

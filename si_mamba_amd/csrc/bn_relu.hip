@@ -18,6 +18,14 @@
 // chunk of kBnChunk rows.  Per-workgroup partial sums go to a (grid, 2, C) buffer and are combined in fp64 by
 // a one-workgroup finalize kernel: deterministic, no atomics.  Sums are taken about the first row's value
 // (shifted data), which removes the cancellation in E[x^2] - E[x]^2.
+//
+// Cross-rank statistics (nn.SyncBatchNorm): the same kernels, entered stage by stage so that a collective fits between
+// the passes.  simamba_bn_stats_local leaves this rank's (count, mean, M2 = sum (x - mean)^2) per channel in fp64 -- free
+// of the rank's own shift -- simamba_bn_stats_merge combines the all-gathered (W, 3, C) block in rank order with the
+// pairwise update of Chan et al. (every rank gets the same bits), simamba_bn_relu_apply is pass 2 with those
+// statistics; simamba_bn_relu_bwd_sums leaves the rank's (sum dy*mask, sum dy*mask*xhat), the caller all-reduces them,
+// simamba_bn_relu_bwd_dx is the backward's pass 2 with the global sums and the global row count (read from the device
+// buffer the merge wrote: no host read anywhere).
 #include "common.h"
 
 namespace simamba {
@@ -36,6 +44,7 @@ struct BnArgs {
   void* y;            // forward output / backward dx
   float* dgterm;
   float* partial;     // (grid, 2, C)
+  const double* count;  // staged backward: the row count of all ranks (device); NULL: rows
   long long rows;
   long long ld;       // row stride (elements) of x / y / dy / dx: channel slices of a wider tensor are processed in place
   int C, group, dgroup, training;
@@ -153,6 +162,59 @@ __global__ __launch_bounds__(kFinCh * kFinPl) void bn_stats_finalize_kernel(
   }
 }
 
+// staged form of the finalize: this rank's (count, mean, M2) per channel in fp64, rows of a (3, C) block with row stride
+// sld.  M2 = sum (x - mean)^2 = S2 - S1^2 / n does not depend on the shift K, so blocks of ranks with different first
+// rows can be merged.  No running statistics here: they belong to the merged result.
+template <typename T>
+__global__ __launch_bounds__(kFinCh * kFinPl) void bn_stats_local_finalize_kernel(
+    const void* x, const float* gterm, const float* partial, int grid, long long rows, int C, double* stats,
+    long long sld) {
+  __shared__ double sm[2][kFinPl][kFinCh];
+  const int c = blockIdx.x * kFinCh + threadIdx.x % kFinCh, pl = threadIdx.x / kFinCh;
+  double S1, S2;
+  finalize_sums(partial, grid, C, c, pl, c < C, sm, S1, S2);
+  if (c >= C || pl != 0) return;
+  float K = to_f32<T>(static_cast<const T*>(x)[c]);
+  if (gterm) K += gterm[c];
+  const double n = static_cast<double>(rows);
+  double m2 = S2 - S1 * S1 / n;
+  m2 = m2 < 0.0 ? 0.0 : m2;
+  stats[c] = n;
+  stats[sld + c] = static_cast<double>(K) + S1 / n;
+  stats[2 * sld + c] = m2;
+}
+
+// merge of the all-gathered (W, 3, C) block, one thread per channel, ranks in the order 0 .. W-1 (a fixed order: every
+// rank computes the same bits).  Pairwise update: n = na + nb, d = mb - ma, mean = ma + d nb / n,
+// M2 = M2a + M2b + d^2 na nb / n.  Never E[x^2] - E[x]^2.
+__global__ void bn_stats_merge_kernel(const double* __restrict__ stats, int W, int C, float eps, float momentum,
+                                      float* mean, float* invstd, double* count, float* running_mean,
+                                      float* running_var) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double n = 0.0, mu = 0.0, m2 = 0.0;
+  for (int w = 0; w < W; ++w) {
+    const double* b = stats + static_cast<size_t>(w) * 3 * C;
+    const double nb = b[c];
+    if (!(nb > 0.0)) continue;                        // a rank without rows adds nothing
+    if (n == 0.0) { n = nb; mu = b[C + c]; m2 = b[2 * C + c]; continue; }
+    const double nn = n + nb, d = b[C + c] - mu;
+    mu += d * (nb / nn);
+    m2 += b[2 * C + c] + d * d * (n * nb / nn);
+    n = nn;
+  }
+  double var = n > 0.0 ? m2 / n : 0.0;
+  var = var < 0.0 ? 0.0 : var;
+  mean[c] = static_cast<float>(mu);
+  invstd[c] = static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps)));
+  if (running_mean) running_mean[c] = static_cast<float>((1.0 - momentum) * running_mean[c] + momentum * mu);
+  if (running_var) {
+    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+    running_var[c] = static_cast<float>((1.0 - momentum) * running_var[c] + momentum * unbiased);
+  }
+  if (c == 0) *count = n;
+}
+
 // eval mode: statistics are the running ones
 __global__ void bn_eval_stats_kernel(const float* running_mean, const float* running_var, float eps, int C,
                                      float* mean, float* invstd) {
@@ -253,7 +315,7 @@ __global__ __launch_bounds__(kBnMaxThreads) void bn_relu_bwd_dx_kernel(BnArgs p,
   const T* __restrict__ dy = static_cast<const T*>(p.dy);
   T* __restrict__ dx = static_cast<T*>(p.y);
   float scale[4], shift[4], mu[4], is[4], kb[4], kw[4];
-  const float inv_n = 1.f / static_cast<float>(p.rows);
+  const float inv_n = 1.f / (p.count ? static_cast<float>(*p.count) : static_cast<float>(p.rows));
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = 4 * cl + i;
@@ -437,6 +499,116 @@ extern "C" int simamba_bn_relu_bwd(const void* dy, const void* x, const float* g
                      dweight, dbias);
   if (f32) hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<float>, dim3(grid), block, sizeof(float) * C * rl, s, a, dweight, dbias);
   else hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<bf16_t>, dim3(grid), block, sizeof(float) * C * rl, s, a, dweight, dbias);
+  return static_cast<int>(hipGetLastError());
+}
+
+// ---- staged entry points (cross-rank statistics) ------------------------------------------------------------------
+extern "C" int simamba_bn_stats_local(const void* x, const float* gterm, int group, double* stats, long long stats_ld,
+                                      float* partial, long long rows, int C, long long ld, int io_dtype,
+                                      void* stream) {
+  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (rows == 0) return SIMAMBA_OK;
+  if (ld == 0) ld = C;
+  if (stats_ld == 0) stats_ld = C;
+  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr) || stats_ld < C) return SIMAMBA_E_SHAPE;
+  if (!x || !stats || !partial) return SIMAMBA_E_NULLPTR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BnArgs a{};
+  a.x = x; a.gterm = gterm; a.partial = partial; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group;
+  a.training = 1;
+  const int grid = simamba_bn_relu_grid(rows);
+  const dim3 block = bn_block(C);
+  const size_t smem = sizeof(float) * 2 * C * bn_row_lanes(C);
+  const dim3 fgrid((C + kFinCh - 1) / kFinCh), fblock(kFinCh * kFinPl);
+  if (io_dtype == SIMAMBA_F32) {
+    hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(grid), block, smem, s, a);
+    hipLaunchKernelGGL(bn_stats_local_finalize_kernel<float>, fgrid, fblock, 0, s, x, gterm, partial, grid, rows, C,
+                       stats, stats_ld);
+  } else {
+    hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, dim3(grid), block, smem, s, a);
+    hipLaunchKernelGGL(bn_stats_local_finalize_kernel<bf16_t>, fgrid, fblock, 0, s, x, gterm, partial, grid, rows, C,
+                       stats, stats_ld);
+  }
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_bn_stats_merge(const double* stats, int world, float* running_mean, float* running_var,
+                                      float momentum, float eps, float* mean, float* invstd, double* count, int C,
+                                      void* stream) {
+  if (C == 0) return SIMAMBA_OK;
+  if (world < 1 || C < 0) return SIMAMBA_E_SHAPE;
+  if (!stats || !mean || !invstd || !count) return SIMAMBA_E_NULLPTR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(bn_stats_merge_kernel, dim3((C + 127) / 128), dim3(128), 0, s, stats, world, C, eps, momentum,
+                     mean, invstd, count, running_mean, running_var);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_bn_relu_apply(const void* x, const float* gterm, int group, const float* weight,
+                                     const float* bias, const float* mean, const float* invstd, void* y,
+                                     long long rows, int C, long long ld, int io_dtype, void* stream) {
+  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (rows == 0) return SIMAMBA_OK;
+  if (ld == 0) ld = C;
+  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
+  if (!x || !y || !mean || !invstd) return SIMAMBA_E_NULLPTR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BnArgs a{};
+  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
+  a.y = y; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group; a.training = 1;
+  const int grid = simamba_bn_relu_grid(rows);
+  if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL(bn_relu_apply_kernel<float>, dim3(grid), bn_block(C), 0, s, a);
+  else hipLaunchKernelGGL(bn_relu_apply_kernel<bf16_t>, dim3(grid), bn_block(C), 0, s, a);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_bn_relu_bwd_sums(const void* dy, const void* x, const float* gterm, int group,
+                                        const float* weight, const float* bias, const float* mean,
+                                        const float* invstd, float* dweight, float* dbias, float* partial,
+                                        long long rows, int C, long long ld, int io_dtype, void* stream) {
+  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (rows == 0) return SIMAMBA_OK;
+  if (ld == 0) ld = C;
+  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
+  if (!dy || !x || !mean || !invstd || !dweight || !dbias || !partial) return SIMAMBA_E_NULLPTR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BnArgs a{};
+  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
+  a.dy = dy; a.partial = partial; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group; a.training = 1;
+  const int grid = simamba_bn_relu_grid(rows);
+  const dim3 block = bn_block(C);
+  const size_t smem = sizeof(float) * 2 * C * bn_row_lanes(C);
+  if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<float>, dim3(grid), block, smem, s, a);
+  else hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<bf16_t>, dim3(grid), block, smem, s, a);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * kFinPl), 0, s, partial, grid, C,
+                     dweight, dbias);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_bn_relu_bwd_dx(const void* dy, const void* x, const float* gterm, int group,
+                                      const float* weight, const float* bias, const float* mean, const float* invstd,
+                                      const float* sum_dweight, const float* sum_dbias, const double* count, void* dx,
+                                      float* dgterm, int dgroup, long long rows, int C, long long ld, int io_dtype,
+                                      void* stream) {
+  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (rows == 0) return SIMAMBA_OK;
+  if (ld == 0) ld = C;
+  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
+  if (dgterm && (dgroup <= 0 || (kBnChunk % dgroup) != 0 || (rows % dgroup) != 0)) return SIMAMBA_E_SHAPE;
+  if (!dy || !x || !mean || !invstd || !dx || !sum_dweight || !sum_dbias || !count) return SIMAMBA_E_NULLPTR;
+  if (dgterm && !gterm) return SIMAMBA_E_NULLPTR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  BnArgs a{};
+  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
+  a.dy = dy; a.y = dx; a.dgterm = dgterm; a.count = count; a.rows = rows; a.ld = ld; a.C = C; a.group = group;
+  a.dgroup = dgroup; a.training = 1;
+  const int grid = simamba_bn_relu_grid(rows);
+  const dim3 block = bn_block(C);
+  const size_t smem = sizeof(float) * C * bn_row_lanes(C);
+  if (io_dtype == SIMAMBA_F32)
+    hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<float>, dim3(grid), block, smem, s, a, sum_dweight, sum_dbias);
+  else
+    hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<bf16_t>, dim3(grid), block, smem, s, a, sum_dweight, sum_dbias);
   return static_cast<int>(hipGetLastError());
 }
 

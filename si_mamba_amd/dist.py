@@ -2,7 +2,9 @@
 
 Mirrors reference utils/dist_utils.py:9-54 (init_dist / reduce_tensor / gather_tensor) and the DDP
 wrap of tools/runner_finetune.py:124-125.  The hot-path kernels have no cross-sample term, so the
-only collective per step is the bucketed gradient all-reduce DDP issues on its own RCCL stream.
+only collective per step is the bucketed gradient all-reduce DDP issues on its own RCCL stream --
+unless the model was converted to nn.SyncBatchNorm (--sync_bn), whose layers add one all-gather of
+(3, C) float64 forward and one all-reduce of (2, C) float32 backward each (encoder_ops.sync_bn_relu_fn).
 """
 from __future__ import annotations
 

@@ -11,12 +11,19 @@
                   tiles: the library's kernels for it leave most of the chip idle (bf16: 540-790 us per layer
                   against 44-143 us split; fp32: 443-1 778 against 156-750 us; tools/bench_wgrad_splitk.py).
 
+  sync_bn_relu_fn the same with batch statistics over the rows of every rank of a process group (nn.SyncBatchNorm,
+                  what the reference's --sync_bn puts in BatchNorm1d's place: tools/runner_finetune.py:121-122,
+                  runner_pretrain.py:111-112): the kernels' stages with one all-gather of (3, C) float64 between
+                  the statistics and the normalisation, and one all-reduce of (2, C) float32 between the two passes
+                  of the backward
+
 bn_relu_fn and group_max_fn are plain autograd Functions over the C ABI; BatchNorm keeps nn.BatchNorm1d's buffers (running_mean,
 running_var, num_batches_tracked) and train/eval semantics.
 """
 from __future__ import annotations
 
 import torch
+import torch.distributed as dist
 
 from . import _lib
 
@@ -126,10 +133,7 @@ class BnReluFn(torch.autograd.Function):
         dx = torch.empty_like(xc)
         dw = torch.empty(C, device=dev, dtype=torch.float32)
         db = torch.empty(C, device=dev, dtype=torch.float32)
-        # the kernel sums dx over runs of dgroup <= 256 rows; wider groups are finished here
-        dgroup = 0 if g is None else (group if _BN_CHUNK % group == 0 else _BN_CHUNK)
-        if g is not None and dgroup == _BN_CHUNK and group % _BN_CHUNK != 0:
-            raise ValueError("bn_relu_fn: group must divide 256 or be a multiple of it")
+        dgroup = _bn_dgroup(g, group)
         dgs = []
         with torch.cuda.device(dev), _lib.timed("bn_relu_bwd", dev):
             for c0, c1 in _slices(C):
@@ -152,18 +156,153 @@ class BnReluFn(torch.autograd.Function):
                 None, None, None, None, None)
 
 
-def bn_relu_fn(x, bn: torch.nn.BatchNorm1d, gterm=None, group=0):
-    """relu(bn(x + gterm[row // group])) for token-major x (rows, C) with ``bn``'s parameters, buffers and mode.
+# ---- the kernels' stages over plain buffers (SyncBnReluFn; the tests drive them with row shards as ranks) --------------
+def _slice_of(g, c0, c1, C):
+    return None if g is None else (g if (c0 == 0 and c1 == C) else g[:, c0:c1].contiguous())
 
-    The HIP kernel computes PER-RANK batch statistics, which is what ``nn.BatchNorm1d`` means.  Any other module
-    type -- in particular the ``nn.SyncBatchNorm`` that ``--sync_bn`` puts in its place
-    (reference tools/runner_finetune.py:121-122, runner_pretrain.py:111-112), whose training statistics are reduced
-    across ranks -- goes through the module itself (stock torch kernels on the same device), so its semantics are
-    kept instead of being silently replaced."""
-    if type(bn) is not torch.nn.BatchNorm1d:
-        if gterm is not None:
-            x = x + gterm.to(x.dtype).repeat_interleave(group, dim=0)
-        return torch.relu(bn(x))
+
+def _bn_partial(lib, rows, C, dev):
+    return torch.empty(lib.simamba_bn_relu_grid(rows), 2, min(C, _BN_MAX_C), device=dev, dtype=torch.float32)
+
+
+def bn_stats_local(xc, g, group, stats, part):
+    """This rank's (count, mean, M2) per channel of xc (rows, C) (+ g[row // group]) into ``stats`` (3, C) float64."""
+    lib = _lib.load()
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    for c0, c1 in _slices(C):
+        rc = lib.simamba_bn_stats_local(_off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(stats, c0),
+                                        C, part.data_ptr(), rows, c1 - c0, C, code, st)
+        _lib.check(rc, "simamba_bn_stats_local")
+
+
+def bn_stats_merge(gathered, running_mean, running_var, momentum, eps, mean, invstd, count):
+    """(W, 3, C) float64 blocks of all ranks -> mean, invstd (C) float32, count (1) float64, running statistics."""
+    world, _, C = gathered.shape
+    rc = _lib.load().simamba_bn_stats_merge(gathered.data_ptr(), world, _lib.ptr(running_mean),
+                                            _lib.ptr(running_var), float(momentum), float(eps), mean.data_ptr(),
+                                            invstd.data_ptr(), count.data_ptr(), C, _lib.stream_ptr(gathered.device))
+    _lib.check(rc, "simamba_bn_stats_merge")
+
+
+def bn_relu_apply(xc, g, group, w, b, mean, invstd, y):
+    lib = _lib.load()
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    for c0, c1 in _slices(C):
+        rc = lib.simamba_bn_relu_apply(_off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(w, c0),
+                                       _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(y, c0), rows, c1 - c0, C,
+                                       code, st)
+        _lib.check(rc, "simamba_bn_relu_apply")
+
+
+def bn_relu_bwd_sums(dyc, xc, g, group, w, b, mean, invstd, sums, part):
+    """This rank's sum dy*mask (``sums[0]``) and sum dy*mask*xhat (``sums[1]``); ``sums`` (2, C) float32."""
+    lib = _lib.load()
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    for c0, c1 in _slices(C):
+        rc = lib.simamba_bn_relu_bwd_sums(_off(dyc, c0), _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group),
+                                          _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0),
+                                          _off(sums[1], c0), _off(sums[0], c0), part.data_ptr(), rows, c1 - c0, C,
+                                          code, st)
+        _lib.check(rc, "simamba_bn_relu_bwd_sums")
+
+
+def _bn_dgroup(g, group):
+    # the kernel sums dx over runs of dgroup <= 256 rows; wider groups are finished by the caller
+    dgroup = 0 if g is None else (group if _BN_CHUNK % group == 0 else _BN_CHUNK)
+    if g is not None and dgroup == _BN_CHUNK and group % _BN_CHUNK != 0:
+        raise ValueError("bn_relu_fn: group must divide 256 or be a multiple of it")
+    return dgroup
+
+
+def bn_relu_bwd_dx(dyc, xc, g, group, w, b, mean, invstd, sums, count, dx):
+    """dx with the sums and the row count of ALL ranks; returns the gradient of g (rows / group, C) float32 or None."""
+    lib = _lib.load()
+    rows, C = xc.shape
+    dev = xc.device
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(dev)
+    dgroup = _bn_dgroup(g, group)
+    dgs = []
+    for c0, c1 in _slices(C):
+        dg = None if g is None else torch.empty(rows // dgroup, c1 - c0, device=dev, dtype=torch.float32)
+        dgs.append(dg)
+        rc = lib.simamba_bn_relu_bwd_dx(_off(dyc, c0), _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group),
+                                        _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(sums[1], c0),
+                                        _off(sums[0], c0), count.data_ptr(), _off(dx, c0), _lib.ptr(dg), dgroup, rows,
+                                        c1 - c0, C, code, st)
+        _lib.check(rc, "simamba_bn_relu_bwd_dx")
+    if g is None:
+        return None
+    dgt = dgs[0] if len(dgs) == 1 else torch.cat(dgs, dim=1)
+    if dgroup != group:
+        dgt = dgt.view(rows // group, group // dgroup, C).sum(1)
+    return dgt
+
+
+class SyncBnReluFn(torch.autograd.Function):
+    """relu(batch_norm(x + g)) in training mode with the statistics of every rank's rows: one all-gather of (3, C)
+    float64 forward, one all-reduce of (2, C) float32 backward, however many channel slices the layer has."""
+
+    @staticmethod
+    def forward(ctx, x, gterm, group, weight, bias, running_mean, running_var, momentum, eps, process_group):
+        _lib.require_gpu(x, "sync_bn_relu_fn")
+        lib = _lib.load()
+        xc = x.contiguous()
+        rows, C = xc.shape
+        dev = xc.device
+        world = dist.get_world_size(process_group)
+        g = None if gterm is None else gterm.float().contiguous()
+        w = None if weight is None else weight.float().contiguous()
+        b = None if bias is None else bias.float().contiguous()
+        y = torch.empty_like(xc)
+        mean = torch.empty(C, device=dev, dtype=torch.float32)
+        invstd = torch.empty(C, device=dev, dtype=torch.float32)
+        count = torch.empty(1, device=dev, dtype=torch.float64)
+        stats = torch.empty(3, C, device=dev, dtype=torch.float64)
+        gathered = torch.empty(world, 3, C, device=dev, dtype=torch.float64)
+        part = _bn_partial(lib, rows, C, dev)
+        with torch.cuda.device(dev), _lib.timed("sync_bn_relu_fwd", dev):
+            bn_stats_local(xc, g, group, stats, part)
+            dist.all_gather_into_tensor(gathered, stats, group=process_group)
+            bn_stats_merge(gathered, running_mean, running_var, momentum, eps, mean, invstd, count)
+            bn_relu_apply(xc, g, group, w, b, mean, invstd, y)
+        ctx.save_for_backward(xc, g, w, b, mean, invstd, count)
+        ctx.meta = (int(group), x.dtype, None if gterm is None else gterm.dtype,
+                    None if weight is None else weight.dtype, None if bias is None else bias.dtype)
+        ctx.part = part
+        ctx.process_group = process_group
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, g, w, b, mean, invstd, count = ctx.saved_tensors
+        group, xdtype, gdtype, wdtype, bdtype = ctx.meta
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(_CAPTURE_MSG)
+        C = xc.shape[1]
+        dev = xc.device
+        dyc = dy.to(xc.dtype).contiguous()
+        dx = torch.empty_like(xc)
+        sums = torch.empty(2, C, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev), _lib.timed("sync_bn_relu_bwd", dev):
+            bn_relu_bwd_sums(dyc, xc, g, group, w, b, mean, invstd, sums, ctx.part)
+            local = sums.clone()             # weight / bias gradients stay this rank's sums (DDP averages them)
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.process_group)
+            dgt = bn_relu_bwd_dx(dyc, xc, g, group, w, b, mean, invstd, sums, count, dx)
+        return (dx.to(xdtype), None if dgt is None else dgt.to(gdtype), None,
+                None if wdtype is None else local[1].to(wdtype), None if bdtype is None else local[0].to(bdtype),
+                None, None, None, None, None)
+
+
+_CAPTURE_MSG = ("sync_bn_relu_fn: the stream is being captured into a graph; the collectives of cross-rank batch "
+                "statistics are not supported inside a capture")
+
+
+def _bn_step(bn):
+    """nn.BatchNorm1d / nn.SyncBatchNorm bookkeeping of one forward: (use batch statistics, momentum, running_mean,
+    running_var to hand to the kernels); counts the batch in num_batches_tracked."""
     training = bn.training or bn.running_mean is None
     momentum = bn.momentum
     if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
@@ -172,8 +311,60 @@ def bn_relu_fn(x, bn: torch.nn.BatchNorm1d, gterm=None, group=0):
             momentum = 1.0 / float(bn.num_batches_tracked)
     rm = bn.running_mean if (bn.track_running_stats and (bn.training or not training)) else None
     rv = bn.running_var if rm is not None else None
-    return BnReluFn.apply(x, gterm, group, bn.weight, bn.bias, rm, rv, 0.0 if momentum is None else momentum,
-                          bn.eps, training)
+    return training, 0.0 if momentum is None else momentum, rm, rv
+
+
+def _bn_relu_local(x, bn, gterm, group):
+    training, momentum, rm, rv = _bn_step(bn)
+    return BnReluFn.apply(x, gterm, group, bn.weight, bn.bias, rm, rv, momentum, bn.eps, training)
+
+
+def sync_bn_relu_fn(x, bn, gterm=None, group=0, process_group=None):
+    """relu(bn(x + gterm[row // group])) with training statistics over the rows of every rank of ``process_group``
+    (``bn.process_group`` when None, else the default group) -- nn.SyncBatchNorm's meaning, on the HIP kernels.
+
+    Ranks may hold different numbers of rows; each needs at least one.  The weight and bias gradients are this rank's
+    own sums, as nn.SyncBatchNorm returns them.  ``bn`` outside training mode uses its running statistics: no
+    collective, the same call as bn_relu_fn."""
+    if not isinstance(bn, (torch.nn.BatchNorm1d, torch.nn.SyncBatchNorm)):
+        raise TypeError(f"sync_bn_relu_fn: expected nn.SyncBatchNorm or nn.BatchNorm1d, got {type(bn).__name__}")
+    if not bn.training:
+        return _bn_relu_local(x, bn, gterm, group)
+    if x.shape[0] < 1:
+        raise ValueError(f"sync_bn_relu_fn: this rank holds {x.shape[0]} rows; every rank needs at least 1")
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("sync_bn_relu_fn: torch.distributed has no initialised process group")
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(_CAPTURE_MSG)
+    if process_group is None:
+        process_group = getattr(bn, "process_group", None)
+    _, momentum, rm, rv = _bn_step(bn)
+    return SyncBnReluFn.apply(x, gterm, group, bn.weight, bn.bias, rm, rv, momentum, bn.eps, process_group)
+
+
+def _sync_world(bn):
+    if not (dist.is_available() and dist.is_initialized()):
+        return 1
+    return dist.get_world_size(bn.process_group)
+
+
+def bn_relu_fn(x, bn: torch.nn.BatchNorm1d, gterm=None, group=0):
+    """relu(bn(x + gterm[row // group])) for token-major x (rows, C) with ``bn``'s parameters, buffers and mode.
+
+    ``nn.BatchNorm1d`` means PER-RANK batch statistics: BnReluFn.  The ``nn.SyncBatchNorm`` that ``--sync_bn`` puts in
+    its place (reference tools/runner_finetune.py:121-122, runner_pretrain.py:111-112) reduces its training
+    statistics across ranks: SyncBnReluFn when it trains in a process group of more than one rank, and BnReluFn in
+    eval mode (running statistics), with a single rank or with no process group, where nn.SyncBatchNorm itself is a
+    plain batch norm.  Any other module type goes through the module itself (stock torch kernels on the same device),
+    so its semantics are kept instead of being silently replaced."""
+    if type(bn) is torch.nn.SyncBatchNorm:
+        if bn.training and _sync_world(bn) > 1:
+            return sync_bn_relu_fn(x, bn, gterm=gterm, group=group)
+    elif type(bn) is not torch.nn.BatchNorm1d:
+        if gterm is not None:
+            x = x + gterm.to(x.dtype).repeat_interleave(group, dim=0)
+        return torch.relu(bn(x))
+    return _bn_relu_local(x, bn, gterm, group)
 
 
 class GroupMaxFn(torch.autograd.Function):
