@@ -26,7 +26,7 @@
 // statistics; simamba_bn_relu_bwd_sums leaves the rank's (sum dy*mask, sum dy*mask*xhat), the caller all-reduces them,
 // simamba_bn_relu_bwd_dx is the backward's pass 2 with the global sums and the global row count (read from the device
 // buffer the merge wrote: no host read anywhere).
-#include "common.h"
+#include "host_common.h"
 
 namespace simamba {
 
@@ -64,6 +64,18 @@ __device__ __forceinline__ void store_c4(T* p, const float (&v)[4]) {
   *reinterpret_cast<Pack<T, 4>*>(p) = pk;
 }
 
+// this thread's 4 channels of row r: v += gterm[r / group]
+__device__ __forceinline__ void add_gterm(const float* gterm, int group, int C, long long r, int cl, float (&v)[4]) {
+  if (gterm) {
+    const float4 g = *reinterpret_cast<const float4*>(gterm + (r / group) * C + 4 * cl);
+    v[0] += g.x; v[1] += g.y; v[2] += g.z; v[3] += g.w;
+  }
+}
+
+// the rows [r0, r1) of this workgroup
+__device__ __forceinline__ long long chunk_begin() { return static_cast<long long>(blockIdx.x) * kBnChunk; }
+__device__ __forceinline__ long long chunk_end(long long r0, long long rows) { return min(r0 + kBnChunk, rows); }
+
 // combine the RL row lanes of a workgroup: s0 / s1 hold this thread's two 4-channel sums
 __device__ __forceinline__ void reduce_row_lanes(float (&s0)[4], float (&s1)[4], float* sm, int tpr, int rl,
                                                  int cl, int rlane, float* out, int C) {
@@ -95,16 +107,12 @@ __global__ __launch_bounds__(kBnMaxThreads) void bn_stats_kernel(BnArgs p) {
     for (int i = 0; i < 4; ++i) K[i] += p.gterm[4 * cl + i];
   }
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-  const long long r0 = static_cast<long long>(blockIdx.x) * kBnChunk;
-  const long long r1 = min(r0 + kBnChunk, p.rows);
+  const long long r0 = chunk_begin(), r1 = chunk_end(r0, p.rows);
 #pragma unroll 4
   for (long long r = r0 + rlane; r < r1; r += rl) {
     float v[4];
     load_c4<T>(x + r * p.ld + 4 * cl, v);
-    if (p.gterm) {
-      const float4 g = *reinterpret_cast<const float4*>(p.gterm + (r / p.group) * C + 4 * cl);
-      v[0] += g.x; v[1] += g.y; v[2] += g.z; v[3] += g.w;
-    }
+    add_gterm(p.gterm, p.group, C, r, cl, v);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float d = v[i] - K[i];
@@ -238,16 +246,12 @@ __global__ __launch_bounds__(kBnMaxThreads) void bn_relu_apply_kernel(BnArgs p) 
     scale[i] = p.invstd[c] * (p.weight ? p.weight[c] : 1.f);
     shift[i] = (p.bias ? p.bias[c] : 0.f) - p.mean[c] * scale[i];
   }
-  const long long r0 = static_cast<long long>(blockIdx.x) * kBnChunk;
-  const long long r1 = min(r0 + kBnChunk, p.rows);
+  const long long r0 = chunk_begin(), r1 = chunk_end(r0, p.rows);
 #pragma unroll 4
   for (long long r = r0 + rlane; r < r1; r += rl) {
     float v[4];
     load_c4<T>(x + r * p.ld + 4 * cl, v);
-    if (p.gterm) {
-      const float4 g = *reinterpret_cast<const float4*>(p.gterm + (r / p.group) * C + 4 * cl);
-      v[0] += g.x; v[1] += g.y; v[2] += g.z; v[3] += g.w;
-    }
+    add_gterm(p.gterm, p.group, C, r, cl, v);
     float o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = fmaxf(fmaf(v[i], scale[i], shift[i]), 0.f);
@@ -272,17 +276,13 @@ __global__ __launch_bounds__(kBnMaxThreads) void bn_relu_bwd_reduce_kernel(BnArg
     shift[i] = (p.bias ? p.bias[c] : 0.f) - mu[i] * scale[i];
   }
   float sb[4] = {0.f, 0.f, 0.f, 0.f}, sw[4] = {0.f, 0.f, 0.f, 0.f};
-  const long long r0 = static_cast<long long>(blockIdx.x) * kBnChunk;
-  const long long r1 = min(r0 + kBnChunk, p.rows);
+  const long long r0 = chunk_begin(), r1 = chunk_end(r0, p.rows);
 #pragma unroll 4
   for (long long r = r0 + rlane; r < r1; r += rl) {
     float v[4], d[4];
     load_c4<T>(x + r * p.ld + 4 * cl, v);
     load_c4<T>(dy + r * p.ld + 4 * cl, d);
-    if (p.gterm) {
-      const float4 g = *reinterpret_cast<const float4*>(p.gterm + (r / p.group) * C + 4 * cl);
-      v[0] += g.x; v[1] += g.y; v[2] += g.z; v[3] += g.w;
-    }
+    add_gterm(p.gterm, p.group, C, r, cl, v);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float dr = fmaf(v[i], scale[i], shift[i]) > 0.f ? d[i] : 0.f;
@@ -325,8 +325,7 @@ __global__ __launch_bounds__(kBnMaxThreads) void bn_relu_bwd_dx_kernel(BnArgs p,
     kb[i] = p.training ? dbias[c] * inv_n : 0.f;
     kw[i] = p.training ? dweight[c] * inv_n : 0.f;
   }
-  const long long r0 = static_cast<long long>(blockIdx.x) * kBnChunk;
-  const long long r1 = min(r0 + kBnChunk, p.rows);
+  const long long r0 = chunk_begin(), r1 = chunk_end(r0, p.rows);
   const int group = p.dgterm ? p.dgroup : kBnChunk;
   for (long long gbase = r0; gbase < r1; gbase += group) {
     float gs[4] = {0.f, 0.f, 0.f, 0.f};
@@ -336,10 +335,7 @@ __global__ __launch_bounds__(kBnMaxThreads) void bn_relu_bwd_dx_kernel(BnArgs p,
       float v[4], d[4], o[4];
       load_c4<T>(x + r * p.ld + 4 * cl, v);
       load_c4<T>(dy + r * p.ld + 4 * cl, d);
-      if (p.gterm) {
-        const float4 g = *reinterpret_cast<const float4*>(p.gterm + (r / p.group) * C + 4 * cl);
-        v[0] += g.x; v[1] += g.y; v[2] += g.z; v[3] += g.w;
-      }
+      add_gterm(p.gterm, p.group, C, r, cl, v);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float dr = fmaf(v[i], scale[i], shift[i]) > 0.f ? d[i] : 0.f;
@@ -419,12 +415,111 @@ static bool bn_shape_ok(long long rows, int C, long long ld, int group, bool has
   if (has_g && (group <= 0 || (rows % group) != 0)) return false;
   return true;
 }
+
+// ---- argument checks ------------------------------------------------------------------------------------------------
+constexpr int kNothingToDo = 1;       // an empty problem: the entry point answers SIMAMBA_OK without a launch
+static int entry_result(int rc) { return rc == kNothingToDo ? SIMAMBA_OK : rc; }
+
+// What every entry point that walks (rows, C) activations does first, in the order they report: dtype, empty, the
+// "0 = contiguous" row stride, shape.  Each entry point's own null pointers come after it.
+static int bn_check(int io_dtype, long long rows, int C, long long& ld, int group, const float* gterm) {
+  if (const int rc = check_io_dtype(io_dtype)) return rc;
+  if (rows == 0) return kNothingToDo;
+  if (ld == 0) ld = C;
+  return bn_shape_ok(rows, C, ld, group, gterm != nullptr) ? SIMAMBA_OK : SIMAMBA_E_SHAPE;
+}
+
+// The backward's pointers and its per-group sums of dx: dgroup > 0 divides kBnChunk and the rows (shape, before any
+// pointer), `required` = the entry point's own pointers are all there, and dgterm needs the gterm it is the gradient of.
+static int bn_check_dgterm(const float* dgterm, int dgroup, long long rows, const float* gterm, bool required) {
+  if (dgterm && (dgroup <= 0 || (kBnChunk % dgroup) != 0 || (rows % dgroup) != 0)) return SIMAMBA_E_SHAPE;
+  if (!required || (dgterm && !gterm)) return SIMAMBA_E_NULLPTR;
+  return SIMAMBA_OK;
+}
+
+// ---- the passes: grid, block, LDS bytes and the I/O type of each, in one place ----------------------------------------
+// the fields every route sets; the routes add their outputs (and the fused ones their `training`, the backward `dgroup`)
+static BnArgs bn_args(const void* x, const float* gterm, int group, const float* weight, const float* bias,
+                      const float* mean, const float* invstd, long long rows, int C, long long ld) {
+  BnArgs a{};
+  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
+  a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group; a.training = 1;
+  return a;
+}
+static dim3 bn_grid(const BnArgs& a) { return dim3(simamba_bn_relu_grid(a.rows)); }
 static dim3 bn_block(int C) {
   const int tpr = C / 4;
   const int rl = kBnMaxThreads / tpr > 0 ? kBnMaxThreads / tpr : 1;
   return dim3(tpr * rl);
 }
-static int bn_row_lanes(int C) { return static_cast<int>(bn_block(C).x) / (C / 4); }
+// `planes` planes of (row lanes, C) floats
+static size_t bn_lds(int C, int planes) { return sizeof(float) * planes * C * (bn_block(C).x / (C / 4)); }
+static dim3 fin_grid(int C) { return dim3((C + kFinCh - 1) / kFinCh); }
+static dim3 fin_block() { return dim3(kFinCh * kFinPl); }
+
+// where the batch statistics go: the fused finalize (mean, invstd, running statistics) or, with `stats`, this rank's
+// (count, mean, M2) block
+struct BnStatsOut {
+  float eps, momentum;
+  float *mean, *invstd, *running_mean, *running_var;
+  double* stats;
+  long long stats_ld;
+};
+
+static void launch_stats(const BnArgs& a, int io_dtype, hipStream_t s, const BnStatsOut& o) {
+  const dim3 grid = bn_grid(a);
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(bn_stats_kernel<T>, grid, bn_block(a.C), bn_lds(a.C, 2), s, a);
+    if (o.stats)
+      hipLaunchKernelGGL(bn_stats_local_finalize_kernel<T>, fin_grid(a.C), fin_block(), 0, s, a.x, a.gterm, a.partial,
+                         static_cast<int>(grid.x), a.rows, a.C, o.stats, o.stats_ld);
+    else
+      hipLaunchKernelGGL(bn_stats_finalize_kernel<T>, fin_grid(a.C), fin_block(), 0, s, a.x, a.gterm, a.partial,
+                         static_cast<int>(grid.x), a.rows, a.C, o.eps, o.momentum, o.mean, o.invstd, o.running_mean,
+                         o.running_var);
+  });
+}
+
+static void launch_eval_stats(const BnArgs& a, hipStream_t s, const float* running_mean, const float* running_var,
+                              float eps, float* mean, float* invstd) {
+  hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((a.C + 127) / 128), dim3(128), 0, s, running_mean, running_var, eps,
+                     a.C, mean, invstd);
+}
+
+static void launch_apply(const BnArgs& a, int io_dtype, hipStream_t s) {
+  with_io_type(io_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(bn_relu_apply_kernel<decltype(tag)>, bn_grid(a), bn_block(a.C), 0, s, a);
+  });
+}
+
+static void launch_bwd_sums(const BnArgs& a, int io_dtype, hipStream_t s, float* dweight, float* dbias) {
+  const dim3 grid = bn_grid(a);
+  with_io_type(io_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<decltype(tag)>, grid, bn_block(a.C), bn_lds(a.C, 2), s, a);
+  });
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, fin_grid(a.C), fin_block(), 0, s, a.partial, static_cast<int>(grid.x), a.C,
+                     dweight, dbias);
+}
+
+static void launch_bwd_dx(const BnArgs& a, int io_dtype, hipStream_t s, const float* dweight, const float* dbias) {
+  with_io_type(io_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<decltype(tag)>, bn_grid(a), bn_block(a.C), bn_lds(a.C, 1), s, a, dweight,
+                       dbias);
+  });
+}
+
+// dtype, no groups, shape, pointers, and a grid that fits 32 bits
+static int group_max_check(int io_dtype, long long groups, int n, int C, bool pointers, dim3& grid) {
+  if (const int rc = check_io_dtype(io_dtype)) return rc;
+  if (groups == 0) return kNothingToDo;
+  if (groups < 0 || n < 1 || n > 256 || C < 4 || (C % 4) != 0) return SIMAMBA_E_SHAPE;
+  if (!pointers) return SIMAMBA_E_NULLPTR;
+  const long long total = groups * (C / 4);
+  if (total > 0x7fffffffll * 256) return SIMAMBA_E_SHAPE;
+  grid = dim3(static_cast<unsigned>((total + 255) / 256));
+  return SIMAMBA_OK;
+}
 
 }  // namespace simamba
 
@@ -438,38 +533,16 @@ extern "C" int simamba_bn_relu_fwd(const void* x, const float* gterm, int group,
                                    const float* bias, float* running_mean, float* running_var, float momentum,
                                    float eps, int training, void* y, float* mean, float* invstd, float* partial,
                                    long long rows, int C, long long ld, int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (rows == 0) return SIMAMBA_OK;
-  if (ld == 0) ld = C;
-  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
+  if (const int rc = bn_check(io_dtype, rows, C, ld, group, gterm)) return entry_result(rc);
   if (!x || !y || !mean || !invstd) return SIMAMBA_E_NULLPTR;
   if (training && !partial) return SIMAMBA_E_NULLPTR;
   if (!training && (!running_mean || !running_var)) return SIMAMBA_E_NULLPTR;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  BnArgs a{};
-  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
-  a.y = y; a.partial = partial; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group;
-  a.training = training;
-  const int grid = simamba_bn_relu_grid(rows);
-  const dim3 block = bn_block(C);
-  const size_t smem = sizeof(float) * 2 * C * bn_row_lanes(C);
-  const bool f32 = io_dtype == SIMAMBA_F32;
-  if (training) {
-    if (f32) {
-      hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(grid), block, smem, s, a);
-      hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * kFinPl), 0, s, x, gterm, partial,
-                         grid, rows, C, eps, momentum, mean, invstd, running_mean, running_var);
-    } else {
-      hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, dim3(grid), block, smem, s, a);
-      hipLaunchKernelGGL(bn_stats_finalize_kernel<bf16_t>, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * kFinPl), 0, s, x, gterm, partial,
-                         grid, rows, C, eps, momentum, mean, invstd, running_mean, running_var);
-    }
-  } else {
-    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 127) / 128), dim3(128), 0, s, running_mean, running_var, eps, C,
-                       mean, invstd);
-  }
-  if (f32) hipLaunchKernelGGL(bn_relu_apply_kernel<float>, dim3(grid), block, 0, s, a);
-  else hipLaunchKernelGGL(bn_relu_apply_kernel<bf16_t>, dim3(grid), block, 0, s, a);
+  BnArgs a = bn_args(x, gterm, group, weight, bias, mean, invstd, rows, C, ld);
+  a.y = y; a.partial = partial; a.training = training;
+  if (training) launch_stats(a, io_dtype, s, {eps, momentum, mean, invstd, running_mean, running_var, nullptr, 0});
+  else launch_eval_stats(a, s, running_mean, running_var, eps, mean, invstd);
+  launch_apply(a, io_dtype, s);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -477,58 +550,30 @@ extern "C" int simamba_bn_relu_bwd(const void* dy, const void* x, const float* g
                                    const float* weight, const float* bias, const float* mean, const float* invstd,
                                    void* dx, float* dgterm, int dgroup, float* dweight, float* dbias, float* partial,
                                    long long rows, int C, long long ld, int io_dtype, int training, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (rows == 0) return SIMAMBA_OK;
-  if (ld == 0) ld = C;
-  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
-  if (dgterm && (dgroup <= 0 || (kBnChunk % dgroup) != 0 || (rows % dgroup) != 0)) return SIMAMBA_E_SHAPE;
-  if (!dy || !x || !mean || !invstd || !dx || !dweight || !dbias || !partial) return SIMAMBA_E_NULLPTR;
-  if (dgterm && !gterm) return SIMAMBA_E_NULLPTR;
+  if (const int rc = bn_check(io_dtype, rows, C, ld, group, gterm)) return entry_result(rc);
+  if (const int rc = bn_check_dgterm(dgterm, dgroup, rows, gterm,
+                                     dy && x && mean && invstd && dx && dweight && dbias && partial))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  BnArgs a{};
-  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
-  a.dy = dy; a.y = dx; a.dgterm = dgterm; a.partial = partial; a.rows = rows; a.ld = ld; a.C = C; a.group = group;
-  a.dgroup = dgroup; a.training = training;
-  const int grid = simamba_bn_relu_grid(rows);
-  const dim3 block = bn_block(C);
-  const int rl = bn_row_lanes(C);
-  const bool f32 = io_dtype == SIMAMBA_F32;
-  if (f32) hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<float>, dim3(grid), block, sizeof(float) * 2 * C * rl, s, a);
-  else hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<bf16_t>, dim3(grid), block, sizeof(float) * 2 * C * rl, s, a);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * kFinPl), 0, s, partial, grid, C,
-                     dweight, dbias);
-  if (f32) hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<float>, dim3(grid), block, sizeof(float) * C * rl, s, a, dweight, dbias);
-  else hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<bf16_t>, dim3(grid), block, sizeof(float) * C * rl, s, a, dweight, dbias);
+  BnArgs a = bn_args(x, gterm, group, weight, bias, mean, invstd, rows, C, ld);
+  a.dy = dy; a.y = dx; a.dgterm = dgterm; a.partial = partial; a.dgroup = dgroup; a.training = training;
+  launch_bwd_sums(a, io_dtype, s, dweight, dbias);
+  launch_bwd_dx(a, io_dtype, s, dweight, dbias);
   return static_cast<int>(hipGetLastError());
 }
 
-// ---- staged entry points (cross-rank statistics) ------------------------------------------------------------------
+// ---- staged entry points (cross-rank statistics): one pass each ------------------------------------------------------
 extern "C" int simamba_bn_stats_local(const void* x, const float* gterm, int group, double* stats, long long stats_ld,
                                       float* partial, long long rows, int C, long long ld, int io_dtype,
                                       void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (rows == 0) return SIMAMBA_OK;
-  if (ld == 0) ld = C;
+  if (const int rc = bn_check(io_dtype, rows, C, ld, group, gterm)) return entry_result(rc);
   if (stats_ld == 0) stats_ld = C;
-  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr) || stats_ld < C) return SIMAMBA_E_SHAPE;
+  if (stats_ld < C) return SIMAMBA_E_SHAPE;
   if (!x || !stats || !partial) return SIMAMBA_E_NULLPTR;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  BnArgs a{};
-  a.x = x; a.gterm = gterm; a.partial = partial; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group;
-  a.training = 1;
-  const int grid = simamba_bn_relu_grid(rows);
-  const dim3 block = bn_block(C);
-  const size_t smem = sizeof(float) * 2 * C * bn_row_lanes(C);
-  const dim3 fgrid((C + kFinCh - 1) / kFinCh), fblock(kFinCh * kFinPl);
-  if (io_dtype == SIMAMBA_F32) {
-    hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(grid), block, smem, s, a);
-    hipLaunchKernelGGL(bn_stats_local_finalize_kernel<float>, fgrid, fblock, 0, s, x, gterm, partial, grid, rows, C,
-                       stats, stats_ld);
-  } else {
-    hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, dim3(grid), block, smem, s, a);
-    hipLaunchKernelGGL(bn_stats_local_finalize_kernel<bf16_t>, fgrid, fblock, 0, s, x, gterm, partial, grid, rows, C,
-                       stats, stats_ld);
-  }
+  BnArgs a = bn_args(x, gterm, group, nullptr, nullptr, nullptr, nullptr, rows, C, ld);
+  a.partial = partial;
+  launch_stats(a, io_dtype, static_cast<hipStream_t>(stream),
+               {0.f, 0.f, nullptr, nullptr, nullptr, nullptr, stats, stats_ld});
   return static_cast<int>(hipGetLastError());
 }
 
@@ -547,18 +592,11 @@ extern "C" int simamba_bn_stats_merge(const double* stats, int world, float* run
 extern "C" int simamba_bn_relu_apply(const void* x, const float* gterm, int group, const float* weight,
                                      const float* bias, const float* mean, const float* invstd, void* y,
                                      long long rows, int C, long long ld, int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (rows == 0) return SIMAMBA_OK;
-  if (ld == 0) ld = C;
-  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
+  if (const int rc = bn_check(io_dtype, rows, C, ld, group, gterm)) return entry_result(rc);
   if (!x || !y || !mean || !invstd) return SIMAMBA_E_NULLPTR;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  BnArgs a{};
-  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
-  a.y = y; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group; a.training = 1;
-  const int grid = simamba_bn_relu_grid(rows);
-  if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL(bn_relu_apply_kernel<float>, dim3(grid), bn_block(C), 0, s, a);
-  else hipLaunchKernelGGL(bn_relu_apply_kernel<bf16_t>, dim3(grid), bn_block(C), 0, s, a);
+  BnArgs a = bn_args(x, gterm, group, weight, bias, mean, invstd, rows, C, ld);
+  a.y = y;
+  launch_apply(a, io_dtype, static_cast<hipStream_t>(stream));
   return static_cast<int>(hipGetLastError());
 }
 
@@ -566,22 +604,11 @@ extern "C" int simamba_bn_relu_bwd_sums(const void* dy, const void* x, const flo
                                         const float* weight, const float* bias, const float* mean,
                                         const float* invstd, float* dweight, float* dbias, float* partial,
                                         long long rows, int C, long long ld, int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (rows == 0) return SIMAMBA_OK;
-  if (ld == 0) ld = C;
-  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
+  if (const int rc = bn_check(io_dtype, rows, C, ld, group, gterm)) return entry_result(rc);
   if (!dy || !x || !mean || !invstd || !dweight || !dbias || !partial) return SIMAMBA_E_NULLPTR;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  BnArgs a{};
-  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
-  a.dy = dy; a.partial = partial; a.rows = rows; a.ld = ld; a.C = C; a.group = group; a.dgroup = group; a.training = 1;
-  const int grid = simamba_bn_relu_grid(rows);
-  const dim3 block = bn_block(C);
-  const size_t smem = sizeof(float) * 2 * C * bn_row_lanes(C);
-  if (io_dtype == SIMAMBA_F32) hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<float>, dim3(grid), block, smem, s, a);
-  else hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel<bf16_t>, dim3(grid), block, smem, s, a);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * kFinPl), 0, s, partial, grid, C,
-                     dweight, dbias);
+  BnArgs a = bn_args(x, gterm, group, weight, bias, mean, invstd, rows, C, ld);
+  a.dy = dy; a.partial = partial;
+  launch_bwd_sums(a, io_dtype, static_cast<hipStream_t>(stream), dweight, dbias);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -590,61 +617,36 @@ extern "C" int simamba_bn_relu_bwd_dx(const void* dy, const void* x, const float
                                       const float* sum_dweight, const float* sum_dbias, const double* count, void* dx,
                                       float* dgterm, int dgroup, long long rows, int C, long long ld, int io_dtype,
                                       void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (rows == 0) return SIMAMBA_OK;
-  if (ld == 0) ld = C;
-  if (!bn_shape_ok(rows, C, ld, group, gterm != nullptr)) return SIMAMBA_E_SHAPE;
-  if (dgterm && (dgroup <= 0 || (kBnChunk % dgroup) != 0 || (rows % dgroup) != 0)) return SIMAMBA_E_SHAPE;
-  if (!dy || !x || !mean || !invstd || !dx || !sum_dweight || !sum_dbias || !count) return SIMAMBA_E_NULLPTR;
-  if (dgterm && !gterm) return SIMAMBA_E_NULLPTR;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  BnArgs a{};
-  a.x = x; a.gterm = gterm; a.weight = weight; a.bias = bias; a.mean = mean; a.invstd = invstd;
-  a.dy = dy; a.y = dx; a.dgterm = dgterm; a.count = count; a.rows = rows; a.ld = ld; a.C = C; a.group = group;
-  a.dgroup = dgroup; a.training = 1;
-  const int grid = simamba_bn_relu_grid(rows);
-  const dim3 block = bn_block(C);
-  const size_t smem = sizeof(float) * C * bn_row_lanes(C);
-  if (io_dtype == SIMAMBA_F32)
-    hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<float>, dim3(grid), block, smem, s, a, sum_dweight, sum_dbias);
-  else
-    hipLaunchKernelGGL(bn_relu_bwd_dx_kernel<bf16_t>, dim3(grid), block, smem, s, a, sum_dweight, sum_dbias);
+  if (const int rc = bn_check(io_dtype, rows, C, ld, group, gterm)) return entry_result(rc);
+  if (const int rc = bn_check_dgterm(dgterm, dgroup, rows, gterm,
+                                     dy && x && mean && invstd && dx && sum_dweight && sum_dbias && count))
+    return rc;
+  BnArgs a = bn_args(x, gterm, group, weight, bias, mean, invstd, rows, C, ld);
+  a.dy = dy; a.y = dx; a.dgterm = dgterm; a.count = count; a.dgroup = dgroup;
+  launch_bwd_dx(a, io_dtype, static_cast<hipStream_t>(stream), sum_dweight, sum_dbias);
   return static_cast<int>(hipGetLastError());
 }
 
 extern "C" int simamba_group_max_fwd(const void* x, void* out, unsigned char* idx, long long groups, int n, int C,
                                      int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (groups == 0) return SIMAMBA_OK;
-  if (groups < 0 || n < 1 || n > 256 || C < 4 || (C % 4) != 0) return SIMAMBA_E_SHAPE;
-  if (!x || !out || !idx) return SIMAMBA_E_NULLPTR;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long total = groups * (C / 4);
-  const dim3 grid(static_cast<unsigned>((total + 255) / 256));
-  if (io_dtype == SIMAMBA_F32)
-    hipLaunchKernelGGL(group_max_fwd_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x),
-                       static_cast<float*>(out), idx, groups, n, C);
-  else
-    hipLaunchKernelGGL(group_max_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(x),
-                       static_cast<bf16_t*>(out), idx, groups, n, C);
+  dim3 grid;
+  if (const int rc = group_max_check(io_dtype, groups, n, C, x && out && idx, grid)) return entry_result(rc);
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(group_max_fwd_kernel<T>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const T*>(x), static_cast<T*>(out), idx, groups, n, C);
+  });
   return static_cast<int>(hipGetLastError());
 }
 
 extern "C" int simamba_group_max_bwd(const void* dout, const unsigned char* idx, void* dx, long long groups, int n,
                                      int C, int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  if (groups == 0) return SIMAMBA_OK;
-  if (groups < 0 || n < 1 || n > 256 || C < 4 || (C % 4) != 0) return SIMAMBA_E_SHAPE;
-  if (!dout || !idx || !dx) return SIMAMBA_E_NULLPTR;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long total = groups * (C / 4);
-  if (total > 0x7fffffffll * 256) return SIMAMBA_E_SHAPE;
-  const dim3 grid(static_cast<unsigned>((total + 255) / 256));
-  if (io_dtype == SIMAMBA_F32)
-    hipLaunchKernelGGL(group_max_bwd_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(dout), idx,
-                       static_cast<float*>(dx), groups, n, C);
-  else
-    hipLaunchKernelGGL(group_max_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(dout), idx,
-                       static_cast<bf16_t*>(dx), groups, n, C);
+  dim3 grid;
+  if (const int rc = group_max_check(io_dtype, groups, n, C, dout && idx && dx, grid)) return entry_result(rc);
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(group_max_bwd_kernel<T>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const T*>(dout), idx, static_cast<T*>(dx), groups, n, C);
+  });
   return static_cast<int>(hipGetLastError());
 }

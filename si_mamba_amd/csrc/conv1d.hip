@@ -11,7 +11,7 @@
 // thread per (channel, tap) adds a channel's slots in index order, and the workgroup STORES that partial to the
 // workspace, [batch slice][dim][width] (dw) and [batch slice][dim] (dbias); det_reduce.hip sums over the slices.
 // Algorithmic HBM bytes: fwd 2*B*D*L*s, bwd 3*B*D*L*s (+ (W+1)*D*4 parameters).
-#include "common.h"
+#include "host_common.h"
 #include "det_reduce.h"
 
 namespace simamba {
@@ -346,8 +346,7 @@ static int fill_common(ConvArgs& a, int io_dtype, int pack = kPack) {
   int bchunk = a.batch;
   while (bchunk > 1 && static_cast<long long>(dblocks) * ((a.batch + bchunk - 1) / bchunk) < 2048) bchunk = (bchunk + 1) / 2;
   a.bchunk = bchunk;
-  const size_t esz = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  a.vec = (a.seqlen * esz) % 16 == 0;
+  a.vec = (a.seqlen * io_esz(io_dtype)) % 16 == 0;
   return dblocks;
 }
 
@@ -355,14 +354,11 @@ static int fill_common(ConvArgs& a, int io_dtype, int pack = kPack) {
 
 using namespace simamba;
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 static int check_conv(const void* x, const float* w, int batch, int dim, int seqlen, int width, int io_dtype) {
   if (!x || !w) return SIMAMBA_E_NULLPTR;
   if (batch < 0 || dim <= 0 || seqlen < 0) return SIMAMBA_E_SHAPE;
   if (width < 2 || width > 4) return SIMAMBA_E_WIDTH;
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
-  return SIMAMBA_OK;
+  return check_io_dtype(io_dtype);
 }
 
 extern "C" int simamba_causal_conv1d_fwd(const void* x, const float* w, const float* bias, void* out,
@@ -378,13 +374,12 @@ extern "C" int simamba_causal_conv1d_fwd(const void* x, const float* w, const fl
   const int dblocks = fill_common(a, io_dtype);
   a.x_bs = x_bstride ? x_bstride : static_cast<long long>(dim) * seqlen;
   a.o_bs = static_cast<long long>(dim) * seqlen;
-  a.vec = a.vec && al16(x) && al16(out) && (a.x_bs * (io_dtype == SIMAMBA_F32 ? 4 : 2)) % 16 == 0;
+  a.vec = a.vec && aligned16(x) && aligned16(out) && (a.x_bs * io_esz(io_dtype)) % 16 == 0;
   dim3 grid(dblocks, (batch + a.bchunk - 1) / a.bchunk);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (io_dtype == SIMAMBA_F32)
-    hipLaunchKernelGGL(conv1d_fwd_kernel<float>, grid, dim3(kConvThreads), 0, s, a);
-  else
-    hipLaunchKernelGGL(conv1d_fwd_kernel<bf16_t>, grid, dim3(kConvThreads), 0, s, a);
+  with_io_type(io_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(conv1d_fwd_kernel<decltype(tag)>, grid, dim3(kConvThreads), 0, s, a);
+  });
   return static_cast<int>(hipGetLastError());
 }
 
@@ -393,7 +388,7 @@ extern "C" int simamba_causal_conv1d_fwd(const void* x, const float* w, const fl
 static long long conv_det_slices(int batch, int dim, int seqlen, int io_dtype) {
   ConvArgs a{};
   a.batch = batch; a.dim = dim; a.seqlen = seqlen;
-  fill_common(a, io_dtype, io_dtype == SIMAMBA_F32 ? 4 : 8);
+  fill_common(a, io_dtype, io_pack(io_dtype));
   return (batch + a.bchunk - 1) / a.bchunk;
 }
 static long long conv_det_dw_floats(long long slices, int dim, int width) {
@@ -424,7 +419,7 @@ extern "C" int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const
   if (det && simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags) > 0 &&
       (!workspace || workspace_floats < simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags)))
     return SIMAMBA_E_WORKSPACE;
-  if (det && !al16(workspace)) return SIMAMBA_E_ALIGN;
+  if (det && !aligned16(workspace)) return SIMAMBA_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the two accumulators are zeroed here; a caller that carves dbias directly behind dw gets one memset node
   // (the deterministic form writes them whole in its sum pass: nothing to clear but for an empty problem)
@@ -441,23 +436,23 @@ extern "C" int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const
   ConvArgs a{};
   a.x = x; a.w = w; a.bias = bias; a.out = dx; a.dout = dout; a.dw = dw; a.dbias = dbias;
   a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.width = width; a.silu = silu;
-  const int dblocks = fill_common(a, io_dtype, io_dtype == SIMAMBA_F32 ? 4 : 8);
+  const int dblocks = fill_common(a, io_dtype, io_pack(io_dtype));
   a.x_bs = x_bstride ? x_bstride : static_cast<long long>(dim) * seqlen;
   a.o_bs = dx_bstride ? dx_bstride : static_cast<long long>(dim) * seqlen;
-  const long long esz_ = io_dtype == SIMAMBA_F32 ? 4 : 2;
-  a.vec = a.vec && al16(x) && al16(dx) && al16(dout) && (a.x_bs * esz_) % 16 == 0 && (a.o_bs * esz_) % 16 == 0;
+  const long long esz = io_esz(io_dtype);
+  a.vec = a.vec && aligned16(x) && aligned16(dx) && aligned16(dout) && (a.x_bs * esz) % 16 == 0 &&
+          (a.o_bs * esz) % 16 == 0;
   dim3 grid(dblocks, (batch + a.bchunk - 1) / a.bchunk);
-  const bool fast = a.vec && seqlen % (io_dtype == SIMAMBA_F32 ? 4 : 8) == 0;
+  const bool fast = a.vec && seqlen % io_pack(io_dtype) == 0;
   if (det) {                                                 // partials in place of the accumulators
     a.dw = workspace;
     a.dbias = dbias ? workspace + conv_det_dw_floats(grid.y, dim, width) : nullptr;
-    if (io_dtype == SIMAMBA_F32) {
-      if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<float, 4, true>), grid, dim3(kConvThreads), 0, s, a);
-      else hipLaunchKernelGGL((conv1d_bwd_kernel<float, 4, true>), grid, dim3(kConvThreads), 0, s, a);
-    } else {
-      if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<bf16_t, 8, true>), grid, dim3(kConvThreads), 0, s, a);
-      else hipLaunchKernelGGL((conv1d_bwd_kernel<bf16_t, 8, true>), grid, dim3(kConvThreads), 0, s, a);
-    }
+    with_io_type(io_dtype, [&](auto tag) {
+      using T = decltype(tag);
+      constexpr int kP = 16 / sizeof(T);
+      if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<T, kP, true>), grid, dim3(kConvThreads), 0, s, a);
+      else hipLaunchKernelGGL((conv1d_bwd_kernel<T, kP, true>), grid, dim3(kConvThreads), 0, s, a);
+    });
     const int e = static_cast<int>(hipGetLastError());
     if (e) return e;
     DetSumJob jobs[2] = {{a.dw, dw, static_cast<long long>(dim) * width, static_cast<long long>(dim) * width,
@@ -465,13 +460,12 @@ extern "C" int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const
                          {a.dbias, dbias, dim, dim, static_cast<int>(grid.y)}};
     return det_sum_launch(jobs, dbias ? 2 : 1, s);
   }
-  if (io_dtype == SIMAMBA_F32) {
-    if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<float, 4>), grid, dim3(kConvThreads), 0, s, a);
-    else hipLaunchKernelGGL((conv1d_bwd_kernel<float, 4>), grid, dim3(kConvThreads), 0, s, a);
-  } else {
-    if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<bf16_t, 8>), grid, dim3(kConvThreads), 0, s, a);
-    else hipLaunchKernelGGL((conv1d_bwd_kernel<bf16_t, 8>), grid, dim3(kConvThreads), 0, s, a);
-  }
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int kP = 16 / sizeof(T);
+    if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<T, kP>), grid, dim3(kConvThreads), 0, s, a);
+    else hipLaunchKernelGGL((conv1d_bwd_kernel<T, kP>), grid, dim3(kConvThreads), 0, s, a);
+  });
   return static_cast<int>(hipGetLastError());
 }
 

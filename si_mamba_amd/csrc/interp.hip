@@ -12,7 +12,7 @@
 //   * interp_bwd_kernel: dfeats[b, s, :] = sum over the points that name centre s of w dout[b, n, :], as a
 //     deterministic gather (see the kernel).
 // HBM-bound: per sample N x C output floats + 3 gathered rows per point (L2-resident: S x C floats).
-#include "common.h"
+#include "host_common.h"
 
 namespace simamba {
 
@@ -170,7 +170,7 @@ extern "C" int simamba_three_nn(const float* xyz1, const float* xyz2, int* idx, 
 
 extern "C" int simamba_three_interpolate_fwd(const void* feats, const int* idx, const float* weight, void* out,
                                              int batch, int N, int S, int C, int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (const int rc = check_io_dtype(io_dtype)) return rc;
   if (batch < 0 || N < 0 || S < 1 || C < 4 || (C % 4) != 0) return SIMAMBA_E_SHAPE;
   if (batch == 0 || N == 0) return SIMAMBA_OK;
   if (!feats || !idx || !weight || !out) return SIMAMBA_E_NULLPTR;
@@ -178,18 +178,17 @@ extern "C" int simamba_three_interpolate_fwd(const void* feats, const int* idx, 
   const long long points = static_cast<long long>(batch) * N;
   const long long total = points * (C / 4);
   const dim3 grid(static_cast<unsigned>((total + 255) / 256));
-  if (io_dtype == SIMAMBA_F32)
-    hipLaunchKernelGGL(interp_fwd_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(feats), idx, weight,
-                       static_cast<float*>(out), points, N, S, C);
-  else
-    hipLaunchKernelGGL(interp_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(feats), idx, weight,
-                       static_cast<bf16_t*>(out), points, N, S, C);
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(interp_fwd_kernel<T>, grid, dim3(256), 0, s, static_cast<const T*>(feats), idx, weight,
+                       static_cast<T*>(out), points, N, S, C);
+  });
   return static_cast<int>(hipGetLastError());
 }
 
 extern "C" int simamba_three_interpolate_bwd(const void* dout, const int* idx, const float* weight, float* dfeats,
                                              int batch, int N, int S, int C, int io_dtype, void* stream) {
-  if (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) return SIMAMBA_E_DTYPE;
+  if (const int rc = check_io_dtype(io_dtype)) return rc;
   if (batch < 0 || N < 0 || N > 8192 || S < 1 || S > 65535 || C < 4 || (C % 4) != 0 || batch > 65535)
     return SIMAMBA_E_SHAPE;
   if (batch == 0) return SIMAMBA_OK;
@@ -201,11 +200,10 @@ extern "C" int simamba_three_interpolate_bwd(const void* dout, const int* idx, c
   }
   if (!dout || !idx || !weight) return SIMAMBA_E_NULLPTR;
   const size_t smem = 8 * static_cast<size_t>(N);
-  if (io_dtype == SIMAMBA_F32)
-    hipLaunchKernelGGL(interp_bwd_kernel<float>, dim3(S, batch), dim3(256), smem, s, static_cast<const float*>(dout), idx,
-                       weight, dfeats, N, S, C);
-  else
-    hipLaunchKernelGGL(interp_bwd_kernel<bf16_t>, dim3(S, batch), dim3(256), smem, s, static_cast<const bf16_t*>(dout),
-                       idx, weight, dfeats, N, S, C);
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(interp_bwd_kernel<T>, dim3(S, batch), dim3(256), smem, s, static_cast<const T*>(dout), idx, weight,
+                       dfeats, N, S, C);
+  });
   return static_cast<int>(hipGetLastError());
 }

@@ -491,7 +491,7 @@ extern "C" int simamba_selective_scan_dt_bwd_ex(const void* u, const void* xdbl,
   int rc;
   if ((rc = scan_check_flags(flags))) return rc;
   if (dstate != kMaxState) return SIMAMBA_E_DSTATE;
-  if ((rc = scan_check_dtype(io_dtype)) || (rc = scan_check_dt_rank(dt_rank, io_dtype))) return rc;
+  if ((rc = check_io_dtype(io_dtype)) || (rc = scan_check_dt_rank(dt_rank, io_dtype))) return rc;
   if (batch > 0 && seqlen > 0 && (!xdbl || !wdt || !z)) return SIMAMBA_E_NULLPTR;
   const XdblOperands x = scan_xdbl_operands(xdbl, wdt, batch, seqlen, dt_rank, io_dtype, xdbl_bstride, xdbl_tstride);
   if (!x.ok) return SIMAMBA_E_VARIANT;

@@ -195,7 +195,7 @@ extern "C" int simamba_scan_fwd_auto_variant(int batch, int dim) {
 extern "C" int simamba_scan_ckpt_step(int batch, int dim, int seqlen, int dstate, int io_dtype) {
   if (batch <= 0 || dim <= 0 || seqlen <= 0) return SIMAMBA_SCAN_CKPT_ROW;
   const long long rows = static_cast<long long>(batch) * dim;
-  if (dstate == kMaxState && dim % 64 == 0 && seqlen % scan_pack(io_dtype) == 0 && rows * seqlen < (1ll << 30) &&
+  if (dstate == kMaxState && dim % 64 == 0 && seqlen % io_pack(io_dtype) == 0 && rows * seqlen < (1ll << 30) &&
       auto_variant(rows, batch, dim) != SIMAMBA_SCAN_ROWSCAN)
     return SIMAMBA_SCAN_CKPT_SEQ;
   return SIMAMBA_SCAN_CKPT_ROW;
@@ -230,7 +230,7 @@ extern "C" int simamba_scan_seq_applicable(int batch, int dim, int seqlen, int d
                                            size_t B_addr, size_t C_addr, long long z_bstride, long long dz_bstride,
                                            long long bc_bstride, long long bc_nstride, long long bc_tstride) {
   if (batch <= 0 || seqlen <= 0 || scan_check_shape(batch, dim, seqlen) || scan_check_dstate(dstate) ||
-      scan_check_dtype(io_dtype))
+      check_io_dtype(io_dtype))
     return 0;
   const ScanOperands o = scan_operands(dim, seqlen, dstate, io_dtype, act_addr_or, has_z != 0, z_bstride, dz_bstride,
                                        bc_bstride, bc_nstride, bc_tstride);
@@ -307,7 +307,7 @@ extern "C" int simamba_selective_scan_dt_fwd(const void* u, const void* xdbl, co
   int rc;
   if ((rc = scan_check_shape(batch, dim, seqlen))) return rc;
   if (dstate != kMaxState) return SIMAMBA_E_DSTATE;
-  if ((rc = scan_check_dtype(io_dtype)) || (rc = scan_check_ckpt(ckpt_step))) return rc;
+  if ((rc = check_io_dtype(io_dtype)) || (rc = scan_check_ckpt(ckpt_step))) return rc;
   if (variant != SIMAMBA_SCAN_AUTO && variant != SIMAMBA_SCAN_LPC2 && variant != SIMAMBA_SCAN_LPC4 &&
       variant != SIMAMBA_SCAN_MIX)
     return SIMAMBA_E_VARIANT;                               // the row-scan kernel reads a delta tensor

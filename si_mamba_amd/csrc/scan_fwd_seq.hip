@@ -488,7 +488,7 @@ static void launch_seq_mix(const SeqArgs& a, hipStream_t s) {
 // 2 = packs along the state (n is: the mixer's x_proj output), 0 = neither keeps a pack aligned -- such operands go
 // to the row-scan kernel, which gathers element by element.
 int scan_fwd_seq_bc_mode(const void* B, const void* C, int io_dtype, long long bc_bs, long long bc_ns, long long bc_ts) {
-  const uintptr_t pm = 4 * scan_esz(io_dtype) - 1;
+  const uintptr_t pm = 4 * io_esz(io_dtype) - 1;
   if (((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & pm) != 0 || bc_bs % 4 != 0) return 0;
   if (bc_ts == 1 && bc_ns % 4 == 0) return 1;
   if (bc_ns == 1 && bc_ts % 4 == 0) return 2;

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <initializer_list>
+#include "host_common.h"
 #include "scan_common.h"
 
 namespace simamba {
@@ -31,22 +32,16 @@ inline int scan_check_ckpt(int& ckpt_step) {                   // 0 = the row-sc
   return (ckpt_step != SIMAMBA_SCAN_CKPT_ROW && ckpt_step != SIMAMBA_SCAN_CKPT_SEQ) ? SIMAMBA_E_VARIANT : SIMAMBA_OK;
 }
 inline int scan_check_dstate(int dstate) { return (dstate < 1 || dstate > kMaxState) ? SIMAMBA_E_DSTATE : SIMAMBA_OK; }
-inline int scan_check_dtype(int io_dtype) {
-  return (io_dtype != SIMAMBA_F32 && io_dtype != SIMAMBA_BF16) ? SIMAMBA_E_DTYPE : SIMAMBA_OK;
-}
 inline int scan_check_flags(int flags) { return (flags & ~SIMAMBA_BWD_DETERMINISTIC) ? SIMAMBA_E_VARIANT : SIMAMBA_OK; }
 // the order of simamba_selective_scan_fwd and of the backward
 inline int scan_check_args(int batch, int dim, int seqlen, int dstate, int io_dtype, int& ckpt_step) {
   int rc;
   if ((rc = scan_check_shape(batch, dim, seqlen)) || (rc = scan_check_ckpt(ckpt_step)) ||
-      (rc = scan_check_dstate(dstate)) || (rc = scan_check_dtype(io_dtype)))
+      (rc = scan_check_dstate(dstate)) || (rc = check_io_dtype(io_dtype)))
     return rc;
   return SIMAMBA_OK;
 }
 
-inline size_t scan_esz(int io_dtype) { return io_dtype == SIMAMBA_F32 ? 4 : 2; }    // bytes per activation element
-inline int scan_pack(int io_dtype) { return io_dtype == SIMAMBA_F32 ? 4 : 8; }      // elements per 16 bytes
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline uintptr_t addr_or(std::initializer_list<const void*> ps) {
   uintptr_t o = 0;
   for (const void* p : ps) o |= reinterpret_cast<uintptr_t>(p);
@@ -73,7 +68,7 @@ struct XdblOperands { const void* B; const void* C; long long bs, ts; bool ok; }
 XdblOperands scan_xdbl_operands(const void* xdbl, const void* wdt, int batch, int seqlen, int dt_rank, int io_dtype,
                                 long long xdbl_bstride, long long xdbl_tstride);
 inline int scan_check_dt_rank(int dt_rank, int io_dtype) {
-  const int pack = scan_pack(io_dtype);
+  const int pack = io_pack(io_dtype);
   return (dt_rank < pack || dt_rank > 24 || dt_rank % pack) ? SIMAMBA_E_SHAPE : SIMAMBA_OK;
 }
 

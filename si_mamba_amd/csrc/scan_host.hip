@@ -8,7 +8,7 @@ ScanOperands scan_operands(int dim, int seqlen, int dstate, int io_dtype, uintpt
                            long long z_bstride, long long dz_bstride, long long bc_bstride, long long bc_nstride,
                            long long bc_tstride) {
   ScanOperands o{};
-  o.esz = scan_esz(io_dtype);
+  o.esz = io_esz(io_dtype);
   o.nchunks = simamba_scan_num_chunks(seqlen);
   o.z_bs = z_bstride ? z_bstride : static_cast<long long>(dim) * seqlen;
   o.dz_bs = dz_bstride ? dz_bstride : static_cast<long long>(dim) * seqlen;
@@ -23,7 +23,7 @@ ScanOperands scan_operands(int dim, int seqlen, int dstate, int io_dtype, uintpt
 
 XdblOperands scan_xdbl_operands(const void* xdbl, const void* wdt, int batch, int seqlen, int dt_rank, int io_dtype,
                                 long long xdbl_bstride, long long xdbl_tstride) {
-  const size_t esz = scan_esz(io_dtype);
+  const size_t esz = io_esz(io_dtype);
   const long long S = dt_rank + 2 * kMaxState;
   XdblOperands x{};
   x.bs = xdbl_bstride ? xdbl_bstride : S * seqlen;

@@ -87,76 +87,10 @@ def _off(t, elems):
     return None if t is None else t.data_ptr() + elems * t.element_size()
 
 
-class BnReluFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gterm, group, weight, bias, running_mean, running_var, momentum, eps, training):
-        _lib.require_gpu(x, "bn_relu_fn")
-        lib = _lib.load()
-        xc = x.contiguous()
-        rows, C = xc.shape
-        dev = xc.device
-        code = _lib.dtype_code(xc.dtype)
-        g = None if gterm is None else gterm.float().contiguous()
-        w = None if weight is None else weight.float().contiguous()
-        b = None if bias is None else bias.float().contiguous()
-        y = torch.empty_like(xc)
-        mean = torch.empty(C, device=dev, dtype=torch.float32)
-        invstd = torch.empty(C, device=dev, dtype=torch.float32)
-        grid = lib.simamba_bn_relu_grid(rows)
-        part = torch.empty(grid, 2, min(C, _BN_MAX_C), device=dev, dtype=torch.float32)
-        gs = []
-        with torch.cuda.device(dev), _lib.timed("bn_relu_fwd", dev):
-            for c0, c1 in _slices(C):
-                gsl = None if g is None else (g if (c0 == 0 and c1 == C) else g[:, c0:c1].contiguous())
-                gs.append(gsl)
-                rc = lib.simamba_bn_relu_fwd(_off(xc, c0), _lib.ptr(gsl), int(group), _off(w, c0), _off(b, c0),
-                                             _off(running_mean, c0), _off(running_var, c0), float(momentum),
-                                             float(eps), int(bool(training)), _off(y, c0), _off(mean, c0),
-                                             _off(invstd, c0), part.data_ptr(), rows, c1 - c0, C, code,
-                                             _lib.stream_ptr(dev))
-                _lib.check(rc, "simamba_bn_relu_fwd")
-        ctx.save_for_backward(xc, g, w, b, mean, invstd)
-        ctx.meta = (int(group), bool(training), code, x.dtype,
-                    None if gterm is None else gterm.dtype,
-                    None if weight is None else weight.dtype, None if bias is None else bias.dtype)
-        ctx.part = part
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        xc, g, w, b, mean, invstd = ctx.saved_tensors
-        group, training, code, xdtype, gdtype, wdtype, bdtype = ctx.meta
-        lib = _lib.load()
-        rows, C = xc.shape
-        dev = xc.device
-        dyc = dy.to(xc.dtype).contiguous()
-        dx = torch.empty_like(xc)
-        dw = torch.empty(C, device=dev, dtype=torch.float32)
-        db = torch.empty(C, device=dev, dtype=torch.float32)
-        dgroup = _bn_dgroup(g, group)
-        dgs = []
-        with torch.cuda.device(dev), _lib.timed("bn_relu_bwd", dev):
-            for c0, c1 in _slices(C):
-                gsl = None if g is None else (g if (c0 == 0 and c1 == C) else g[:, c0:c1].contiguous())
-                dg = None if g is None else torch.empty(rows // dgroup, c1 - c0, device=dev, dtype=torch.float32)
-                dgs.append(dg)
-                rc = lib.simamba_bn_relu_bwd(_off(dyc, c0), _off(xc, c0), _lib.ptr(gsl), group, _off(w, c0),
-                                             _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(dx, c0), _lib.ptr(dg),
-                                             dgroup, _off(dw, c0), _off(db, c0), ctx.part.data_ptr(), rows, c1 - c0, C,
-                                             code, int(training), _lib.stream_ptr(dev))
-                _lib.check(rc, "simamba_bn_relu_bwd")
-        dgt = None
-        if g is not None:
-            dgt = dgs[0] if len(dgs) == 1 else torch.cat(dgs, dim=1)
-            if dgroup != group:
-                dgt = dgt.view(rows // group, group // dgroup, C).sum(1)
-            dgt = dgt.to(gdtype)
-        return (dx.to(xdtype), dgt, None,
-                None if wdtype is None else dw.to(wdtype), None if bdtype is None else db.to(bdtype),
-                None, None, None, None, None)
+def _abi(name, *args):
+    _lib.check(getattr(_lib.load(), name)(*args), name)
 
 
-# ---- the kernels' stages over plain buffers (SyncBnReluFn; the tests drive them with row shards as ranks) --------------
 def _slice_of(g, c0, c1, C):
     return None if g is None else (g if (c0 == 0 and c1 == C) else g[:, c0:c1].contiguous())
 
@@ -165,48 +99,25 @@ def _bn_partial(lib, rows, C, dev):
     return torch.empty(lib.simamba_bn_relu_grid(rows), 2, min(C, _BN_MAX_C), device=dev, dtype=torch.float32)
 
 
-def bn_stats_local(xc, g, group, stats, part):
-    """This rank's (count, mean, M2) per channel of xc (rows, C) (+ g[row // group]) into ``stats`` (3, C) float64."""
-    lib = _lib.load()
-    rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
-    for c0, c1 in _slices(C):
-        rc = lib.simamba_bn_stats_local(_off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(stats, c0),
-                                        C, part.data_ptr(), rows, c1 - c0, C, code, st)
-        _lib.check(rc, "simamba_bn_stats_local")
+def _bn_operands(x, gterm, weight, bias):
+    """What both Functions hand to the kernels: x contiguous, the additive term and the parameters contiguous in fp32,
+    and the outputs y, mean, invstd."""
+    xc = x.contiguous()
+    g, w, b = (None if t is None else t.float().contiguous() for t in (gterm, weight, bias))
+    mean = torch.empty(xc.shape[1], device=xc.device, dtype=torch.float32)
+    return xc, g, w, b, torch.empty_like(xc), mean, torch.empty_like(mean)
 
 
-def bn_stats_merge(gathered, running_mean, running_var, momentum, eps, mean, invstd, count):
-    """(W, 3, C) float64 blocks of all ranks -> mean, invstd (C) float32, count (1) float64, running statistics."""
-    world, _, C = gathered.shape
-    rc = _lib.load().simamba_bn_stats_merge(gathered.data_ptr(), world, _lib.ptr(running_mean),
-                                            _lib.ptr(running_var), float(momentum), float(eps), mean.data_ptr(),
-                                            invstd.data_ptr(), count.data_ptr(), C, _lib.stream_ptr(gathered.device))
-    _lib.check(rc, "simamba_bn_stats_merge")
+def _dtypes(*tensors):
+    return tuple(None if t is None else t.dtype for t in tensors)
 
 
-def bn_relu_apply(xc, g, group, w, b, mean, invstd, y):
-    lib = _lib.load()
-    rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
-    for c0, c1 in _slices(C):
-        rc = lib.simamba_bn_relu_apply(_off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(w, c0),
-                                       _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(y, c0), rows, c1 - c0, C,
-                                       code, st)
-        _lib.check(rc, "simamba_bn_relu_apply")
-
-
-def bn_relu_bwd_sums(dyc, xc, g, group, w, b, mean, invstd, sums, part):
-    """This rank's sum dy*mask (``sums[0]``) and sum dy*mask*xhat (``sums[1]``); ``sums`` (2, C) float32."""
-    lib = _lib.load()
-    rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
-    for c0, c1 in _slices(C):
-        rc = lib.simamba_bn_relu_bwd_sums(_off(dyc, c0), _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group),
-                                          _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0),
-                                          _off(sums[1], c0), _off(sums[0], c0), part.data_ptr(), rows, c1 - c0, C,
-                                          code, st)
-        _lib.check(rc, "simamba_bn_relu_bwd_sums")
+def _bn_grads(dtypes, dx, dgt, dw, db):
+    """backward's tuple for (x, gterm, group, weight, bias, + 5 more), each gradient in the dtype its input had."""
+    xdtype, gdtype, wdtype, bdtype = dtypes
+    return (dx.to(xdtype), None if dgt is None else dgt.to(gdtype), None,
+            None if wdtype is None else dw.to(wdtype), None if bdtype is None else db.to(bdtype),
+            None, None, None, None, None)
 
 
 def _bn_dgroup(g, group):
@@ -217,28 +128,111 @@ def _bn_dgroup(g, group):
     return dgroup
 
 
-def bn_relu_bwd_dx(dyc, xc, g, group, w, b, mean, invstd, sums, count, dx):
-    """dx with the sums and the row count of ALL ranks; returns the gradient of g (rows / group, C) float32 or None."""
-    lib = _lib.load()
+def _bn_dx_slices(xc, g, group, call):
+    """call(c0, c1, g's slice, dg, dgroup) per channel slice, dg (rows / dgroup, c1 - c0) for the kernel's per-group
+    sums of dx; returns the gradient of g (rows / group, C) float32, or None without g."""
     rows, C = xc.shape
-    dev = xc.device
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(dev)
     dgroup = _bn_dgroup(g, group)
     dgs = []
     for c0, c1 in _slices(C):
-        dg = None if g is None else torch.empty(rows // dgroup, c1 - c0, device=dev, dtype=torch.float32)
+        dg = None if g is None else torch.empty(rows // dgroup, c1 - c0, device=xc.device, dtype=torch.float32)
         dgs.append(dg)
-        rc = lib.simamba_bn_relu_bwd_dx(_off(dyc, c0), _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group),
-                                        _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(sums[1], c0),
-                                        _off(sums[0], c0), count.data_ptr(), _off(dx, c0), _lib.ptr(dg), dgroup, rows,
-                                        c1 - c0, C, code, st)
-        _lib.check(rc, "simamba_bn_relu_bwd_dx")
+        call(c0, c1, _slice_of(g, c0, c1, C), dg, dgroup)
     if g is None:
         return None
     dgt = dgs[0] if len(dgs) == 1 else torch.cat(dgs, dim=1)
     if dgroup != group:
         dgt = dgt.view(rows // group, group // dgroup, C).sum(1)
     return dgt
+
+
+class BnReluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gterm, group, weight, bias, running_mean, running_var, momentum, eps, training):
+        _lib.require_gpu(x, "bn_relu_fn")
+        lib = _lib.load()
+        xc, g, w, b, y, mean, invstd = _bn_operands(x, gterm, weight, bias)
+        rows, C = xc.shape
+        dev = xc.device
+        code = _lib.dtype_code(xc.dtype)
+        part = _bn_partial(lib, rows, C, dev)
+        with torch.cuda.device(dev), _lib.timed("bn_relu_fwd", dev):
+            for c0, c1 in _slices(C):
+                _abi("simamba_bn_relu_fwd", _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(w, c0),
+                     _off(b, c0), _off(running_mean, c0), _off(running_var, c0), float(momentum), float(eps),
+                     int(bool(training)), _off(y, c0), _off(mean, c0), _off(invstd, c0), part.data_ptr(), rows, c1 - c0,
+                     C, code, _lib.stream_ptr(dev))
+        ctx.save_for_backward(xc, g, w, b, mean, invstd)
+        ctx.meta = (int(group), bool(training), code, _dtypes(x, gterm, weight, bias))
+        ctx.part = part
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, g, w, b, mean, invstd = ctx.saved_tensors
+        group, training, code, dtypes = ctx.meta
+        rows, C = xc.shape
+        dev = xc.device
+        dyc = dy.to(xc.dtype).contiguous()
+        dx = torch.empty_like(xc)
+        dw = torch.empty(C, device=dev, dtype=torch.float32)
+        db = torch.empty(C, device=dev, dtype=torch.float32)
+
+        def one(c0, c1, gsl, dg, dgroup):
+            _abi("simamba_bn_relu_bwd", _off(dyc, c0), _off(xc, c0), _lib.ptr(gsl), group, _off(w, c0), _off(b, c0),
+                 _off(mean, c0), _off(invstd, c0), _off(dx, c0), _lib.ptr(dg), dgroup, _off(dw, c0), _off(db, c0),
+                 ctx.part.data_ptr(), rows, c1 - c0, C, code, int(training), _lib.stream_ptr(dev))
+        with torch.cuda.device(dev), _lib.timed("bn_relu_bwd", dev):
+            dgt = _bn_dx_slices(xc, g, group, one)
+        return _bn_grads(dtypes, dx, dgt, dw, db)
+
+
+# ---- the kernels' stages over plain buffers (SyncBnReluFn; the tests drive them with row shards as ranks) --------------
+def bn_stats_local(xc, g, group, stats, part):
+    """This rank's (count, mean, M2) per channel of xc (rows, C) (+ g[row // group]) into ``stats`` (3, C) float64."""
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    for c0, c1 in _slices(C):
+        _abi("simamba_bn_stats_local", _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(stats, c0), C,
+             part.data_ptr(), rows, c1 - c0, C, code, st)
+
+
+def bn_stats_merge(gathered, running_mean, running_var, momentum, eps, mean, invstd, count):
+    """(W, 3, C) float64 blocks of all ranks -> mean, invstd (C) float32, count (1) float64, running statistics."""
+    world, _, C = gathered.shape
+    _abi("simamba_bn_stats_merge", gathered.data_ptr(), world, _lib.ptr(running_mean), _lib.ptr(running_var),
+         float(momentum), float(eps), mean.data_ptr(), invstd.data_ptr(), count.data_ptr(), C,
+         _lib.stream_ptr(gathered.device))
+
+
+def bn_relu_apply(xc, g, group, w, b, mean, invstd, y):
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    for c0, c1 in _slices(C):
+        _abi("simamba_bn_relu_apply", _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(w, c0),
+             _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(y, c0), rows, c1 - c0, C, code, st)
+
+
+def bn_relu_bwd_sums(dyc, xc, g, group, w, b, mean, invstd, sums, part):
+    """This rank's sum dy*mask (``sums[0]``) and sum dy*mask*xhat (``sums[1]``); ``sums`` (2, C) float32."""
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    for c0, c1 in _slices(C):
+        _abi("simamba_bn_relu_bwd_sums", _off(dyc, c0), _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group),
+             _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(sums[1], c0), _off(sums[0], c0),
+             part.data_ptr(), rows, c1 - c0, C, code, st)
+
+
+def bn_relu_bwd_dx(dyc, xc, g, group, w, b, mean, invstd, sums, count, dx):
+    """dx with the sums and the row count of ALL ranks; returns the gradient of g (rows / group, C) float32 or None."""
+    rows, C = xc.shape
+    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+
+    def one(c0, c1, gsl, dg, dgroup):
+        _abi("simamba_bn_relu_bwd_dx", _off(dyc, c0), _off(xc, c0), _lib.ptr(gsl), int(group), _off(w, c0), _off(b, c0),
+             _off(mean, c0), _off(invstd, c0), _off(sums[1], c0), _off(sums[0], c0), count.data_ptr(), _off(dx, c0),
+             _lib.ptr(dg), dgroup, rows, c1 - c0, C, code, st)
+    return _bn_dx_slices(xc, g, group, one)
 
 
 class SyncBnReluFn(torch.autograd.Function):
@@ -249,16 +243,10 @@ class SyncBnReluFn(torch.autograd.Function):
     def forward(ctx, x, gterm, group, weight, bias, running_mean, running_var, momentum, eps, process_group):
         _lib.require_gpu(x, "sync_bn_relu_fn")
         lib = _lib.load()
-        xc = x.contiguous()
+        xc, g, w, b, y, mean, invstd = _bn_operands(x, gterm, weight, bias)
         rows, C = xc.shape
         dev = xc.device
         world = dist.get_world_size(process_group)
-        g = None if gterm is None else gterm.float().contiguous()
-        w = None if weight is None else weight.float().contiguous()
-        b = None if bias is None else bias.float().contiguous()
-        y = torch.empty_like(xc)
-        mean = torch.empty(C, device=dev, dtype=torch.float32)
-        invstd = torch.empty(C, device=dev, dtype=torch.float32)
         count = torch.empty(1, device=dev, dtype=torch.float64)
         stats = torch.empty(3, C, device=dev, dtype=torch.float64)
         gathered = torch.empty(world, 3, C, device=dev, dtype=torch.float64)
@@ -269,8 +257,7 @@ class SyncBnReluFn(torch.autograd.Function):
             bn_stats_merge(gathered, running_mean, running_var, momentum, eps, mean, invstd, count)
             bn_relu_apply(xc, g, group, w, b, mean, invstd, y)
         ctx.save_for_backward(xc, g, w, b, mean, invstd, count)
-        ctx.meta = (int(group), x.dtype, None if gterm is None else gterm.dtype,
-                    None if weight is None else weight.dtype, None if bias is None else bias.dtype)
+        ctx.meta = (int(group), _dtypes(x, gterm, weight, bias))
         ctx.part = part
         ctx.process_group = process_group
         return y
@@ -278,7 +265,7 @@ class SyncBnReluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xc, g, w, b, mean, invstd, count = ctx.saved_tensors
-        group, xdtype, gdtype, wdtype, bdtype = ctx.meta
+        group, dtypes = ctx.meta
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(_CAPTURE_MSG)
         C = xc.shape[1]
@@ -291,9 +278,7 @@ class SyncBnReluFn(torch.autograd.Function):
             local = sums.clone()             # weight / bias gradients stay this rank's sums (DDP averages them)
             dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.process_group)
             dgt = bn_relu_bwd_dx(dyc, xc, g, group, w, b, mean, invstd, sums, count, dx)
-        return (dx.to(xdtype), None if dgt is None else dgt.to(gdtype), None,
-                None if wdtype is None else local[1].to(wdtype), None if bdtype is None else local[0].to(bdtype),
-                None, None, None, None, None)
+        return _bn_grads(dtypes, dx, dgt, local[1], local[0])
 
 
 _CAPTURE_MSG = ("sync_bn_relu_fn: the stream is being captured into a graph; the collectives of cross-rank batch "
@@ -314,6 +299,10 @@ def _bn_step(bn):
     return training, 0.0 if momentum is None else momentum, rm, rv
 
 
+def _dist_up():
+    return dist.is_available() and dist.is_initialized()
+
+
 def _bn_relu_local(x, bn, gterm, group):
     training, momentum, rm, rv = _bn_step(bn)
     return BnReluFn.apply(x, gterm, group, bn.weight, bn.bias, rm, rv, momentum, bn.eps, training)
@@ -332,7 +321,7 @@ def sync_bn_relu_fn(x, bn, gterm=None, group=0, process_group=None):
         return _bn_relu_local(x, bn, gterm, group)
     if x.shape[0] < 1:
         raise ValueError(f"sync_bn_relu_fn: this rank holds {x.shape[0]} rows; every rank needs at least 1")
-    if not (dist.is_available() and dist.is_initialized()):
+    if not _dist_up():
         raise RuntimeError("sync_bn_relu_fn: torch.distributed has no initialised process group")
     if x.is_cuda and torch.cuda.is_current_stream_capturing():
         raise RuntimeError(_CAPTURE_MSG)
@@ -343,9 +332,7 @@ def sync_bn_relu_fn(x, bn, gterm=None, group=0, process_group=None):
 
 
 def _sync_world(bn):
-    if not (dist.is_available() and dist.is_initialized()):
-        return 1
-    return dist.get_world_size(bn.process_group)
+    return dist.get_world_size(bn.process_group) if _dist_up() else 1
 
 
 def bn_relu_fn(x, bn: torch.nn.BatchNorm1d, gterm=None, group=0):
@@ -371,7 +358,6 @@ class GroupMaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _lib.require_gpu(x, "group_max_fn")
-        lib = _lib.load()
         xc = x.contiguous()
         groups, n, C = xc.shape
         dev = xc.device
@@ -379,9 +365,8 @@ class GroupMaxFn(torch.autograd.Function):
         out = torch.empty(groups, C, device=dev, dtype=xc.dtype)
         idx = torch.empty(groups, C, device=dev, dtype=torch.uint8)
         with torch.cuda.device(dev):
-            rc = lib.simamba_group_max_fwd(xc.data_ptr(), out.data_ptr(), idx.data_ptr(), groups, n, C, code,
-                                           _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_group_max_fwd")
+            _abi("simamba_group_max_fwd", xc.data_ptr(), out.data_ptr(), idx.data_ptr(), groups, n, C, code,
+                 _lib.stream_ptr(dev))
         ctx.save_for_backward(idx)
         ctx.meta = (groups, n, C, code, xc.dtype)
         return out
@@ -390,13 +375,11 @@ class GroupMaxFn(torch.autograd.Function):
     def backward(ctx, dout):
         (idx,) = ctx.saved_tensors
         groups, n, C, code, dtype = ctx.meta
-        lib = _lib.load()
         d = dout.to(dtype).contiguous()
         dx = torch.empty(groups, n, C, device=d.device, dtype=dtype)
         with torch.cuda.device(d.device):
-            rc = lib.simamba_group_max_bwd(d.data_ptr(), idx.data_ptr(), dx.data_ptr(), groups, n, C, code,
-                                           _lib.stream_ptr(d.device))
-        _lib.check(rc, "simamba_group_max_bwd")
+            _abi("simamba_group_max_bwd", d.data_ptr(), idx.data_ptr(), dx.data_ptr(), groups, n, C, code,
+                 _lib.stream_ptr(d.device))
         return dx
 
 

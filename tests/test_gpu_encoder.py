@@ -118,7 +118,6 @@ def test_bn_relu_argument_errors(device):
     x = torch.zeros(64, 8, device=device)
     m = torch.zeros(8, device=device)
     part = torch.zeros(1, 2, 8, device=device)
-    # group must divide 256 and rows
     # group must divide rows
     rc = lib.simamba_bn_relu_fwd(x.data_ptr(), m.data_ptr(), 7, None, None, None, None, 0.1, 1e-5, 1, x.data_ptr(),
                                  m.data_ptr(), m.data_ptr(), part.data_ptr(), 64, 8, 0, 0, None)

@@ -181,6 +181,57 @@ def test_one_rank_equals_the_monolithic_forward(rows, C, group, device):
     assert nerr(got["y"], y) < 1e-6
 
 
+@pytest.mark.parametrize("rows,C,group,ld,dtype", [
+    (300, 8, 0, 0, torch.float32),           # a ragged tail, two threads per row
+    (1024, 512, 32, 0, torch.float32),       # the group term and the per-group sums of dx
+    (512, 8, 0, 16, torch.float32),          # channels 8..15 of a 16-wide tensor, in place
+    (512, 256, 32, 0, torch.bfloat16)])
+def test_fused_and_staged_entry_points_are_the_same_passes(rows, C, group, ld, dtype, device):
+    """Raw ABI, one rank: simamba_bn_relu_apply with the mean / invstd simamba_bn_relu_fwd wrote gives the fused y, and
+    simamba_bn_relu_bwd_sums + _bwd_dx with them and count = rows give simamba_bn_relu_bwd's dx, dgterm, dweight and
+    dbias -- bit for bit: the same kernels on the same inputs, no atomics."""
+    from si_mamba_amd import _lib
+    lib = _lib.load()
+    width = ld or C
+    c0 = width - C
+    x, gt, dy, w, b = make_case((rows,), width, group, dtype, device, rows + C)
+    code, st = _lib.dtype_code(dtype), _lib.stream_ptr(device)
+
+    def at(t):                                               # the slice's first element
+        return t.data_ptr() + c0 * t.element_size()
+
+    def f32(*shape):
+        return torch.zeros(*shape, device=device)
+    part = f32(lib.simamba_bn_relu_grid(rows), 2, C)
+    mean, invstd = f32(C), f32(C)
+    count = torch.full((1,), float(rows), device=device, dtype=torch.float64)
+    dgroup = group
+    fused = dict(y=torch.zeros_like(x), dx=torch.zeros_like(x), dw=f32(C), db=f32(C),
+                 dg=f32(rows // group, C) if group else None)
+    staged = {k: None if v is None else torch.zeros_like(v) for k, v in fused.items()}
+    args = (at(x), _lib.ptr(gt), group, at(w), at(b))
+    assert lib.simamba_bn_relu_fwd(*args, None, None, MOM, EPS, 1, at(fused["y"]), mean.data_ptr(), invstd.data_ptr(),
+                                   part.data_ptr(), rows, C, ld, code, st) == 0
+    assert lib.simamba_bn_relu_apply(*args, mean.data_ptr(), invstd.data_ptr(), at(staged["y"]), rows, C, ld, code,
+                                     st) == 0
+    args = (at(dy),) + args + (mean.data_ptr(), invstd.data_ptr())
+    o = fused
+    assert lib.simamba_bn_relu_bwd(*args, at(o["dx"]), _lib.ptr(o["dg"]), dgroup, o["dw"].data_ptr(),
+                                   o["db"].data_ptr(), part.data_ptr(), rows, C, ld, code, 1, st) == 0
+    o = staged
+    assert lib.simamba_bn_relu_bwd_sums(*args, o["dw"].data_ptr(), o["db"].data_ptr(), part.data_ptr(), rows, C, ld,
+                                        code, st) == 0
+    assert lib.simamba_bn_relu_bwd_dx(*args, o["dw"].data_ptr(), o["db"].data_ptr(), count.data_ptr(), at(o["dx"]),
+                                      _lib.ptr(o["dg"]), dgroup, rows, C, ld, code, st) == 0
+    torch.cuda.synchronize()
+    assert float(fused["y"].float().abs().sum()) > 0 and float(fused["dx"].float().abs().sum()) > 0
+    for k, v in fused.items():
+        if v is not None:
+            assert torch.equal(staged[k], v), k
+    if c0:                                                   # the other channels of the wide tensor are left alone
+        assert not fused["y"][:, :c0].any() and not fused["dx"][:, :c0].any()
+
+
 def test_large_mean_is_stable_across_shards(device):
     """Two shards whose first rows, and hence shifts, differ; channel means 1000x the spread must not cancel in the
     merge (the bar of test_bn_relu_large_mean_is_stable)."""

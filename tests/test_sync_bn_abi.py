@@ -1,6 +1,6 @@
-"""CPU: the staged BatchNorm+ReLU entry points (csrc/bn_relu.hip; the stages nn.SyncBatchNorm's cross-rank statistics
-run between collectives) validate their arguments before any launch, with the codes and the order of checks of
-simamba_bn_relu_fwd / _bwd: dtype (-3), empty problem (0), shape (-2), null pointers (-1).
+"""CPU: the entry points of csrc/bn_relu.hip -- the fused simamba_bn_relu_fwd / _bwd, the stages nn.SyncBatchNorm's
+cross-rank statistics run between collectives, and the group max -- validate their arguments before any launch, all with
+the same codes in the same order: dtype (-3), empty problem (0), shape (-2), null pointers (-1).
 
 Every row states what it changes in a call that would otherwise be accepted, and the code the library answers; rows
 with two faults pin the order of the checks.  P is an address that is never dereferenced: no row reaches a launch."""
@@ -18,8 +18,14 @@ _SUMS = dict(dy=P, x=P, gterm=None, group=0, weight=None, bias=None, mean=P, inv
              rows=64, C=8, ld=0, io_dtype=0, stream=None)
 _DX = dict(dy=P, x=P, gterm=None, group=0, weight=None, bias=None, mean=P, invstd=P, sum_dweight=P, sum_dbias=P,
            count=P, dx=P, dgterm=None, dgroup=0, rows=64, C=8, ld=0, io_dtype=0, stream=None)
+_FWD = dict(x=P, gterm=None, group=0, weight=None, bias=None, running_mean=None, running_var=None, momentum=0.1,
+            eps=1e-5, training=1, y=P, mean=P, invstd=P, partial=P, rows=64, C=8, ld=0, io_dtype=0, stream=None)
+_BWD = dict(dy=P, x=P, gterm=None, group=0, weight=None, bias=None, mean=P, invstd=P, dx=P, dgterm=None, dgroup=0,
+            dweight=P, dbias=P, partial=P, rows=64, C=8, ld=0, io_dtype=0, training=1, stream=None)
+_GMAX_FWD = dict(x=P, out=P, idx=P, groups=4, n=32, C=8, io_dtype=0, stream=None)
+_GMAX_BWD = dict(dout=P, idx=P, dx=P, groups=4, n=32, C=8, io_dtype=0, stream=None)
 
-# what the four stages that walk (rows, C) activations share
+# what the six entry points that walk (rows, C) activations share
 _COMMON = [
     (dict(io_dtype=7), E_DTYPE), (dict(io_dtype=-1), E_DTYPE),
     (dict(rows=0), OK), (dict(rows=0, x=None), OK), (dict(rows=0, C=6), OK),              # empty: nothing to check
@@ -30,6 +36,17 @@ _COMMON = [
     # two faults: dtype, empty, shape, pointers
     (dict(io_dtype=7, rows=0), E_DTYPE), (dict(io_dtype=7, C=6), E_DTYPE), (dict(C=6, x=None), E_SHAPE),
     (dict(gterm=P, group=7, x=None), E_SHAPE),
+]
+
+# ... and the two directions of the group max
+_GMAX = [
+    (dict(io_dtype=7), E_DTYPE), (dict(io_dtype=-1), E_DTYPE),
+    (dict(groups=0), OK), (dict(groups=0, C=6), OK),
+    (dict(groups=-1), E_SHAPE), (dict(n=0), E_SHAPE), (dict(n=257), E_SHAPE), (dict(C=0), E_SHAPE), (dict(C=6), E_SHAPE),
+    (dict(idx=None), E_NULL),
+    # a grid of more than 2^31 - 1 workgroups is refused, after the pointers, not truncated
+    (dict(groups=1 << 42), E_SHAPE), (dict(groups=1 << 42, idx=None), E_NULL),
+    (dict(io_dtype=7, groups=0), E_DTYPE), (dict(io_dtype=7, C=6), E_DTYPE), (dict(C=6, idx=None), E_SHAPE),
 ]
 
 ROWS = [
@@ -58,6 +75,28 @@ ROWS = [
         (dict(gterm=P, group=64, dgterm=P, dgroup=128), E_SHAPE),                         # 64 rows % 128
         (dict(dgterm=P, dgroup=32), E_NULL),
         (dict(gterm=P, group=32, dgterm=P, dgroup=48, dy=None), E_SHAPE),
+    ]),
+    ("simamba_bn_relu_fwd", _FWD, _COMMON + [
+        (dict(y=None), E_NULL), (dict(mean=None), E_NULL), (dict(invstd=None), E_NULL),
+        (dict(partial=None), E_NULL),                                                     # batch statistics need it
+        (dict(training=0), E_NULL), (dict(training=0, running_mean=P), E_NULL),           # eval: the running ones
+        (dict(training=0, running_var=P), E_NULL),
+        (dict(C=6, partial=None), E_SHAPE), (dict(io_dtype=7, training=0), E_DTYPE), (dict(rows=0, training=0), OK),
+    ]),
+    ("simamba_bn_relu_bwd", _BWD, _COMMON + [
+        (dict(dy=None), E_NULL), (dict(dx=None), E_NULL), (dict(mean=None), E_NULL), (dict(invstd=None), E_NULL),
+        (dict(dweight=None), E_NULL), (dict(dbias=None), E_NULL), (dict(partial=None), E_NULL),
+        (dict(gterm=P, group=32, dgterm=P, dgroup=0), E_SHAPE), (dict(gterm=P, group=32, dgterm=P, dgroup=48), E_SHAPE),
+        (dict(gterm=P, group=64, dgterm=P, dgroup=128), E_SHAPE),
+        (dict(dgterm=P, dgroup=32), E_NULL),
+        (dict(gterm=P, group=32, dgterm=P, dgroup=48, dy=None), E_SHAPE), (dict(dgterm=P, dgroup=48), E_SHAPE),
+        (dict(C=6, dgterm=P, dgroup=32), E_SHAPE),
+    ]),
+    ("simamba_group_max_fwd", _GMAX_FWD, _GMAX + [
+        (dict(x=None), E_NULL), (dict(out=None), E_NULL), (dict(groups=0, x=None), OK), (dict(n=0, x=None), E_SHAPE),
+    ]),
+    ("simamba_group_max_bwd", _GMAX_BWD, _GMAX + [
+        (dict(dout=None), E_NULL), (dict(dx=None), E_NULL), (dict(groups=0, dx=None), OK), (dict(n=0, dx=None), E_SHAPE),
     ]),
 ]
 
