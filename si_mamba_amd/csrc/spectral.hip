@@ -9,8 +9,9 @@
 // round-robin (tournament) ordering: G/2 disjoint column pairs per step, one 16-lane DPP row per pair.
 // Above 128 patches the graph and the top-k eigenpairs run on the global-workspace kernels of spectral_large.hip.
 // This file is compiled WITHOUT fast-math and with -ffp-contract=off so that distances and the
-// Laplacian entries round exactly like the reference's unfused torch ops.
-#include "spectral_common.h"
+// Laplacian entries round exactly like the reference's unfused torch ops; those expressions, shared with the
+// other two files, are in spectral_device.h.
+#include "spectral_device.h"
 
 namespace simamba {
 
@@ -25,12 +26,7 @@ __global__ void dist_sum_kernel(const float* __restrict__ pts, double* __restric
   double s = 0.0;
   for (int e = threadIdx.x; e < G * G; e += kGraphThreads) {
     const int i = e / G, j = e - i * G;
-    float d2 = 0.f;
-    for (int f = 0; f < F; ++f) {
-      const float df = P[i * F + f] - P[j * F + f];
-      d2 = d2 + df * df;
-    }
-    s += static_cast<double>(sqrtf(d2));
+    s += static_cast<double>(point_dist(P, i, j, F));
   }
   sred[threadIdx.x] = s;
   __syncthreads();
@@ -59,7 +55,7 @@ __device__ __forceinline__ void quad_argmin(float& v, int& i) {
     const float ov = step == 0 ? dpp<DPP_QUAD_XOR1>(v, v) : dpp<DPP_QUAD_XOR2>(v, v);
     const int oi = step == 0 ? __builtin_amdgcn_update_dpp(i, i, DPP_QUAD_XOR1, 0xf, 0xf, false)
                              : __builtin_amdgcn_update_dpp(i, i, DPP_QUAD_XOR2, 0xf, 0xf, false);
-    const bool take = (ov < v) || (ov == v && static_cast<unsigned>(oi) < static_cast<unsigned>(i));
+    const bool take = knn_take(ov, oi, v, i);
     v = take ? ov : v;
     i = take ? oi : i;
   }
@@ -82,13 +78,8 @@ __global__ __launch_bounds__(kSpecMaxG * kKnnLanes) void knn_graph_kernel(const 
   for (int e = tid; e < G * LD; e += nthr) sAdj[e] = 0.f;
   __syncthreads();
   const bool self_loop = flags & SIMAMBA_SPEC_SELF_LOOP;
-  const bool binary = flags & SIMAMBA_SPEC_BINARY;
   const bool symmetric = flags & SIMAMBA_SPEC_SYMMETRIC;
-  float inv2s2 = 0.f;
-  if (flags & SIMAMBA_SPEC_SIGMA_MEAN) {
-    const float sigma = static_cast<float>(*dist_sum / (static_cast<double>(B) * G * G));
-    inv2s2 = 2.f * (sigma * sigma);
-  }
+  const float inv2s2 = knn_inv2s2(flags, dist_sum, B, G);
   const int i = tid >> 2, part = tid & 3;             // node, lane of its quad (blockDim = 4 G: every quad is whole)
   int nlist = 0;
   {
@@ -123,11 +114,7 @@ __global__ __launch_bounds__(kSpecMaxG * kKnnLanes) void knn_graph_kernel(const 
       pv = bv; pi = bi;
       if (bi == 0x7fffffff) break;             // NaN distances: nothing left to pick (quad-uniform)
       if (m == 0 && !self_loop) continue;      // drop the nearest (the point itself)
-      float w = 1.f;
-      if (!binary) {
-        const float dd = bv * bv;
-        w = (flags & SIMAMBA_SPEC_SIGMA_MEAN) ? expf(-dd / inv2s2) : expf(-1.f * alpha * dd);
-      }
+      const float w = knn_edge_weight(flags, bv, alpha, inv2s2);
       if (part == 0) {
         sNb[i * kKnnMaxK + nlist] = bi;
         sWt[i * kKnnMaxK + nlist] = w;
@@ -190,26 +177,14 @@ __global__ __launch_bounds__(kEigThreads) void laplacian_eig_kernel(EigArgs p) {
   const float* A = p.adj + static_cast<size_t>(blockIdx.x) * G * G;
 
   // degrees of (A + A^T)/2, then the Laplacian's lower triangle mirrored (+ shift) into Wt
-  if (tid < G) {
-    float s = 0.f;
-    for (int j = 0; j < G; ++j) s = s + (A[tid * G + j] + A[j * G + tid]) / 2.f;
-    sDeg[tid] = s;
-  }
+  if (tid < G) sDeg[tid] = degree_sum(A, G, tid);
   for (int e = tid; e < kSpecMaxG * LD; e += kEigThreads) Wt[e] = 0.f;
   __syncthreads();
   const bool msym = p.flags & SIMAMBA_SPEC_MATRIX_SYM;
   for (int e = tid; e < G * G; e += kEigThreads) {
     const int i = e / G, j = e - i * G;
-    if (i >= j) {   // eigh(UPLO='L'): only the lower triangle of the (unsymmetric) L is read
-      const float aij = (A[i * G + j] + A[j * G + i]) / 2.f;
-      float l;
-      if (msym) {
-        const float di = powf(sDeg[i], -0.5f), dj = powf(sDeg[j], -0.5f);
-        l = (i == j ? 1.f : 0.f) - (di * aij) * dj;
-      } else {
-        const float dinv = 1.0f / (sDeg[i] + 1e-6f);
-        l = (i == j ? 1.f : 0.f) - dinv * aij;
-      }
+    if (i >= j) {
+      const float l = laplacian_entry(sym_adj(A, G, i, j), sDeg[i], sDeg[j], i == j, msym);
       const float w = l + (i == j ? kEigShift : 0.f);
       Wt[i * LD + j] = w;
       Wt[j * LD + i] = w;
@@ -401,23 +376,21 @@ extern "C" size_t simamba_laplacian_topk_workspace_bytes(int B, int G) {
   return sizeof(float) * static_cast<size_t>(B) * G * G;
 }
 
-// raise the dynamic-LDS cap of the two big-tile kernels once per process (thread-safe static init;
-// the value never changes afterwards, so this is not observable state)
-static void ensure_lds_attrs() {
-  static const bool once = [] {
-    const int cap = 4 * (kSpecMaxG * (kSpecMaxG + 1) + kSpecMaxG * 64 + 2 * kSpecMaxG * kKnnMaxK);   // knn_graph_kernel
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(laplacian_eig_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_graph_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    return true;
-  }();
-  (void)once;
-}
+// dynamic-LDS cap of the two big-tile kernels (knn_graph_kernel's layout at G = 128, F = 64 is the larger)
+constexpr int kBigTileLds = 4 * (kSpecMaxG * (kSpecMaxG + 1) + kSpecMaxG * 64 + 2 * kSpecMaxG * kKnnMaxK);
 
 static int check_groups(int B, int G, int max_g = kSpecMaxG) {
   if (B < 0) return SIMAMBA_E_SHAPE;
   if (G < 2 || G > max_g) return SIMAMBA_E_GROUPS;
+  return SIMAMBA_OK;
+}
+
+// B, G, then k: `need` = pairs to extract (k, +1 for MATRIX_SYM) must fit G
+static int check_topk(int B, int G, int k, unsigned flags, int max_g, int* need) {
+  const int rc = check_groups(B, G, max_g);
+  if (rc) return rc;
+  *need = k + ((flags & SIMAMBA_SPEC_MATRIX_SYM) ? 1 : 0);
+  if (k < 0 || *need > G) return SIMAMBA_E_GROUPS;
   return SIMAMBA_OK;
 }
 
@@ -438,7 +411,7 @@ extern "C" int simamba_knn_graph(const float* points, float* adj, void* workspac
     hipLaunchKernelGGL(dist_sum_kernel, dim3(B), dim3(kGraphThreads), 0, s, points, acc, G, F);
   }
   if (G > kSpecMaxG) return launch_knn_graph_large(points, adj, acc, B, G, F, knn, alpha, flags, s);
-  ensure_lds_attrs();
+  ensure_lds_cap<knn_graph_kernel>(kBigTileLds);
   const size_t smem = sizeof(float) * (static_cast<size_t>(G) * (G + 1) + G * F + 2 * G * kKnnMaxK);
   hipLaunchKernelGGL(knn_graph_kernel, dim3(B), dim3(G * kKnnLanes), smem, s, points, adj, acc, B, G, F, knn, alpha,
                      flags);
@@ -449,10 +422,9 @@ extern "C" int simamba_laplacian_topk(const float* adj, float* evals, float* eve
                                       float* all_evals, float* all_evecs, int B, int G, int k, unsigned flags,
                                       void* stream) {
   if (!adj) return SIMAMBA_E_NULLPTR;
-  int rc = check_groups(B, G);
+  int need;
+  const int rc = check_topk(B, G, k, flags, kSpecMaxG, &need);
   if (rc) return rc;
-  const int need = k + ((flags & SIMAMBA_SPEC_MATRIX_SYM) ? 1 : 0);
-  if (k < 0 || need > G) return SIMAMBA_E_GROUPS;
   if (B == 0) return SIMAMBA_OK;
   EigArgs a{adj, evals, evecs, order, all_evals, all_evecs, B, G, k, flags};
   // top-k only: Householder tridiagonalisation + bisection + inverse iteration (spectral_tridiag.hip);
@@ -460,7 +432,7 @@ extern "C" int simamba_laplacian_topk(const float* adj, float* evals, float* eve
   if (!all_evals && !all_evecs && need <= kTdMaxSel && G >= 3)
     return launch_tridiag_topk(a, static_cast<hipStream_t>(stream));
   const size_t smem = sizeof(float) * kSpecMaxG * kEigLD;
-  ensure_lds_attrs();
+  ensure_lds_cap<laplacian_eig_kernel>(kBigTileLds);
   hipLaunchKernelGGL(laplacian_eig_kernel, dim3(B), dim3(kEigThreads), smem, static_cast<hipStream_t>(stream), a);
   return static_cast<int>(hipGetLastError());
 }
@@ -474,10 +446,9 @@ extern "C" int simamba_laplacian_topk_ex(const float* adj, float* evals, float* 
                                          void* stream) {
   if (!adj) return SIMAMBA_E_NULLPTR;
   if (flags & ~kSpecKnownFlags) return SIMAMBA_E_VARIANT;
-  int rc = check_groups(B, G, kSpecMaxGLarge);
+  int need;
+  const int rc = check_topk(B, G, k, flags, kSpecMaxGLarge, &need);
   if (rc) return rc;
-  const int need = k + ((flags & SIMAMBA_SPEC_MATRIX_SYM) ? 1 : 0);
-  if (k < 0 || need > G) return SIMAMBA_E_GROUPS;
   const bool large = G > kSpecMaxG || (flags & SIMAMBA_SPEC_LARGE_G);
   if (!large)
     return simamba_laplacian_topk(adj, evals, evecs, order, nullptr, nullptr, B, G, k, flags, stream);

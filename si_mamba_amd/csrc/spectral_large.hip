@@ -10,23 +10,24 @@
 //     The launch boundary orders the two phases.  128 nodes per workgroup, 8 lanes per node; the selection is
 //     the lexicographic (distance, index) sweep of knn_graph_kernel with the distances recomputed from the
 //     LDS-resident points in every pass (a node's 512 distances do not fit its registers), and the second
-//     phase recomputes the lists rather than storing them.  Same arithmetic as knn_graph_kernel: identical edges,
-//     identical weights.
+//     phase recomputes the lists rather than storing them.  Distances, order predicates and weights are the
+//     functions of spectral_device.h that knn_graph_kernel calls: identical edges, identical weights.
 //
-//   laplacian_large_kernel  the algorithm of laplacian_tridiag_kernel with the matrix in the caller's workspace:
-//     1. S = mirrored lower triangle of I - D^-1 A (or the MATRIX_SYM form), built exactly as there;
+//   laplacian_large_kernel  the top-k solver of laplacian_tridiag_kernel with the matrix in the caller's workspace
+//     (1024 lanes, vectors of pitch 512).  Written here:
 //     2. Householder tridiagonalisation.  The rank-2 update of reflector k is fused with the matvec of
 //        reflector k+1: row k+1 is updated first (it is all the next reflector needs), then ONE pass over the
 //        trailing block applies update k and forms S22 v_{k+1}.  That is one read and one write of the block per
 //        reflector instead of two reads and a write.  The reflector is stored in the (dead) row k, contiguous,
 //        for the back-transformation;
-//     3. fp64 Sturm multisection, one wave per eigenvalue;
-//     4. fp64 inverse iteration (pivoted tridiagonal LU; the factors of at most four vectors share LDS at a time),
-//        modified Gram-Schmidt, back-transformation with the next reflector's load in flight;
-//     5. sign convention, MATRIX_SYM skip, smallest / largest selection, rank-sort argsort into `order`.
+//     4a. the batching of the inverse iteration: the LU factors of at most four vectors share LDS at a time;
+//     4c. the back-transformation with the next reflector's load in flight.
+//     Everything else (Laplacian entry, reflector parameters, Gershgorin range, Sturm multisection, the inverse
+//     iteration itself, Gram-Schmidt, sign convention, outputs) is spectral_device.h.
 // Compiled with -ffp-contract=off like spectral.hip: distances and Laplacian entries round like the reference's
 // unfused torch ops, and every S update is the same expression in every element (S stays exactly symmetric).
-#include "spectral_common.h"
+#include "spectral_device.h"
+
 
 namespace simamba {
 
@@ -59,12 +60,7 @@ __global__ __launch_bounds__(kKnnRowThreads) void knn_rows_kernel(const float* _
     for (int e = tid; e < nrows * G; e += kKnnRowThreads) A[static_cast<size_t>(r0) * G + e] = 0.f;
   global_barrier();
   const bool self_loop = flags & SIMAMBA_SPEC_SELF_LOOP;
-  const bool binary = flags & SIMAMBA_SPEC_BINARY;
-  float inv2s2 = 0.f;
-  if (flags & SIMAMBA_SPEC_SIGMA_MEAN) {
-    const float sigma = static_cast<float>(*dist_sum / (static_cast<double>(B) * G * G));
-    inv2s2 = 2.f * (sigma * sigma);
-  }
+  const float inv2s2 = knn_inv2s2(flags, dist_sum, B, G);
   const int i = r0 + tid / kKnnRowLanes, part = tid % kKnnRowLanes;
   if (i >= G) return;                              // whole 8-lane groups leave together; no barrier follows
   float pv = -1.f;                                 // previous pick, ascending lexicographic (value, index) order
@@ -73,12 +69,7 @@ __global__ __launch_bounds__(kKnnRowThreads) void knn_rows_kernel(const float* _
     float bv = 3.0e38f;
     int bi = 0x7fffffff;
     for (int j = part; j < G; j += kKnnRowLanes) {   // ascending j inside the lane: first hit is the lowest
-      float d2 = 0.f;
-      for (int f = 0; f < F; ++f) {
-        const float df = sP[i * F + f] - sP[j * F + f];
-        d2 = d2 + df * df;
-      }
-      const float v = sqrtf(d2);
+      const float v = point_dist(sP, i, j, F);
       const bool after_prev = (v > pv) || (v == pv && j > pi);
       if (after_prev && (v < bv)) { bv = v; bi = j; }
     }
@@ -86,18 +77,14 @@ __global__ __launch_bounds__(kKnnRowThreads) void knn_rows_kernel(const float* _
     for (int off = 1; off < kKnnRowLanes; off <<= 1) {
       const float ov = __shfl_xor(bv, off);
       const int oi = __shfl_xor(bi, off);
-      const bool take = (ov < bv) || (ov == bv && static_cast<unsigned>(oi) < static_cast<unsigned>(bi));
+      const bool take = knn_take(ov, oi, bv, bi);
       bv = take ? ov : bv;
       bi = take ? oi : bi;
     }
     pv = bv; pi = bi;
     if (bi == 0x7fffffff) break;                   // NaN distances: nothing left to pick (group-uniform)
     if (m == 0 && !self_loop) continue;            // drop the nearest (the point itself)
-    float w = 1.f;
-    if (!binary) {
-      const float dd = bv * bv;
-      w = (flags & SIMAMBA_SPEC_SIGMA_MEAN) ? expf(-dd / inv2s2) : expf(-1.f * alpha * dd);
-    }
+    const float w = knn_edge_weight(flags, bv, alpha, inv2s2);
     if (part == 0) {
       if (kMirror) A[static_cast<size_t>(bi) * G + i] = w;
       else A[static_cast<size_t>(i) * G + bi] = w;
@@ -107,15 +94,9 @@ __global__ __launch_bounds__(kKnnRowThreads) void knn_rows_kernel(const float* _
 
 int launch_knn_graph_large(const float* pts, float* adj, const double* dist_sum, int B, int G, int F, int knn,
                            float alpha, unsigned flags, hipStream_t s) {
-  static const bool once = [] {
-    const int cap = static_cast<int>(sizeof(float)) * kSpecMaxGLarge * 64;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rows_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rows_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    return true;
-  }();
-  (void)once;
+  const int cap = static_cast<int>(sizeof(float)) * kSpecMaxGLarge * 64;
+  ensure_lds_cap<knn_rows_kernel<false>>(cap);
+  ensure_lds_cap<knn_rows_kernel<true>>(cap);
   const dim3 grid(B, (G + kKnnRows - 1) / kKnnRows);
   const size_t smem = sizeof(float) * static_cast<size_t>(G) * F;
   hipLaunchKernelGGL(knn_rows_kernel<false>, grid, dim3(kKnnRowThreads), smem, s, pts, adj, dist_sum, B, G, F, knn,
@@ -136,35 +117,10 @@ constexpr int kLgBtPer = kSpecMaxGLarge / 64;      // reflector entries per lane
 constexpr size_t kLgDynLds = sizeof(double) * (kTdMaxSel + 4 * kLgVecBatch) * kSpecMaxGLarge +
                              kLgVecBatch * kSpecMaxGLarge;
 
-__device__ __forceinline__ double lg_wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 __device__ __forceinline__ float lg_wave_sum_f32(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
-}
-
-// 1/x to ~1 ulp (see spectral_tridiag.hip)
-__device__ __forceinline__ double lg_rcp_f64(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-
-__device__ __forceinline__ int lg_sturm_count(const double* d, const double* e2, int n, double sigma,
-                                              double pivmin) {
-  double q = d[0] - sigma;
-  if (fabs(q) < pivmin) q = -pivmin;
-  int cnt = q < 0.0;
-  for (int i = 1; i < n; ++i) {
-    q = d[i] - sigma - e2[i - 1] * lg_rcp_f64(q);
-    if (fabs(q) < pivmin) q = -pivmin;
-    cnt += q < 0.0;
-  }
-  return cnt;
 }
 
 __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, float* __restrict__ ws) {
@@ -199,25 +155,13 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
   const int nsel = p.k;
   const int ntot = nsel + skip;
 
-  // ---- 1. Laplacian (the same expressions as laplacian_tridiag_kernel) -----------------------------------------
-  if (tid < G) {
-    float s = 0.f;
-    for (int j = 0; j < G; ++j) s = s + (A[tid * G + j] + A[j * G + tid]) / 2.f;
-    sDeg[tid] = s;
-  }
+  // ---- 1. Laplacian ---------------------------------------------------------------------------------------------
+  if (tid < G) sDeg[tid] = degree_sum(A, G, tid);
   __syncthreads();
   for (int e = tid; e < G * G; e += kLgThreads) {
     const int i = e / G, j = e - i * G;
-    if (i >= j) {   // eigh(UPLO='L'): only the lower triangle of the (unsymmetric) L is read
-      const float aij = (A[i * G + j] + A[j * G + i]) / 2.f;
-      float l;
-      if (msym) {
-        const float di = powf(sDeg[i], -0.5f), dj = powf(sDeg[j], -0.5f);
-        l = (i == j ? 1.f : 0.f) - (di * aij) * dj;
-      } else {
-        const float dinv = 1.0f / (sDeg[i] + 1e-6f);
-        l = (i == j ? 1.f : 0.f) - dinv * aij;
-      }
+    if (i >= j) {
+      const float l = laplacian_entry(sym_adj(A, G, i, j), sDeg[i], sDeg[j], i == j, msym);
       S[i * G + j] = l;
       S[j * G + i] = l;
     }
@@ -259,13 +203,8 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
       nrm2 += (v.x + v.y) + (v.z + v.w);
     }
     const float x0 = sX0;
-    const float rest = nrm2 - x0 * x0;
-    float tau = 0.f, scale = 0.f, beta = x0;
-    if (rest > 1e-30f && rest > 1e-12f * nrm2) {   // identical in every lane
-      beta = -copysignf(sqrtf(nrm2), x0);
-      tau = (beta - x0) / beta;
-      scale = 1.0f / (x0 - beta);
-    }
+    float beta, tau, scale;
+    householder_params(nrm2, x0, &beta, &tau, &scale);      // identical in every lane
     if (tid == 0) { sTau[k] = tau; sE[k] = beta; }
     if (t >= 1 && t <= m) {
       const float v = (t == 1) ? 1.f : s * scale;
@@ -328,128 +267,28 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
   }
   __syncthreads();
   if (tid < G) sE2[tid] = sE[tid] * sE[tid];
-  // Gershgorin range and pivmin
-  double glo = 1e300, ghi = -1e300, emax = 0.0;
-  if (tid < G) {
-    const double el = tid > 0 ? fabs(sE[tid - 1]) : 0.0, er = tid + 1 < G ? fabs(sE[tid]) : 0.0;
-    glo = sD[tid] - el - er;
-    ghi = sD[tid] + el + er;
-    emax = er * er;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    glo = fmin(glo, __shfl_xor(glo, off));
-    ghi = fmax(ghi, __shfl_xor(ghi, off));
-    emax = fmax(emax, __shfl_xor(emax, off));
-  }
-  if (lane == 0) { sRed[0][wave] = glo; sRed[1][wave] = ghi; sRed[2][wave] = emax; }
-  __syncthreads();
-  glo = sRed[0][0]; ghi = sRed[1][0]; emax = sRed[2][0];
-#pragma unroll
-  for (int w = 1; w < kLgWaves; ++w) {
-    glo = fmin(glo, sRed[0][w]); ghi = fmax(ghi, sRed[1][w]); emax = fmax(emax, sRed[2][w]);
-  }
-  const double tnorm = fmax(fabs(glo), fabs(ghi));
-  const double pivmin = fmax(emax, 1.0) * 2.2250738585072014e-308 * 4.0 + 1e-290;
-  glo -= 1e-12 * tnorm + 1e-300;
-  ghi += 1e-12 * tnorm + 1e-300;
-
-  // ---- 3. wanted eigenvalues: multisection, one wave = 64 shifts per eigenvalue and round -------------------------
-  {
+  // ---- 3. Gershgorin range, then one wave per wanted eigenvalue ---------------------------------------------------
+  double glo, ghi, emax, tnorm, pivmin;
+  gershgorin_wave(sD, sE, G, tid, &glo, &ghi, &emax);
+  gershgorin_block<kLgThreads>(sRed[0], sRed[1], sRed[2], tid, &glo, &ghi, emax, &tnorm, &pivmin);
+  if (wave < ntot) {
     const int want = smallest ? wave : (G - 1 - wave);   // ascending index of the eigenvalue this wave finds
-    double lo = glo, hi = ghi;
-    if (wave < ntot) {
-      for (int round = 0; round < 5; ++round) {   // 65^-5 ~ 1e-9 of the Gershgorin range
-        const double step = (hi - lo) * (1.0 / 65.0);
-        const double sigma = lo + step * (lane + 1);
-        const int cnt = lg_sturm_count(sD, sE2, G, sigma, pivmin);
-        const unsigned long long above = __ballot(cnt > want);
-        const int tt = above ? __builtin_ctzll(above) : 64;
-        const double nlo = lo + step * tt;
-        hi = (tt == 64) ? hi : lo + step * (tt + 1);
-        lo = nlo;
-      }
-      if (lane == 0) sLam[wave] = 0.5 * (lo + hi);
-    }
+    const double lam = multisect_eigenvalue(sD, sE2, G, want, glo, ghi, pivmin, lane);
+    if (lane == 0) sLam[wave] = lam;
   }
   __syncthreads();
 
   // ---- 4a. inverse iteration, one lane (of its own wave) per vector, kLgVecBatch vectors per LDS batch -------------
   for (int b0 = 0; b0 < ntot; b0 += kLgVecBatch) {
     if (lane == 0 && wave >= b0 && wave < b0 + kLgVecBatch && wave < ntot) {
-      const int sv = wave, slot = wave - b0, n = G;
-      double* ra = sLa + slot * NG; double* ub = sLb + slot * NG; double* uc = sLc + slot * NG;
-      double* l = sLl + slot * NG; double* z = sZ + sv * NG;
-      unsigned char* piv = sPiv + slot * NG;
-      const double lam = sLam[sv];
-      const double tiny = fmax(tnorm, 1.0) * 1.1e-16;
-      double ai = sD[0] - lam;
-      double bi = (n > 1) ? sE[0] : 0.0;
-      for (int i = 0; i + 1 < n; ++i) {
-        const double sub = sE[i];
-        const double a1 = sD[i + 1] - lam;
-        const double b1 = (i + 2 < n) ? sE[i + 1] : 0.0;
-        if (fabs(ai) >= fabs(sub)) {
-          if (fabs(ai) < tiny) ai = tiny;
-          const double r = lg_rcp_f64(ai);
-          const double mult = sub * r;
-          ra[i] = r; ub[i] = bi; uc[i] = 0.0; l[i] = mult; piv[i] = 0;
-          ai = a1 - mult * bi;
-          bi = b1;
-        } else {
-          const double r = lg_rcp_f64(sub);
-          const double mult = ai * r;
-          ra[i] = r; ub[i] = a1; uc[i] = b1; l[i] = mult; piv[i] = 1;
-          ai = bi - mult * a1;
-          bi = -mult * b1;
-        }
-      }
-      if (fabs(ai) < tiny) ai = tiny;
-      ra[n - 1] = lg_rcp_f64(ai); ub[n - 1] = 0.0; uc[n - 1] = 0.0;
-      unsigned rng = 12345u + 977u * sv;
-      for (int i = 0; i < n; ++i) {               // deterministic start vector in (-1, 1)
-        rng = rng * 1664525u + 1013904223u;
-        z[i] = (static_cast<double>(rng >> 8) / 8388608.0) - 1.0;
-      }
-      for (int it = 0; it < 3; ++it) {
-        double zi = z[0];
-        for (int i = 0; i + 1 < n; ++i) {
-          double zn = z[i + 1];
-          if (piv[i]) { const double tmp = zi; zi = zn; zn = tmp; }
-          z[i] = zi;
-          zi = zn - l[i] * zi;
-        }
-        double z1 = zi * ra[n - 1], z2 = 0.0, nr = z1 * z1;
-        z[n - 1] = z1;
-        for (int i = n - 2; i >= 0; --i) {
-          const double zc = (z[i] - ub[i] * z1 - uc[i] * z2) * ra[i];
-          z[i] = zc;
-          nr = fma(zc, zc, nr);
-          z2 = z1; z1 = zc;
-        }
-        nr = 1.0 / sqrt(nr);
-        for (int i = 0; i < n; ++i) z[i] *= nr;
-      }
+      const int slot = wave - b0;
+      tridiag_inverse_iteration(G, sLam[wave], tnorm, inverse_iteration_seed(wave), sD, sE, sLa + slot * NG,
+                                sLb + slot * NG, sLc + slot * NG, sLl + slot * NG, sPiv + slot * NG, sZ + wave * NG);
     }
     __syncthreads();
   }
   // ---- 4b. modified Gram-Schmidt (wave 0) -------------------------------------------------------------------------
-  if (tid < 64) {
-    for (int sv = 1; sv < ntot; ++sv) {
-      double* zs = sZ + sv * NG;
-      for (int t2 = 0; t2 < sv; ++t2) {
-        const double* zt = sZ + t2 * NG;
-        double dot = 0.0;
-        for (int i = tid; i < G; i += 64) dot += zs[i] * zt[i];
-        dot = lg_wave_sum_f64(dot);
-        for (int i = tid; i < G; i += 64) zs[i] -= dot * zt[i];
-      }
-      double nr = 0.0;
-      for (int i = tid; i < G; i += 64) nr += zs[i] * zs[i];
-      nr = 1.0 / sqrt(lg_wave_sum_f64(nr));
-      for (int i = tid; i < G; i += 64) zs[i] *= nr;
-    }
-  }
+  if (tid < 64) gram_schmidt_wave0<NG>(sZ, ntot, G, tid);
   __syncthreads();
   // ---- 4c. back-transformation v = H_0 ... H_{G-3} z, one wave per vector; reflector k sits in row k of S ---------
   for (int sv = wave; sv < ntot; sv += kLgWaves) {
@@ -478,63 +317,23 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
         const int i = lane + 64 * q;
         if (i < m) dot += static_cast<double>(vk[q]) * z[k + 1 + i];
       }
-      dot = lg_wave_sum_f64(dot) * tau;
+      dot = wave_sum_f64(dot) * tau;
 #pragma unroll
       for (int q = 0; q < kLgBtPer; ++q) {
         const int i = lane + 64 * q;
         if (i < m) z[k + 1 + i] -= dot * static_cast<double>(vk[q]);
       }
     }
-    // sign convention: component of largest magnitude positive (first such index on ties)
-    double best = -1.0; int bi = 0x7fffffff;
-    for (int i = lane; i < G; i += 64) {
-      const double v = fabs(static_cast<double>(static_cast<float>(z[i])));
-      if (v > best) { best = v; bi = i; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double ob = __shfl_xor(best, off);
-      const int oi = __shfl_xor(bi, off);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) sSign[sv] = z[bi] < 0.0 ? -1.f : 1.f;
+    sign_of_largest(z, G, lane, &sSign[sv]);
   }
   __syncthreads();
 
   // ---- 5. outputs (the first `skip` extracted pairs are dropped: MATRIX_SYM) -----------------------------------------
-  if (p.evals && tid < nsel)
-    p.evals[static_cast<size_t>(blockIdx.x) * nsel + tid] = static_cast<float>(sLam[tid + skip]);
-  if (p.evecs) {
-    float* out = p.evecs + static_cast<size_t>(blockIdx.x) * G * nsel;
-    for (int e = tid; e < G * nsel; e += kLgThreads) {
-      const int i = e / nsel, mm = e - i * nsel;
-      out[e] = static_cast<float>(sZ[(mm + skip) * NG + i]) * sSign[mm + skip];
-    }
-  }
-  if (p.order) {
-    long long* out = p.order + static_cast<size_t>(blockIdx.x) * nsel * G;
-    for (int e = tid; e < G * nsel; e += kLgThreads) {
-      const int mm = e / G, i = e - mm * G;
-      const double* z = sZ + (mm + skip) * NG;
-      const float sg = sSign[mm + skip];
-      const float vi = static_cast<float>(z[i]) * sg;
-      int rk = 0;
-      for (int j = 0; j < G; ++j) {
-        const float vj = static_cast<float>(z[j]) * sg;
-        rk += (vj < vi) || (vj == vi && j < i);
-      }
-      out[mm * G + rk] = i;
-    }
-  }
+  write_topk_outputs<kLgThreads, NG>(p, sZ, sLam, sSign, skip);
 }
 
 int launch_laplacian_large_topk(const EigArgs& a, float* ws, hipStream_t s) {
-  static const bool once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(laplacian_large_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLgDynLds));
-    return true;
-  }();
-  (void)once;
+  ensure_lds_cap<laplacian_large_kernel>(static_cast<int>(kLgDynLds));
   hipLaunchKernelGGL(laplacian_large_kernel, dim3(a.B), dim3(kLgThreads), kLgDynLds, s, a, ws);
   return static_cast<int>(hipGetLastError());
 }

@@ -205,6 +205,42 @@ def test_forced_large_kernel_agrees_with_tridiagonal_kernel(name, device):
     np.testing.assert_allclose(v.cpu().numpy(), g["hardest.sym.vals"], atol=2e-5)
 
 
+# (G, forced large kernel): a single reflector, an odd G, a Gershgorin reduction that crosses one wave and the full
+# pitch on both kernels; the first size above the LDS limit and a G that is no multiple of 64 on the large kernel.
+SHARED_STEP_CASES = [(3, False), (5, False), (65, False), (128, False), (3, True), (5, True), (65, True), (128, True),
+                     (129, True), (200, True)]
+SHARED_STEP_SEED = 0     # float64 spectra of these clouds: selected eigenvalues at least 2.4e-3 apart (checked on CPU)
+
+
+@pytest.mark.parametrize("G,large", SHARED_STEP_CASES)
+def test_shared_solver_steps_small_and_full_width(G, large, device):
+    """The solver steps both eigen kernels share are parametrised by pitch, thread count and the number of extracted
+    pairs; every other test runs k = 4.  Here: k = min(8, G) smallest (all eight waves, both inverse-iteration batches
+    of the large kernel) and k = min(7, G - 1) MATRIX_SYM (eight extracted, first dropped), on a weighted symmetric
+    graph, at the module's bound.  No eigenvector parity with the oracle: at k = 8 the gaps of a random cloud are not
+    controlled, and residual and orthogonality do not depend on them."""
+    import contextlib
+    from si_mamba_amd import _lib, spectral
+    tol = 2e-5 * max(1, G / 128)
+    c = unit_ball_centers(2, G, SHARED_STEP_SEED)
+    adj = sr.create_graph_from_feature_space(c, min(8, G - 1), 10.0, True, False, False)
+    for k, msym in [(min(8, G), False), (min(7, G - 1), True)]:
+        skip = 1 if msym else 0
+        S = sr.eigh_lower(sr.sym_laplacian(adj.double()) if msym else sr.rw_laplacian(adj.double()))
+        want = torch.linalg.eigh(S)[0][:, skip:skip + k]
+        before = _lib.counters.get("spectral_large_g", 0)
+        with (_lib.spectral_large_g() if large and G <= 128 else contextlib.nullcontext()):
+            vals, vecs, _, _, order = spectral._eig(adj.to(device), k, True, msym, want_all=False, want_order=True)
+        assert _lib.counters.get("spectral_large_g", 0) == before + (1 if large else 0)
+        err = (vals.double().cpu() - want).abs().max().item()
+        res = _residual(adj, vals, vecs, msym=msym)
+        orth = (vecs.transpose(1, 2) @ vecs - torch.eye(k, device=device)).abs().max().item()
+        print(f"G={G} large={large} k={k} msym={msym}: eigenvalue err {err:.2e} residual {res:.2e} orth {orth:.2e}")
+        assert err < tol and res < tol and orth < tol, (k, msym, err, res, orth)
+        for i in range(k):
+            assert torch.equal(order[:, i], spectral.argsort_rows(vecs[:, :, i].contiguous())), (k, msym, i)
+
+
 def test_full_batch_large(device):
     """(B = 64, G = 512): solver invariants of the k pairs without an oracle (no full spectrum at this size)."""
     from si_mamba_amd import spectral
