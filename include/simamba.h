@@ -439,6 +439,26 @@ int simamba_group_max_bwd(const void* dout, const unsigned char* idx, void* dx, 
                           int io_dtype, void* stream);
 
 /*
+ * Backward of y = max over the n rows of a patch of (x W^T + b), without the dense (groups * n, c_out) gradient between
+ * the max and the product (csrc/encoder_sparse.hip).  idx (groups, c_out) uint8 is what simamba_group_max_fwd left;
+ * an entry >= n contributes nothing.  fp32 arithmetic, no atomics, every sum in a fixed order: the same bits on every
+ * call.
+ *   dout : (groups, c_out) io_dtype ; weight : (c_out, c_in) io_dtype ; x, dx : (groups * n, c_in) io_dtype, all
+ *   contiguous and 16-byte aligned (else SIMAMBA_E_ALIGN).  1 <= n <= 32, c_in % 64 == 0, c_out % 4 == 0,
+ *   c_out <= 384 (else SIMAMBA_E_SHAPE).  Checks in the order dtype, empty, shape, null pointers, alignment.
+ * simamba_max_linear_bwd_dx: dx[g n + r][:] = sum over {c : idx[g][c] == r} of dout[g][c] * weight[c][:], ascending c;
+ *   every row is written once, rows no channel chose as zeros.
+ * simamba_max_linear_bwd_dw: dw[c][:] = sum over g of dout[g][c] * x[g n + idx[g][c]][:] in fp32, (c_out, c_in);
+ *   partial: simamba_max_linear_bwd_slabs(groups, c_in) * c_out * c_in floats of scratch (per-slab sums, added in slab
+ *   order).
+ */
+int simamba_max_linear_bwd_slabs(long long groups, int c_in);
+int simamba_max_linear_bwd_dx(const void* dout, const unsigned char* idx, const void* weight, void* dx,
+                              long long groups, int n, int c_in, int c_out, int io_dtype, void* stream);
+int simamba_max_linear_bwd_dw(const void* dout, const unsigned char* idx, const void* x, float* dw, float* partial,
+                              long long groups, int n, int c_in, int c_out, int io_dtype, void* stream);
+
+/*
  * Feature propagation of the part-segmentation head (reference part_segmentation/models/pointnet2_utils.py:262-305,
  * PointNetFeaturePropagation.forward): for every query point the three nearest of the sample's S centres
  * (squared distance in the reference's expanded form, ties to the lower index), weights 1/(d + 1e-8) normalised

@@ -108,6 +108,9 @@ SIGNATURES = {
                                        c_int, _P]),
     "simamba_group_max_fwd": (c_int, [_P, _P, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_group_max_bwd": (c_int, [_P, _P, _P, _LL, c_int, c_int, c_int, _P]),
+    "simamba_max_linear_bwd_slabs": (c_int, [_LL, c_int]),
+    "simamba_max_linear_bwd_dx": (c_int, [_P, _P, _P, _P, _LL, c_int, c_int, c_int, c_int, _P]),
+    "simamba_max_linear_bwd_dw": (c_int, [_P, _P, _P, _P, _P, _LL, c_int, c_int, c_int, c_int, _P]),
     "simamba_three_nn": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "simamba_three_interpolate_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "simamba_three_interpolate_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -334,6 +337,26 @@ class fuse_out_norm(_Override):
 
 def fuse_out_norm_enabled():
     return _fuse_out_norm[0]
+
+
+_sparse_max_linear = [None]   # None: the measured default (sparse_max_linear_enabled); True / False: forced
+
+
+class sparse_max_linear(_Override):
+    """Context manager for benchmarks and parity tests: the encoder's last layer (linear, then max over the patch) with
+    the sparse backward of csrc/encoder_sparse.hip wherever its shapes apply (True), or as token_linear + group_max_fn
+    with the dense gradient between them (False).  Production never enters it and gets the measured default."""
+    cell, coerce = _sparse_max_linear, staticmethod(_tristate)
+
+
+def sparse_max_linear_enabled(dtype):
+    """Default: fp32 I/O only.  Measured at (8192 patches, 32 points, 512 -> 384), the whole backward of the pair
+    (tools/bench_encoder.py, profiles/encoder_sparse_kernels.txt): fp32 877 us sparse against 1 734 us dense (the two
+    exact-fp32 GEMMs run 103 GFLOP each on 31/32 zeros); bf16 904 us sparse against 489 us dense -- the bf16 MFMA does
+    each of those GEMMs in ~0.1 ms, less than the sparse kernels' latency-bound LDS loops take, so bf16 keeps the dense
+    route."""
+    import torch
+    return (dtype == torch.float32) if _sparse_max_linear[0] is None else _sparse_max_linear[0]
 
 
 class hand_in_proj(_Override):

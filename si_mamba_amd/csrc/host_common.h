@@ -1,5 +1,7 @@
 // Shared host helpers of the entry points: what they all make of `io_dtype`, and of a pointer's alignment.
 #pragma once
+#include <atomic>
+
 #include "common.h"
 
 namespace simamba {
@@ -17,6 +19,22 @@ template <typename F>
 inline decltype(auto) with_io_type(int io_dtype, F&& f) {
   if (io_dtype == SIMAMBA_F32) return f(float{});
   return f(bf16_t{});
+}
+
+// Raise kKernel's dynamic-LDS cap to `bytes`, once per kernel and device (the attribute belongs to the device's copy of
+// the code object; `bytes` is a constant of the kernel, so this is not observable state).  Returns the hipError_t of the
+// attribute call; a failure is not remembered, so the next call tries again.
+template <auto kKernel>
+inline hipError_t ensure_lds_cap(int bytes) {
+  static std::atomic<unsigned long long> done{0};          // bit d: device d has the cap
+  int dev = 0;
+  if (const hipError_t e = hipGetDevice(&dev)) return e;
+  const unsigned long long bit = (dev >= 0 && dev < 64) ? 1ull << dev : 0;
+  if (bit && (done.load(std::memory_order_acquire) & bit)) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
+  return e;
 }
 
 }  // namespace simamba

@@ -411,7 +411,7 @@ extern "C" int simamba_knn_graph(const float* points, float* adj, void* workspac
     hipLaunchKernelGGL(dist_sum_kernel, dim3(B), dim3(kGraphThreads), 0, s, points, acc, G, F);
   }
   if (G > kSpecMaxG) return launch_knn_graph_large(points, adj, acc, B, G, F, knn, alpha, flags, s);
-  ensure_lds_cap<knn_graph_kernel>(kBigTileLds);
+  (void)ensure_lds_cap<knn_graph_kernel>(kBigTileLds);
   const size_t smem = sizeof(float) * (static_cast<size_t>(G) * (G + 1) + G * F + 2 * G * kKnnMaxK);
   hipLaunchKernelGGL(knn_graph_kernel, dim3(B), dim3(G * kKnnLanes), smem, s, points, adj, acc, B, G, F, knn, alpha,
                      flags);
@@ -432,7 +432,7 @@ extern "C" int simamba_laplacian_topk(const float* adj, float* evals, float* eve
   if (!all_evals && !all_evecs && need <= kTdMaxSel && G >= 3)
     return launch_tridiag_topk(a, static_cast<hipStream_t>(stream));
   const size_t smem = sizeof(float) * kSpecMaxG * kEigLD;
-  ensure_lds_cap<laplacian_eig_kernel>(kBigTileLds);
+  (void)ensure_lds_cap<laplacian_eig_kernel>(kBigTileLds);
   hipLaunchKernelGGL(laplacian_eig_kernel, dim3(B), dim3(kEigThreads), smem, static_cast<hipStream_t>(stream), a);
   return static_cast<int>(hipGetLastError());
 }

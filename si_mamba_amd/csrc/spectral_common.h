@@ -1,7 +1,7 @@
 // Shared host declarations of the spectral kernels (spectral.hip, spectral_tridiag.hip, spectral_large.hip); the
 // device steps they share are in spectral_device.h.
 #pragma once
-#include "common.h"
+#include "host_common.h"   // ensure_lds_cap
 
 namespace simamba {
 
@@ -20,18 +20,6 @@ struct EigArgs {
   int B, G, k;
   unsigned flags;
 };
-
-// raise kKernel's dynamic-LDS cap once per process (thread-safe static init, one per kernel; the value never changes
-// afterwards, so this is not observable state)
-template <auto kKernel>
-inline void ensure_lds_cap(int bytes) {
-  static const bool once = [bytes] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              bytes);
-    return true;
-  }();
-  (void)once;
-}
 
 int launch_tridiag_topk(const EigArgs& a, hipStream_t s);
 // large-G paths: adjacency in the caller's adj (zero-filled here); the Laplacian in `ws` (B*G*G floats)

@@ -95,8 +95,8 @@ __global__ __launch_bounds__(kKnnRowThreads) void knn_rows_kernel(const float* _
 int launch_knn_graph_large(const float* pts, float* adj, const double* dist_sum, int B, int G, int F, int knn,
                            float alpha, unsigned flags, hipStream_t s) {
   const int cap = static_cast<int>(sizeof(float)) * kSpecMaxGLarge * 64;
-  ensure_lds_cap<knn_rows_kernel<false>>(cap);
-  ensure_lds_cap<knn_rows_kernel<true>>(cap);
+  (void)ensure_lds_cap<knn_rows_kernel<false>>(cap);
+  (void)ensure_lds_cap<knn_rows_kernel<true>>(cap);
   const dim3 grid(B, (G + kKnnRows - 1) / kKnnRows);
   const size_t smem = sizeof(float) * static_cast<size_t>(G) * F;
   hipLaunchKernelGGL(knn_rows_kernel<false>, grid, dim3(kKnnRowThreads), smem, s, pts, adj, dist_sum, B, G, F, knn,
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
 }
 
 int launch_laplacian_large_topk(const EigArgs& a, float* ws, hipStream_t s) {
-  ensure_lds_cap<laplacian_large_kernel>(static_cast<int>(kLgDynLds));
+  (void)ensure_lds_cap<laplacian_large_kernel>(static_cast<int>(kLgDynLds));
   hipLaunchKernelGGL(laplacian_large_kernel, dim3(a.B), dim3(kLgThreads), kLgDynLds, s, a, ws);
   return static_cast<int>(hipGetLastError());
 }

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(kTdThreads) void laplacian_tridiag_kernel(EigArgs p
 }
 
 int launch_tridiag_topk(const EigArgs& a, hipStream_t s) {
-  ensure_lds_cap<laplacian_tridiag_kernel>(kSpecMaxG * kTdLD * 4);
+  (void)ensure_lds_cap<laplacian_tridiag_kernel>(kSpecMaxG * kTdLD * 4);
   hipLaunchKernelGGL(laplacian_tridiag_kernel, dim3(a.B), dim3(kTdThreads), sizeof(float) * kSpecMaxG * kTdLD, s, a);
   return static_cast<int>(hipGetLastError());
 }

@@ -17,6 +17,12 @@
                   the statistics and the normalisation, and one all-reduce of (2, C) float32 between the two passes
                   of the backward
 
+  token_linear_group_max   group_max_fn(token_linear(x, W, b)) as ONE autograd node (the encoder's last layer): the same
+                  forward, and a backward that never forms the dense (rows, C_out) gradient of which the max leaves
+                  one entry in n non-zero -- csrc/encoder_sparse.hip sums only the products that are not zero (1/n of
+                  the two GEMMs, no atomics, bitwise repeatable); bf16 I/O, where the dense GEMMs are the faster
+                  ones, and shapes outside token_linear_group_max_ok take the two separate ops
+
 bn_relu_fn and group_max_fn are plain autograd Functions over the C ABI; BatchNorm keeps nn.BatchNorm1d's buffers (running_mean,
 running_var, num_batches_tracked) and train/eval semantics.
 """
@@ -386,3 +392,88 @@ class GroupMaxFn(torch.autograd.Function):
 def group_max_fn(x):
     """(groups, n, C) -> (groups, C): max over the n points of each patch."""
     return GroupMaxFn.apply(x)
+
+
+# ---- linear + max over the patch as one node with a sparse backward (csrc/encoder_sparse.hip) ---------------------------
+_SPARSE_MAX_N = 32         # points per patch
+_SPARSE_MAX_COUT = 384     # rows of W the input-gradient kernel keeps in LDS
+
+
+def _linear_io_dtype(x):
+    """dtype F.linear will return for x: the autocast dtype inside an autocast region, else x's own."""
+    return torch.get_autocast_dtype("cuda") if (x.is_cuda and torch.is_autocast_enabled("cuda")) else x.dtype
+
+
+def token_linear_group_max_ok(x, weight, n):
+    """Shape limits of simamba_max_linear_bwd_dx / _dw (include/simamba.h); anything else takes token_linear +
+    group_max_fn.  The one place where the route is chosen: by default fp32 I/O only, where the sparse backward was
+    measured faster (_lib.sparse_max_linear_enabled); _lib.sparse_max_linear forces either route."""
+    if not (x.is_cuda and x.dim() == 2 and weight.dim() == 2 and _lib.sparse_max_linear_enabled(_linear_io_dtype(x))):
+        return False
+    rows, cin = x.shape
+    cout = weight.shape[0]
+    return (1 <= n <= _SPARSE_MAX_N and rows > 0 and rows % n == 0 and cin == weight.shape[1] and cin % 64 == 0
+            and cout % 4 == 0 and 4 <= cout <= _SPARSE_MAX_COUT
+            and _linear_io_dtype(x) in (torch.float32, torch.bfloat16)
+            and x.is_contiguous() and x.data_ptr() % 16 == 0)
+
+
+class TokenLinearGroupMaxFn(torch.autograd.Function):
+    """max over each run of n rows of F.linear(x, weight, bias).  Saves x, weight and the arg max (uint8): neither the
+    (rows, C_out) product nor a dense gradient of it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, n):
+        y = torch.nn.functional.linear(x, weight, bias).contiguous()     # as TokenLinearFn: autocast's rounding
+        rows, cout = y.shape
+        groups = rows // n
+        dev = y.device
+        code = _lib.dtype_code(y.dtype)
+        out = torch.empty(groups, cout, device=dev, dtype=y.dtype)
+        idx = torch.empty(groups, cout, device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _abi("simamba_group_max_fwd", y.data_ptr(), out.data_ptr(), idx.data_ptr(), groups, n, cout, code,
+                 _lib.stream_ptr(dev))
+        ctx.save_for_backward(x, weight, idx)
+        ctx.meta = (groups, int(n), code, y.dtype, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, idx = ctx.saved_tensors
+        groups, n, code, io, has_bias = ctx.meta
+        cout, cin = weight.shape
+        dev = dout.device
+        d = dout.to(io).contiguous()
+        dx = dw = db = None
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            if ctx.needs_input_grad[0]:
+                w = weight.detach().to(io).contiguous()
+                dx = torch.empty(groups * n, cin, device=dev, dtype=io)
+                _abi("simamba_max_linear_bwd_dx", d.data_ptr(), idx.data_ptr(), w.data_ptr(), dx.data_ptr(), groups, n,
+                     cin, cout, code, st)
+                dx = dx.to(x.dtype)
+            if ctx.needs_input_grad[1]:
+                xc = x.detach().to(io).contiguous()
+                slabs = _lib.load().simamba_max_linear_bwd_slabs(groups, cin)
+                part = torch.empty(slabs, cout, cin, device=dev, dtype=torch.float32)
+                dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
+                _abi("simamba_max_linear_bwd_dw", d.data_ptr(), idx.data_ptr(), xc.data_ptr(), dw.data_ptr(),
+                     part.data_ptr(), groups, n, cin, cout, code, st)
+                dw = dw.to(weight.dtype)
+        if has_bias and ctx.needs_input_grad[2]:
+            db = d.sum(0, dtype=torch.float32).to(weight.dtype)          # over the patches, not the points
+        return dx, dw, db, None
+
+
+def token_linear_group_max(x, weight, bias, n):
+    """(groups * n, C_in) tokens -> (groups, C_out): max over the n points of each patch of x W^T + b.  The forward is
+    token_linear followed by group_max_fn, bit for bit; within token_linear_group_max_ok (fp32 I/O by default) the
+    backward skips the zeros the max leaves (TokenLinearGroupMaxFn), otherwise the two ops run as they are."""
+    if token_linear_group_max_ok(x, weight, n):
+        _lib.count("max_linear_sparse")
+        return TokenLinearGroupMaxFn.apply(x, weight, bias, n)
+    _lib.count("max_linear_dense")
+    y = token_linear(x, weight, bias)
+    return group_max_fn(y.view(y.shape[0] // n, n, y.shape[1]))

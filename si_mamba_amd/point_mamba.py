@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import grouping, spectral
 from .block import MixerModel
 from .add_norm import add_layer_norm_fn
-from .encoder_ops import bn_relu_fn, group_max_fn, token_linear
+from .encoder_ops import bn_relu_fn, group_max_fn, token_linear, token_linear_group_max
 
 
 class Group(nn.Module):
@@ -107,8 +107,8 @@ class Encoder(nn.Module):
             w3 = c3.weight.squeeze(-1)
             gterm = lin(fg, w3[:, :cf], c3.bias)                                         # (B*G, 512): global half + bias
             x = bn_relu_fn(lin(f, w3[:, cf:]), bn2, gterm=gterm, group=n)
-            f = lin(x, c4.weight.squeeze(-1), c4.bias)
-            return group_max_fn(f.view(bs * g, n, self.encoder_channel)).reshape(bs, g, self.encoder_channel)
+            # last layer and its max as one node: same forward; in fp32 a backward without the zeros behind the max
+            return token_linear_group_max(x, c4.weight.squeeze(-1), c4.bias, n).reshape(bs, g, self.encoder_channel)
         x = torch.relu(bn1(lin(x, c1.weight.squeeze(-1), c1.bias)))
         f = lin(x, c2.weight.squeeze(-1), c2.bias).view(bs * g, n, 256)
         fg = f.max(dim=1, keepdim=True)[0]

@@ -1,4 +1,5 @@
-"""Encoder streaming kernels micro-benchmark (tuning tool): bn_relu fwd/bwd and group max at the bench shapes."""
+"""Encoder streaming kernels micro-benchmark (tuning tool): bn_relu fwd/bwd, group max, and the backward of the last
+layer + max (sparse against dense) at the bench shapes."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch.nn as nn
@@ -34,6 +35,29 @@ for groups, n, C in [(8192, 32, 256), (8192, 32, 384)]:
     y = group_max_fn(x); dy = torch.randn_like(y)
     t = timeit(lambda: torch.autograd.grad(y, x, dy, retain_graph=True))
     print(f"group_max bwd: {t*1e3:7.1f} us  {mb/t/1e3:6.2f} TB/s;  torch max fwd {timeit(lambda: x.detach().max(dim=1)[0])*1e3:.1f} us")
+
+# ---- last layer + max: the sparse backward (csrc/encoder_sparse.hip) against the dense chain it replaces --------------
+# dense chain = group_max bwd (dense gradient) + input-gradient GEMM | split-K weight gradient + its sum | bias sum over
+# all rows; "dx" and "dw" rows time one product each (the dense ones include the group_max bwd both need)
+from si_mamba_amd import _lib
+from si_mamba_amd.encoder_ops import token_linear_group_max
+G, n, cin, cout = 8192, 32, 512, 384
+for dtype in (torch.float32, torch.bfloat16):
+    x = torch.randn(G * n, cin, device=dev).to(dtype)
+    w = (torch.randn(cout, cin, device=dev) / cin ** 0.5).to(dtype)
+    b = torch.randn(cout, device=dev).to(dtype)
+    dy = torch.randn(G, cout, device=dev).to(dtype)
+    for sparse in (True, False):
+        ts = []
+        for need in ((True, True, True), (True, False, False), (False, True, False)):   # all | dx only | dw only
+            xa, wa, ba = (t.clone().requires_grad_(r) for t, r in zip((x, w, b), need))
+            with _lib.sparse_max_linear(sparse):
+                y = token_linear_group_max(xa, wa, ba, n)
+            wrt = [t for t, r in zip((xa, wa, ba), need) if r]
+            ts.append(timeit(lambda: torch.autograd.grad(y, wrt, dy, retain_graph=True)))
+            del y
+        print(f"linear+max bwd ({G},{n},{cin}->{cout}) {str(dtype)[6:]:8s} {'sparse' if sparse else 'dense '}: "
+              f"all {ts[0]*1e3:7.1f} us   dx {ts[1]*1e3:7.1f} us   dw {ts[2]*1e3:7.1f} us")
 
 # ---- segmentation / pre-training head kernels ---------------------------------------------------------------
 from si_mamba_amd.interp import three_interpolate, three_nn
