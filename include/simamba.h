@@ -489,6 +489,35 @@ int simamba_chamfer_bwd(const float* pred, const float* gt, const float* ddist, 
                         const unsigned char* idx2, float* dpred, long long pairs, int n, int m, void* stream);
 
 /*
+ * The same distance between whole clouds, with gradients for both sets (csrc/chamfer_large.hip): tiled kernels,
+ * 1 <= n, m <= 8192 points per set, any number of pairs (pairs * (ceil(n / 256) + ceil(m / 256)) < 2^31).
+ *   x : (pairs, n, 3) fp32 ; y : (pairs, m, 3) fp32 ; dist : (pairs) fp32 ;
+ *   idx1 : (pairs, n) int32 nearest y of every x ; idx2 : (pairs, m) int32 nearest x of every y ;
+ *   d1 : (pairs, n) fp32, d2 : (pairs, m) fp32 : the squared distances to those neighbours (direct differences,
+ *   dx*dx + dy*dy + dz*dz; strict `<` in ascending index, so the lowest index wins a tie) ;
+ *   dist[p] = mean_i d1[p][i] + mean_j d2[p][j], fp64 partial sums in a fixed order.  All outputs are written by every
+ *   call; no workspace.  NaN / inf do not propagate: the search starts from 3.0e38 with a strict `<` (as in the
+ *   small kernels), so such a query reports distance 3.0e38 and index 0.
+ * Backward, from ddist (pairs) and the indices the forward left:
+ *   dx[i] = ddist * ( 2/n (x_i - y[idx1[i]]) + 2/m sum over {j : idx2[j] == i} of (x_i - y_j) ), ascending j,
+ *   dy symmetric.  dx (pairs, n, 3) or dy (pairs, m, 3) may be NULL: that gradient is skipped and nothing is written
+ *   for it.  No atomics in either call: the same bits every time.
+ * Checks in the order shape (SIMAMBA_E_SHAPE), empty (pairs == 0: SIMAMBA_OK, nothing read), null pointers.
+ * The _ex forms take `queries`, the query points a thread keeps in registers: 0 = the library's choice (what the plain
+ * forms pass: the largest of 4, 2, 1 that both sets fill and that leaves 512 workgroups), 1, 2 or 4 = that kernel
+ * (parity tests: the outputs do not depend on it, bit for bit); anything else SIMAMBA_E_VARIANT, checked first.
+ * Still ABI version 9: symbols added, none changed.
+ */
+int simamba_chamfer_large_fwd(const float* x, const float* y, float* dist, int* idx1, int* idx2, float* d1, float* d2,
+                              long long pairs, int n, int m, void* stream);
+int simamba_chamfer_large_bwd(const float* x, const float* y, const float* ddist, const int* idx1, const int* idx2,
+                              float* dx, float* dy, long long pairs, int n, int m, void* stream);
+int simamba_chamfer_large_fwd_ex(const float* x, const float* y, float* dist, int* idx1, int* idx2, float* d1,
+                                 float* d2, long long pairs, int n, int m, int queries, void* stream);
+int simamba_chamfer_large_bwd_ex(const float* x, const float* y, const float* ddist, const int* idx1, const int* idx2,
+                                 float* dx, float* dy, long long pairs, int n, int m, int queries, void* stream);
+
+/*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,
  * K=group_size, return_sorted=False)): idx[b][g][0..K) = the K points of cloud b nearest to centre g, ascending
  * squared distance (direct differences), ties to the lower point index.

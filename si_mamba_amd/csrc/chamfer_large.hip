@@ -1,0 +1,255 @@
+// Chamfer distance between whole clouds (1 <= n, m <= 8192 points per set), with gradients for both sets: the tiled
+// family beside the one-wave kernels of chamfer.hip (n, m <= 64, the MAE patch loss).  pytorch3d semantics: squared
+// L2 to the nearest neighbour, mean over each set's points, both directions summed; one value per pair of sets.
+//
+//   * chamfer_large_nn_kernel: both directions in one launch.  A workgroup owns 256 * Q query points of one set of
+//     one pair (Q = 1, 2 or 4 per thread, in registers) and walks the other set in LDS tiles of kChTile points,
+//     staged coalesced and padded to (x, y, z, -) so that one LDS read serves a target (ds_read_b96 here, where the
+//     fourth dword is unused; ds_read_b128 in the backward, where it carries an index); every lane reads the same
+//     address (a broadcast), and Q queries share each read.  Distance from direct differences, dx*dx + dy*dy + dz*dz
+//     as in chamfer.hip; strict `<` in ascending target index, so the lowest index wins a tie.  Writes the nearest
+//     distance (fp32) and index (int32) of every query.
+//   * chamfer_large_reduce_kernel: dist[p] = mean_i d1[p, i] + mean_j d2[p, j], one workgroup per pair, fp64 partial
+//     sums in a fixed order (thread t takes elements t, t + 256, ...; then a tree over the 256 threads).  No atomics.
+//   * chamfer_large_bwd_kernel: for either or both sets,
+//       dX_i = g ( 2/n (x_i - y[a(i)]) + 2/m sum_{j : b(j) = i} (x_i - y_j) ),
+//     the reverse matches found by the same tiled sweep: the tile holds (y_j, b(j)) in one float4, a thread compares
+//     b(j) against its own i and adds in ascending j.  n * m compares like the forward, no float atomics: the same
+//     bits on every call.
+// The result of a query does not depend on Q, the tile size or the grid mapping.
+// NaN and inf do not propagate as they do in pytorch3d: the search starts from 3.0e38 with a strict `<`, as in
+// chamfer.hip, so a query with a NaN coordinate, or one whose targets are all NaN, reports distance 3.0e38 and index 0,
+// and a diverged cloud shows as a huge finite (or inf) loss, not as NaN.
+#include <type_traits>
+
+#include "host_common.h"
+
+namespace simamba {
+
+constexpr int kChThreads = 256;
+constexpr int kChTile = 1024;        // targets per LDS tile: 16 KB
+constexpr int kChMaxPoints = 8192;
+
+// Stage targets [t0, t0 + cnt) of `set` (cnt <= kChTile) as float4; .w carries tag[t] (an int, bit-cast) or 0.
+__device__ __forceinline__ void stage_tile(float4* sT, const float* __restrict__ set, const int* __restrict__ tag,
+                                           int t0, int cnt) {
+  float* s = reinterpret_cast<float*>(sT);
+  const float* g = set + static_cast<long long>(t0) * 3;
+  for (int e = threadIdx.x; e < cnt * 3; e += kChThreads) {      // coalesced: consecutive lanes, consecutive floats
+    const int t = e / 3;
+    s[4 * t + (e - 3 * t)] = g[e];
+  }
+  if (tag)
+    for (int t = threadIdx.x; t < cnt; t += kChThreads) s[4 * t + 3] = __builtin_bit_cast(float, tag[t0 + t]);
+}
+
+// Work item `r` of a pair: blocks [0, bx) serve set X against Y, blocks [bx, bx + by) set Y against X.
+template <int Q>
+__global__ __launch_bounds__(kChThreads) void chamfer_large_nn_kernel(const float* __restrict__ x,
+                                                                      const float* __restrict__ y,
+                                                                      int* __restrict__ idx1, int* __restrict__ idx2,
+                                                                      float* __restrict__ d1, float* __restrict__ d2,
+                                                                      int n, int m, int bx, int by) {
+  __shared__ float4 sT[kChTile];
+  const long long pr = blockIdx.x / (bx + by);
+  const int r = static_cast<int>(blockIdx.x - pr * (bx + by));
+  const bool fwd = r < bx;                                       // workgroup-uniform
+  const int nq = fwd ? n : m, nt = fwd ? m : n;
+  const float* qs = (fwd ? x : y) + pr * nq * 3;
+  const float* ts = (fwd ? y : x) + pr * nt * 3;
+  int* oi = (fwd ? idx1 : idx2) + pr * nq;
+  float* od = (fwd ? d1 : d2) + pr * nq;
+  const int q0 = (fwd ? r : r - bx) * (kChThreads * Q) + threadIdx.x;
+
+  float qx[Q], qy[Q], qz[Q], best[Q];
+  int bi[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = min(q0 + q * kChThreads, nq - 1);              // lanes past the end repeat the last query
+    qx[q] = qs[3 * i]; qy[q] = qs[3 * i + 1]; qz[q] = qs[3 * i + 2];
+    best[q] = 3.0e38f; bi[q] = 0;
+  }
+  const bool wave_live = q0 - (threadIdx.x & 63) < nq;           // a wave with no query only helps staging
+  for (int t0 = 0; t0 < nt; t0 += kChTile) {
+    const int cnt = min(kChTile, nt - t0);
+    __syncthreads();
+    stage_tile(sT, ts, nullptr, t0, cnt);
+    __syncthreads();
+    if (!wave_live) continue;
+#pragma unroll 4
+    for (int j = 0; j < cnt; ++j) {
+      const float4 t = sT[j];
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const float dx = qx[q] - t.x, dy = qy[q] - t.y, dz = qz[q] - t.z;
+        const float d = dx * dx + dy * dy + dz * dz;
+        if (d < best[q]) { best[q] = d; bi[q] = t0 + j; }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = q0 + q * kChThreads;
+    if (i < nq) { od[i] = best[q]; oi[i] = bi[q]; }
+  }
+}
+
+__global__ __launch_bounds__(kChThreads) void chamfer_large_reduce_kernel(const float* __restrict__ d1,
+                                                                          const float* __restrict__ d2,
+                                                                          float* __restrict__ dist, int n, int m) {
+  __shared__ double s1[kChThreads], s2[kChThreads];
+  const long long pr = blockIdx.x;
+  const float* a = d1 + pr * n;
+  const float* b = d2 + pr * m;
+  double t1 = 0.0, t2 = 0.0;
+  for (int i = threadIdx.x; i < n; i += kChThreads) t1 += static_cast<double>(a[i]);
+  for (int j = threadIdx.x; j < m; j += kChThreads) t2 += static_cast<double>(b[j]);
+  s1[threadIdx.x] = t1; s2[threadIdx.x] = t2;
+  __syncthreads();
+  for (int w = kChThreads / 2; w >= 1; w >>= 1) {
+    if (threadIdx.x < w) { s1[threadIdx.x] += s1[threadIdx.x + w]; s2[threadIdx.x] += s2[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dist[pr] = static_cast<float>(s1[0] / n + s2[0] / m);
+}
+
+// Blocks [0, bx) of a pair write dx, blocks [bx, bx + by) dy; bx or by is 0 when that gradient is not wanted.
+template <int Q>
+__global__ __launch_bounds__(kChThreads) void chamfer_large_bwd_kernel(const float* __restrict__ x,
+                                                                       const float* __restrict__ y,
+                                                                       const float* __restrict__ ddist,
+                                                                       const int* __restrict__ idx1,
+                                                                       const int* __restrict__ idx2,
+                                                                       float* __restrict__ dx, float* __restrict__ dy,
+                                                                       int n, int m, int bx, int by) {
+  __shared__ float4 sT[kChTile];
+  const long long pr = blockIdx.x / (bx + by);
+  const int r = static_cast<int>(blockIdx.x - pr * (bx + by));
+  const bool forx = r < bx;
+  const int ns = forx ? n : m, no = forx ? m : n;                // own set, other set
+  const float* self = (forx ? x : y) + pr * ns * 3;
+  const float* other = (forx ? y : x) + pr * no * 3;
+  const int* near_other = (forx ? idx1 : idx2) + pr * ns;        // nearest of the other set, per own point
+  const int* near_self = (forx ? idx2 : idx1) + pr * no;         // nearest own point, per point of the other set
+  float* out = (forx ? dx : dy) + pr * ns * 3;
+  const int q0 = (forx ? r : r - bx) * (kChThreads * Q) + threadIdx.x;
+  const float g = ddist[pr];
+  const float k1 = 2.f * g / static_cast<float>(ns), k2 = 2.f * g / static_cast<float>(no);
+
+  float px[Q], py[Q], pz[Q], gx[Q], gy[Q], gz[Q];
+  int own[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = q0 + q * kChThreads;
+    const int ic = min(i, ns - 1);
+    own[q] = i < ns ? i : -1;                                    // -1 matches no index
+    px[q] = self[3 * ic]; py[q] = self[3 * ic + 1]; pz[q] = self[3 * ic + 2];
+    const int a = min(max(near_other[ic], 0), no - 1);           // an index from outside the forward stays in range
+    gx[q] = k1 * (px[q] - other[3 * a]); gy[q] = k1 * (py[q] - other[3 * a + 1]);
+    gz[q] = k1 * (pz[q] - other[3 * a + 2]);
+  }
+  const bool wave_live = q0 - (threadIdx.x & 63) < ns;
+  for (int t0 = 0; t0 < no; t0 += kChTile) {
+    const int cnt = min(kChTile, no - t0);
+    __syncthreads();
+    stage_tile(sT, other, near_self, t0, cnt);
+    __syncthreads();
+    if (!wave_live) continue;
+#pragma unroll 4
+    for (int j = 0; j < cnt; ++j) {
+      const float4 t = sT[j];
+      const int b = __builtin_bit_cast(int, t.w);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (b == own[q]) {
+          gx[q] += k2 * (px[q] - t.x); gy[q] += k2 * (py[q] - t.y); gz[q] += k2 * (pz[q] - t.z);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = q0 + q * kChThreads;
+    if (i < ns) { out[3 * i] = gx[q]; out[3 * i + 1] = gy[q]; out[3 * i + 2] = gz[q]; }
+  }
+}
+
+// Queries per thread: as many as still leave two workgroups per CU, and no more than the smaller set fills.
+inline int chamfer_large_q(long long pairs, int n, int m) {
+  for (int q = 4; q > 1; q >>= 1) {
+    const int per = kChThreads * q;
+    if (n >= per && m >= per && pairs * ((n + per - 1) / per + (m + per - 1) / per) >= 512) return q;
+  }
+  return 1;
+}
+
+// f(std::integral_constant<int, Q>{}) for the chosen Q
+template <typename F>
+inline void with_queries_per_thread(int q, F&& f) {
+  if (q == 4) f(std::integral_constant<int, 4>{});
+  else if (q == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 1>{});
+}
+
+// `queries`: 0 = chamfer_large_q's choice; 1, 2 or 4 force that kernel (parity tests)
+inline int chamfer_large_check(long long pairs, int n, int m, int queries) {
+  if (queries != 0 && queries != 1 && queries != 2 && queries != 4) return SIMAMBA_E_VARIANT;
+  if (pairs < 0 || n < 1 || m < 1 || n > kChMaxPoints || m > kChMaxPoints) return SIMAMBA_E_SHAPE;
+  return SIMAMBA_OK;
+}
+
+}  // namespace simamba
+
+using namespace simamba;
+
+extern "C" int simamba_chamfer_large_fwd_ex(const float* x, const float* y, float* dist, int* idx1, int* idx2,
+                                            float* d1, float* d2, long long pairs, int n, int m, int queries,
+                                            void* stream) {
+  if (const int rc = chamfer_large_check(pairs, n, m, queries)) return rc;
+  if (pairs == 0) return SIMAMBA_OK;
+  if (!x || !y || !dist || !idx1 || !idx2 || !d1 || !d2) return SIMAMBA_E_NULLPTR;
+  const int q = queries ? queries : chamfer_large_q(pairs, n, m), per = kChThreads * q;
+  const int bx = (n + per - 1) / per, by = (m + per - 1) / per;
+  const long long grid = pairs * (bx + by);
+  if (grid > 0x7fffffffll) return SIMAMBA_E_SHAPE;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 g(static_cast<unsigned>(grid)), b(kChThreads);
+  with_queries_per_thread(q, [&](auto tag) {
+    hipLaunchKernelGGL(chamfer_large_nn_kernel<decltype(tag)::value>, g, b, 0, st, x, y, idx1, idx2, d1, d2, n, m, bx,
+                       by);
+  });
+  if (const hipError_t e = hipGetLastError()) return static_cast<int>(e);
+  hipLaunchKernelGGL(chamfer_large_reduce_kernel, dim3(static_cast<unsigned>(pairs)), b, 0, st, d1, d2, dist, n, m);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_chamfer_large_fwd(const float* x, const float* y, float* dist, int* idx1, int* idx2, float* d1,
+                                         float* d2, long long pairs, int n, int m, void* stream) {
+  return simamba_chamfer_large_fwd_ex(x, y, dist, idx1, idx2, d1, d2, pairs, n, m, 0, stream);
+}
+
+extern "C" int simamba_chamfer_large_bwd_ex(const float* x, const float* y, const float* ddist, const int* idx1,
+                                            const int* idx2, float* dx, float* dy, long long pairs, int n, int m,
+                                            int queries, void* stream) {
+  if (const int rc = chamfer_large_check(pairs, n, m, queries)) return rc;
+  if (pairs == 0) return SIMAMBA_OK;
+  if (!x || !y || !ddist || !idx1 || !idx2) return SIMAMBA_E_NULLPTR;
+  if (!dx && !dy) return SIMAMBA_OK;
+  const int q = queries ? queries : chamfer_large_q(pairs, n, m), per = kChThreads * q;
+  const int bx = dx ? (n + per - 1) / per : 0, by = dy ? (m + per - 1) / per : 0;
+  const long long grid = pairs * (bx + by);
+  if (grid > 0x7fffffffll) return SIMAMBA_E_SHAPE;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 g(static_cast<unsigned>(grid)), b(kChThreads);
+  with_queries_per_thread(q, [&](auto tag) {
+    hipLaunchKernelGGL(chamfer_large_bwd_kernel<decltype(tag)::value>, g, b, 0, st, x, y, ddist, idx1, idx2, dx, dy, n,
+                       m, bx, by);
+  });
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int simamba_chamfer_large_bwd(const float* x, const float* y, const float* ddist, const int* idx1,
+                                         const int* idx2, float* dx, float* dy, long long pairs, int n, int m,
+                                         void* stream) {
+  return simamba_chamfer_large_bwd_ex(x, y, ddist, idx1, idx2, dx, dy, pairs, n, m, 0, stream);
+}

@@ -41,7 +41,13 @@ def default_mae_config(**over):
 
 
 # ---- Chamfer distance on the HIP kernels ----------------------------------------------------------------------------
+CHAMFER_SMALL_MAX = 64       # points per set of the one-wave kernels (csrc/chamfer.hip); the tiled ones take 8192
+
+
 class ChamferFn(torch.autograd.Function):
+    """Two routes.  Sets of up to 64 points whose ``gt`` needs no gradient (the MAE patch loss) run the one-wave
+    kernels; everything else, up to 8192 points per set, the tiled kernels, which also differentiate ``gt``."""
+
     @staticmethod
     def forward(ctx, pred, gt):
         _lib.require_gpu(pred, "chamfer_distance")
@@ -51,15 +57,29 @@ class ChamferFn(torch.autograd.Function):
         pairs, n, _ = p.shape
         m = g.shape[1]
         dev = p.device
+        ctx.small = n <= CHAMFER_SMALL_MAX and m <= CHAMFER_SMALL_MAX and not ctx.needs_input_grad[1]
+        ctx.in_dtype, ctx.gt_dtype = pred.dtype, gt.dtype
         dist = torch.empty(pairs, device=dev, dtype=torch.float32)
-        i1 = torch.empty(pairs, n, device=dev, dtype=torch.uint8)
-        i2 = torch.empty(pairs, m, device=dev, dtype=torch.uint8)
-        with torch.cuda.device(dev):
-            rc = lib.simamba_chamfer_fwd(p.data_ptr(), g.data_ptr(), dist.data_ptr(), i1.data_ptr(), i2.data_ptr(),
-                                         pairs, n, m, _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_chamfer_fwd")
+        if ctx.small:
+            _lib.count("chamfer_small")
+            i1 = torch.empty(pairs, n, device=dev, dtype=torch.uint8)
+            i2 = torch.empty(pairs, m, device=dev, dtype=torch.uint8)
+            with torch.cuda.device(dev):
+                rc = lib.simamba_chamfer_fwd(p.data_ptr(), g.data_ptr(), dist.data_ptr(), i1.data_ptr(), i2.data_ptr(),
+                                             pairs, n, m, _lib.stream_ptr(dev))
+            _lib.check(rc, "simamba_chamfer_fwd")
+        else:
+            _lib.count("chamfer_large")
+            i1 = torch.empty(pairs, n, device=dev, dtype=torch.int32)
+            i2 = torch.empty(pairs, m, device=dev, dtype=torch.int32)
+            d1 = torch.empty(pairs, n, device=dev, dtype=torch.float32)
+            d2 = torch.empty(pairs, m, device=dev, dtype=torch.float32)
+            with torch.cuda.device(dev):
+                rc = lib.simamba_chamfer_large_fwd(p.data_ptr(), g.data_ptr(), dist.data_ptr(), i1.data_ptr(),
+                                                   i2.data_ptr(), d1.data_ptr(), d2.data_ptr(), pairs, n, m,
+                                                   _lib.stream_ptr(dev))
+            _lib.check(rc, "simamba_chamfer_large_fwd")
         ctx.save_for_backward(p, g, i1, i2)
-        ctx.in_dtype = pred.dtype
         return dist
 
     @staticmethod
@@ -67,17 +87,27 @@ class ChamferFn(torch.autograd.Function):
         p, g, i1, i2 = ctx.saved_tensors
         lib = _lib.load()
         pairs, n, _ = p.shape
-        dp = torch.empty_like(p)
+        m = g.shape[1]
         dd = ddist.float().contiguous()
+        if ctx.small:
+            dp = torch.empty_like(p)
+            with torch.cuda.device(p.device):
+                rc = lib.simamba_chamfer_bwd(p.data_ptr(), g.data_ptr(), dd.data_ptr(), i1.data_ptr(), i2.data_ptr(),
+                                             dp.data_ptr(), pairs, n, m, _lib.stream_ptr(p.device))
+            _lib.check(rc, "simamba_chamfer_bwd")
+            return dp.to(ctx.in_dtype), None
+        dp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        dg = torch.empty_like(g) if ctx.needs_input_grad[1] else None
         with torch.cuda.device(p.device):
-            rc = lib.simamba_chamfer_bwd(p.data_ptr(), g.data_ptr(), dd.data_ptr(), i1.data_ptr(), i2.data_ptr(),
-                                         dp.data_ptr(), pairs, n, g.shape[1], _lib.stream_ptr(p.device))
-        _lib.check(rc, "simamba_chamfer_bwd")
-        return dp.to(ctx.in_dtype), None
+            rc = lib.simamba_chamfer_large_bwd(p.data_ptr(), g.data_ptr(), dd.data_ptr(), i1.data_ptr(), i2.data_ptr(),
+                                               _lib.ptr(dp), _lib.ptr(dg), pairs, n, m, _lib.stream_ptr(p.device))
+        _lib.check(rc, "simamba_chamfer_large_bwd")
+        return (None if dp is None else dp.to(ctx.in_dtype)), (None if dg is None else dg.to(ctx.gt_dtype))
 
 
 def chamfer_distance(pred, gt):
-    """(pairs, n, 3), (pairs, m, 3) -> (pairs,): pytorch3d ``chamfer_distance(..., batch_reduction=None)[0]``."""
+    """(pairs, n, 3), (pairs, m, 3) -> (pairs,): pytorch3d ``chamfer_distance(..., batch_reduction=None)[0]``, for
+    sets of up to 8192 points; both arguments are differentiable."""
     return ChamferFn.apply(pred, gt)
 
 
@@ -297,5 +327,33 @@ class Point_MAE_Mamba(nn.Module):
         gt = gt.reshape(B * Mtok, M, 3)
         loss = chamfer_distance(rebuild.float(), gt.float()).mean()
         if return_parts:
-            return loss, dict(enc, rebuild=rebuild, gt=gt, x_full=x_full)
+            return loss, dict(enc, rebuild=rebuild, gt=gt, x_full=x_full, neighborhood=neighborhood, center=center)
         return loss
+
+    @torch.no_grad()
+    def reconstruct(self, pts, mask=None):
+        """pts (B,N,3) -> (rebuilt, visible, loss_patches): what the model makes of the patches it did not see, as
+        whole clouds.  ``Mtok`` is the number of masked tokens per cloud -- every masked patch once per ordering
+        (``k_top_eigenvectors``, twice with ``reverse``), the decoder rebuilding each of them; with one ordering it is
+        the number ``nm`` of masked patches, and ``(G - nm)`` below is ``(G - Mtok)``.
+          rebuilt      (B, Mtok * M, 3)     the rebuilt masked patches moved back to their centres
+          visible      (B, (G - nm) * M, 3) the visible patches at their centres
+          loss_patches (B, Mtok)            the Chamfer loss of every rebuilt patch; its mean is forward()'s loss
+        The whole-cloud score of a pre-trained model in one line:
+          ``chamfer_distance(torch.cat([visible, rebuilt], 1), pts)``
+        ``mask`` (B,G) bool, the same number of True in every row, replaces the random mask.  Dropout and drop-path
+        follow the module's mode: call ``eval()`` first for a repeatable result.  Built on
+        ``forward(return_parts=True)``, whose dict carries ``neighborhood`` and ``center`` for this; the patch loss
+        runs once more here for its per-patch values (forward reduces it to the mean); clouds of one length only
+        (``lengths`` is refused by forward)."""
+        _, parts = self.forward(pts, mask=mask, return_parts=True)
+        neighborhood, center = parts["neighborhood"], parts["center"]
+        B, G, M, _ = neighborhood.shape
+        rebuild, src = parts["rebuild"].float(), parts["msk_src"]                 # (B * Mtok, M, 3), (B, Mtok)
+        Mtok = src.shape[1]
+        centre = torch.gather(center, 1, src.unsqueeze(-1).expand(-1, -1, 3))
+        rebuilt = (rebuild.view(B, Mtok, M, 3) + centre.unsqueeze(2)).reshape(B, Mtok * M, 3)
+        keep = ~parts["mask"]
+        visible = (neighborhood[keep] + center[keep].unsqueeze(1)).reshape(B, -1, 3)
+        loss_patches = chamfer_distance(rebuild, parts["gt"].float()).view(B, Mtok)
+        return rebuilt, visible, loss_patches

@@ -106,7 +106,8 @@ def _install_pytorch3d(_mod):
                          abs_cosine=True):
         if any(a is not None for a in (x_lengths, y_lengths, x_normals, y_normals, weights)) or norm != 2 \
                 or point_reduction != "mean" or single_directional:
-            raise NotImplementedError("chamfer_distance shim: equal-length clouds, squared L2, mean over points")
+            raise NotImplementedError("chamfer_distance shim: whole clouds of up to 8192 points (no per-cloud lengths, "
+                                      "normals or weights), squared L2, mean over points, both directions")
         d = mae.chamfer_distance(x, y)
         if batch_reduction == "mean":
             d = d.mean()
