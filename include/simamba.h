@@ -516,6 +516,32 @@ int simamba_chamfer_large_fwd_ex(const float* x, const float* y, float* dist, in
                                  float* d2, long long pairs, int n, int m, int queries, void* stream);
 int simamba_chamfer_large_bwd_ex(const float* x, const float* y, const float* ddist, const int* idx1, const int* idx2,
                                  float* dx, float* dy, long long pairs, int n, int m, int queries, void* stream);
+/*
+ * The same kernels for ragged batches (sets padded to a common n, m) and the rest of pytorch3d's arguments but normals.
+ *   xlen, ylen : (pairs) int32, device, or NULL (= n, m everywhere): pair p is the first xlen[p] points of x[p] against
+ *                the first ylen[p] of y[p]; nothing at or behind a length is read.  The kernels clamp the values to
+ *                [1, n] and [1, m]; the library never reads them on the host.  Every pair's outputs are what the pair
+ *                returns alone at its true lengths, bit for bit; rows behind a length are written as 0 (index 0).
+ *   norm       : 2 = squared L2 as above ; 1 = |dx| + |dy| + |dz|, gradient sign(a - b) per coordinate, sign(0) = 0.
+ *   reduction  : 0 mean: dist[p] = sum_i d1[p][i] / xlen[p] + sum_j d2[p][j] / ylen[p] ; 1 sum: no division ;
+ *                2 none: dist is not written and may be NULL, and the backward takes per-point upstream gradients
+ *                dd1 (pairs, n), dd2 (pairs, m) in place of ddist (pairs); whichever of the two is unused may be NULL.
+ *   flags      : bit 0 = one-way (x against y only): idx2, d2, dd2 are not touched and may be NULL, dist has the x term
+ *                only, dx has only the own-nearest term and dy only the reverse matches,
+ *                dy[j] = -k sum over {i : idx1[i] == j} of (x_i - y_j), ascending i.
+ *   queries    : as in the _ex forms.
+ * dx or dy may be NULL as above; rows behind a length get exactly 0.  No atomics: the same bits every time.
+ * Checks in the order variant (queries, norm, reduction, flags: SIMAMBA_E_VARIANT), shape, empty (pairs == 0:
+ * SIMAMBA_OK, nothing read), null pointers.  With xlen = ylen = NULL, norm 2, reduction 0 and flags 0 these are the _ex
+ * forms (which are that call).  Still ABI version 9: symbols added, none changed.
+ */
+int simamba_chamfer_ragged_fwd(const float* x, const float* y, const int* xlen, const int* ylen, float* dist,
+                               int* idx1, int* idx2, float* d1, float* d2, long long pairs, int n, int m, int norm,
+                               int reduction, int flags, int queries, void* stream);
+int simamba_chamfer_ragged_bwd(const float* x, const float* y, const int* xlen, const int* ylen, const float* ddist,
+                               const float* dd1, const float* dd2, const int* idx1, const int* idx2, float* dx,
+                               float* dy, long long pairs, int n, int m, int norm, int reduction, int flags,
+                               int queries, void* stream);
 
 /*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, spectral
+from . import _lib, grouping, spectral
 from .block import MixerModel
 from .point_mamba import Encoder, Group
 
@@ -105,10 +105,115 @@ class ChamferFn(torch.autograd.Function):
         return (None if dp is None else dp.to(ctx.in_dtype)), (None if dg is None else dg.to(ctx.gt_dtype))
 
 
-def chamfer_distance(pred, gt):
+_CHAMFER_REDUCTIONS = {"mean": 0, "sum": 1, None: 2}
+
+
+def _pair_lengths(t, pairs, device, what):
+    """A per-pair length argument as the tiled kernels read it: grouping._per_cloud's rules, then int32.  The kernels
+    clamp into [1, padded]; the clamp here only keeps 2^32 + 5 from becoming 5.  No host read."""
+    t = grouping._per_cloud(t, pairs, device, what)
+    return None if t is None else t.clamp(-1, 1 << 20).to(torch.int32)
+
+
+class ChamferRaggedFn(torch.autograd.Function):
+    """The tiled kernels with per-pair lengths, norm 1 or 2, mean / sum / no point reduction and one-way matching
+    (simamba_chamfer_ragged_*).  Returns dist (pairs,), or with no reduction d1 (pairs, n) and, unless one-way,
+    d2 (pairs, m)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, xlen, ylen, norm, reduction, one_way):
+        _lib.require_gpu(pred, "chamfer_distance")
+        lib = _lib.load()
+        _lib.count("chamfer_ragged")
+        p = pred.float().contiguous()
+        g = gt.detach().float().contiguous()
+        pairs, n, _ = p.shape
+        m = g.shape[1]
+        dev = p.device
+        ctx.in_dtype, ctx.gt_dtype = pred.dtype, gt.dtype
+        ctx.mode = (norm, reduction, int(one_way))
+        dist = torch.empty(pairs, device=dev, dtype=torch.float32) if reduction != 2 else None
+        i1 = torch.empty(pairs, n, device=dev, dtype=torch.int32)
+        d1 = torch.empty(pairs, n, device=dev, dtype=torch.float32)
+        i2 = None if one_way else torch.empty(pairs, m, device=dev, dtype=torch.int32)
+        d2 = None if one_way else torch.empty(pairs, m, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            rc = lib.simamba_chamfer_ragged_fwd(p.data_ptr(), g.data_ptr(), _lib.ptr(xlen), _lib.ptr(ylen),
+                                                _lib.ptr(dist), i1.data_ptr(), _lib.ptr(i2), d1.data_ptr(),
+                                                _lib.ptr(d2), pairs, n, m, norm, reduction, int(one_way), 0,
+                                                _lib.stream_ptr(dev))
+        _lib.check(rc, "simamba_chamfer_ragged_fwd")
+        ctx.save_for_backward(p, g, i1, i2, xlen, ylen)
+        if reduction != 2:
+            return dist
+        return d1 if one_way else (d1, d2)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        p, g, i1, i2, xlen, ylen = ctx.saved_tensors
+        norm, reduction, one_way = ctx.mode
+        lib = _lib.load()
+        pairs, n, _ = p.shape
+        m = g.shape[1]
+        up = [None if t is None else t.float().contiguous() for t in grads]
+        if reduction != 2:
+            dd, dd1, dd2 = up[0], None, None
+        else:
+            dd, dd1 = None, up[0]
+            dd2 = None if one_way else up[1]
+            if dd1 is None:
+                dd1 = torch.zeros(pairs, n, device=p.device, dtype=torch.float32)
+            if dd2 is None and not one_way:
+                dd2 = torch.zeros(pairs, m, device=p.device, dtype=torch.float32)
+        dp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        dg = torch.empty_like(g) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(p.device):
+            rc = lib.simamba_chamfer_ragged_bwd(p.data_ptr(), g.data_ptr(), _lib.ptr(xlen), _lib.ptr(ylen),
+                                                _lib.ptr(dd), _lib.ptr(dd1), _lib.ptr(dd2), i1.data_ptr(),
+                                                _lib.ptr(i2), _lib.ptr(dp), _lib.ptr(dg), pairs, n, m, norm, reduction,
+                                                one_way, 0, _lib.stream_ptr(p.device))
+        _lib.check(rc, "simamba_chamfer_ragged_bwd")
+        return (None if dp is None else dp.to(ctx.in_dtype)), (None if dg is None else dg.to(ctx.gt_dtype)), \
+            None, None, None, None, None
+
+
+def chamfer_distance(pred, gt, *, x_lengths=None, y_lengths=None, weights=None, norm=2, point_reduction="mean",
+                     single_directional=False):
     """(pairs, n, 3), (pairs, m, 3) -> (pairs,): pytorch3d ``chamfer_distance(..., batch_reduction=None)[0]``, for
-    sets of up to 8192 points; both arguments are differentiable."""
-    return ChamferFn.apply(pred, gt)
+    sets of up to 8192 points; both arguments are differentiable.
+
+    The keywords are pytorch3d's.  ``x_lengths`` / ``y_lengths`` (pairs,) integers: pair p is the first
+    ``x_lengths[p]`` points of ``pred[p]`` against the first ``y_lengths[p]`` of ``gt[p]`` (values outside [1, n] /
+    [1, m] are clamped by the kernel; the padding is never read).  ``norm`` 1 or 2; ``point_reduction`` "mean" (over
+    the real points), "sum" or None, which returns the per-point ``(cham_x (pairs, n), cham_y (pairs, m))`` with zeros
+    behind the lengths; ``single_directional`` drops the gt-to-pred term (``cham_y`` is None); ``weights`` (pairs,)
+    scales every pair and is differentiable.  Any of them takes the tiled kernels whatever the set sizes; without
+    them the call is what it always was.  No host read."""
+    if norm not in (1, 2):
+        raise ValueError(f"chamfer_distance: norm must be 1 or 2, got {norm!r}")
+    if point_reduction == "max":
+        raise NotImplementedError("chamfer_distance: point_reduction='max' is not built (mean, sum or None)")
+    if point_reduction not in _CHAMFER_REDUCTIONS:
+        raise ValueError(f"chamfer_distance: point_reduction must be 'mean', 'sum' or None, got {point_reduction!r}")
+    one_way = bool(single_directional)
+    pairs = pred.shape[0]
+    xlen = _pair_lengths(x_lengths, pairs, pred.device, "chamfer_distance: x_lengths")
+    ylen = _pair_lengths(y_lengths, pairs, pred.device, "chamfer_distance: y_lengths")
+    if weights is not None:
+        if not torch.is_tensor(weights) or weights.shape != (pairs,):
+            raise ValueError(f"chamfer_distance: weights must be a tensor of shape ({pairs},)")
+        if not weights.dtype.is_floating_point:
+            raise TypeError(f"chamfer_distance: weights must hold floats, got {weights.dtype}")
+    if xlen is None and ylen is None and weights is None and norm == 2 and point_reduction == "mean" and not one_way:
+        return ChamferFn.apply(pred, gt)
+    out = ChamferRaggedFn.apply(pred, gt, xlen, ylen, norm, _CHAMFER_REDUCTIONS[point_reduction], one_way)
+    if point_reduction is not None:
+        return out if weights is None else out * weights
+    cham_x, cham_y = (out, None) if one_way else out
+    if weights is not None:
+        cham_x = cham_x * weights[:, None]
+        cham_y = None if cham_y is None else cham_y * weights[:, None]
+    return cham_x, cham_y
 
 
 # ---- index arithmetic shared by encoder and decoder ---------------------------------------------------------------

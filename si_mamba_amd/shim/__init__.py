@@ -12,7 +12,9 @@ try/except falls back to plain ``nn.LayerNorm`` (the only path its configs use).
 three pytorch3d entry points the reference calls (models/point_mamba.py:24, :37;
 part_segmentation/models/pt_mamba.py:13): ``sample_farthest_points``, ``knn_points`` and ``chamfer_distance``,
 on the HIP kernels, with the call forms and return shapes the reference uses, plus the ``lengths`` /
-``random_start_point`` arguments of the first two for ragged batches (clouds padded to a common point count).
+``random_start_point`` arguments of the first two for ragged batches (clouds padded to a common point count), and
+everything but the normals of the third (``x_lengths`` / ``y_lengths``, ``weights``, ``norm``, ``point_reduction``,
+``single_directional``).
 """
 from __future__ import annotations
 
@@ -104,15 +106,33 @@ def _install_pytorch3d(_mod):
     def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
                          batch_reduction="mean", point_reduction="mean", norm=2, single_directional=False,
                          abs_cosine=True):
-        if any(a is not None for a in (x_lengths, y_lengths, x_normals, y_normals, weights)) or norm != 2 \
-                or point_reduction != "mean" or single_directional:
-            raise NotImplementedError("chamfer_distance shim: whole clouds of up to 8192 points (no per-cloud lengths, "
-                                      "normals or weights), squared L2, mean over points, both directions")
-        d = mae.chamfer_distance(x, y)
-        if batch_reduction == "mean":
-            d = d.mean()
-        elif batch_reduction == "sum":
+        """(loss, None); with ``point_reduction=None`` ((cham_x, cham_y), None), or (cham_x, None) when one-way."""
+        if x_normals is not None or y_normals is not None:
+            raise NotImplementedError("chamfer_distance shim: x_normals / y_normals are not built")
+        if batch_reduction not in ("mean", "sum", None):
+            raise ValueError(f"chamfer_distance shim: batch_reduction must be 'mean', 'sum' or None, got "
+                             f"{batch_reduction!r}")
+        if point_reduction is None and batch_reduction is not None:
+            raise ValueError("chamfer_distance shim: point_reduction=None needs batch_reduction=None")
+        extra = any(a is not None for a in (x_lengths, y_lengths, weights)) or norm != 2 \
+            or point_reduction != "mean" or single_directional
+        if extra and not (x.is_cuda and y.is_cuda):
+            raise NotImplementedError("chamfer_distance shim: lengths are taken by the HIP kernels only (a ROCm "
+                                      "device, sets of up to 8192 points), and so are weights, norm, "
+                                      "point_reduction and single_directional")
+        d = mae.chamfer_distance(x, y, x_lengths=x_lengths, y_lengths=y_lengths, weights=weights, norm=norm,
+                                 point_reduction=point_reduction, single_directional=single_directional)
+        if point_reduction is None:
+            return (d[0] if single_directional else d), None
+        if batch_reduction == "sum":
             d = d.sum()
+        elif batch_reduction == "mean":
+            if weights is None:
+                d = d.mean() if d.shape[0] else d.sum()              # the mean over max(P, 1) pairs
+            else:
+                total = weights.sum()
+                d = torch.where(total > 0, d.sum() / torch.where(total > 0, total, torch.ones_like(total)),
+                                torch.zeros_like(total))
         return d, None
 
     root3d = _mod("pytorch3d")

@@ -12,15 +12,26 @@ kernel's own share of peak, not that share; the kernel time is what a rocprofv3 
 
     python tools/bench_chamfer.py [--out profiles/chamfer_large.json]
 prints one JSON line and, with --out, writes it there.
+
+    python tools/bench_chamfer.py --ragged [--parent DIR] [--runs 5] [--out profiles/chamfer_ragged.json]
+times, at the same three shapes, the plain call, the ragged call (x_lengths / y_lengths) at full lengths and the ragged
+call with lengths spread over [n/2, n] and [m/2, m], next to the share of the n * m point pairs that remains.  DIR is a
+built checkout of the parent commit: its plain call is timed too, `runs` times in alternation with this tree, every
+run a fresh process, so that the two trees see the same machine in the same minutes.  Without --parent that
+comparison is reported as not measured.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--child" in sys.argv:                        # a timing process of --ragged: the tree whose package it imports
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--child") + 1])
+sys.path.insert(0, ROOT)
 from si_mamba_amd.mae import chamfer_distance  # noqa: E402
 
 SHAPES = [(64, 1024, 1024), (64, 2048, 1024), (16, 8192, 8192)]
@@ -60,12 +71,104 @@ def torch_form(x, y):
     return d.min(2)[0].mean(1) + d.min(1)[0].mean(1)
 
 
+def half_to_full(size, pairs, seed):
+    """`pairs` lengths spread evenly over [size / 2, size], both ends included, in a fixed shuffled order."""
+    ln = torch.linspace(size / 2, size, pairs).round().long()
+    return ln[torch.randperm(pairs, generator=torch.Generator().manual_seed(seed))]
+
+
+def ragged_child():
+    """One process of --ragged: the plain call of the tree it imported and, where that tree has them, the ragged calls.
+    Prints one JSON line."""
+    import inspect
+    dev = torch.device("cuda:0")
+    has_lengths = "x_lengths" in inspect.signature(chamfer_distance).parameters
+    rows = []
+    for pairs, n, m in SHAPES:
+        x, y = clouds(pairs, n, 1, dev), clouds(pairs, m, 2, dev)
+        w = torch.rand(pairs, device=dev)
+        modes = {"plain": {}}
+        if has_lengths:
+            nx, ny = half_to_full(n, pairs, 3), half_to_full(m, pairs, 4)
+            modes["ragged_full"] = dict(x_lengths=torch.full((pairs,), n, device=dev),
+                                        y_lengths=torch.full((pairs,), m, device=dev))
+            modes["ragged_half_to_full"] = dict(x_lengths=nx.to(dev), y_lengths=ny.to(dev))
+        row = dict(shape=[pairs, n, m])
+        for name, kw in modes.items():
+            def fwd_bwd():
+                xa, ya = x.detach().requires_grad_(), y.detach().requires_grad_()
+                (chamfer_distance(xa, ya, **kw) * w).sum().backward()
+
+            row[name + "_fwd_ms"] = round(timeit(lambda: chamfer_distance(x, y, **kw))[0], 4)
+            row[name + "_fwd_bwd_ms"] = round(timeit(fwd_bwd)[0], 4)
+        if has_lengths:
+            row["half_to_full_share_of_point_pairs"] = round(float((nx * ny).sum()) / (pairs * n * m), 4)
+            same = torch.equal(chamfer_distance(x, y), chamfer_distance(x, y, **modes["ragged_full"]))
+            row["ragged_full_equals_plain_bitwise"] = bool(same)
+        rows.append(row)
+    print(json.dumps(dict(tree=ROOT, device=torch.cuda.get_device_name(0), rows=rows)))
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def ragged_main(args):
+    """Alternate fresh timing processes of the parent tree and of this one; one JSON line of medians and every run."""
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    trees = ([("parent", os.path.abspath(args.parent))] if args.parent else []) + [("this", here)]
+    runs = {name: [] for name, _ in trees}
+    for r in range(args.runs):
+        for name, tree in trees:
+            print(f"run {r + 1} of {args.runs}: {name}", file=sys.stderr, flush=True)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", tree], check=True,
+                                 capture_output=True, text=True, timeout=600).stdout
+            runs[name].append(json.loads(out.strip().splitlines()[-1]))
+    rows = []
+    for i, shape in enumerate(SHAPES):
+        row = dict(shape=list(shape))
+        for name in runs:
+            for key in runs[name][0]["rows"][i]:
+                if key.endswith("_ms"):
+                    vals = [r["rows"][i][key] for r in runs[name]]
+                    row[f"{name}_{key}"] = dict(median=median(vals), runs=vals)
+                elif key != "shape":
+                    row[key] = runs[name][-1]["rows"][i][key]
+        for k in ("fwd_ms", "fwd_bwd_ms"):
+            plain = row[f"this_plain_{k}"]["median"]
+            if args.parent:
+                row[f"a_plain_over_parent_{k}"] = round(plain / row[f"parent_plain_{k}"]["median"], 4)
+            else:
+                row[f"a_plain_over_parent_{k}"] = "not measured (no --parent)"
+            row[f"b_ragged_full_over_plain_{k}"] = round(row[f"this_ragged_full_{k}"]["median"] / plain, 4)
+            row[f"c_ragged_half_to_full_over_plain_{k}"] = round(row[f"this_ragged_half_to_full_{k}"]["median"] / plain,
+                                                                 4)
+        rows.append(row)
+    line = json.dumps(dict(what="chamfer_distance, plain and ragged calls, fp32, one MI355X; call times (events around "
+                                "back-to-back calls, median of 5 windows of ~0.2 s) per process, then the median over "
+                                f"{args.runs} processes per tree, parent and this tree alternating",
+                           device=runs["this"][0]["device"], parent_measured=bool(args.parent), rows=rows))
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (with --ragged)")
+    ap.add_argument("--runs", type=int, default=5, help="timing processes per tree (with --ragged)")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.ragged and not args.child:
+        return ragged_main(args)                 # starts the timing processes; opens no device itself
     if not torch.cuda.is_available():
         raise SystemExit("bench_chamfer.py needs a ROCm device: a time from anything else says nothing")
+    if args.child:
+        return ragged_child()
     dev = torch.device("cuda:0")
     rows = []
     for pairs, n, m in SHAPES:
