@@ -43,13 +43,6 @@ struct LnArgs {
   float eps;
 };
 
-__device__ __forceinline__ float wave_allreduce_sum(float v) {
-  v = row_allreduce_sum(v);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
 template <typename T>
 __device__ __forceinline__ float4 ld4(const T* p) {
   const Pack<T, 4> pk = *reinterpret_cast<const Pack<T, 4>*>(p);

@@ -89,6 +89,13 @@ __device__ __forceinline__ float row_allreduce_sum(float v) {
   v += dpp<DPP_ROW_MIRROR>(0.f, v);
   return v;
 }
+// sum over the 64 lanes of a wave, result in every lane
+__device__ __forceinline__ float wave_allreduce_sum(float v) {
+  v = row_allreduce_sum(v);
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }

@@ -12,6 +12,7 @@
 // workspace, [batch slice][dim][width] (dw) and [batch slice][dim] (dbias); det_reduce.hip sums over the slices.
 // Algorithmic HBM bytes: fwd 2*B*D*L*s, bwd 3*B*D*L*s (+ (W+1)*D*4 parameters).
 #include "host_common.h"
+#include "mfma_device.h"
 #include "det_reduce.h"
 
 namespace simamba {
@@ -230,8 +231,8 @@ __device__ __forceinline__ void unpack16(const uint4& r, float (&v)[P]) {
     const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-      v[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
+      v[2 * i] = bf16_lo(w[i]);
+      v[2 * i + 1] = bf16_hi(w[i]);
     }
   }
 }

@@ -20,17 +20,10 @@
 //     in front of those of block j + 2; one barrier per block.
 //
 // One wave per SIMD (the B fragments alone are 192 registers), 256 workgroups at the model shape: one per CU, one round.
-#include <type_traits>
-
-#include "common.h"
+// The LDS reads that feed MFMAs and stores are lds_read16 / lds_wait of csrc/mfma_device.h, under the contract stated there.
+#include "mfma_device.h"
 
 namespace simamba {
-
-typedef float ip_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 ip_bf16x8 __attribute__((ext_vector_type(8)));
-// 16-byte register values as a NATIVE vector: HIP's ip_u4 is a struct whose copies hipcc lowers to memcpy between address
-// spaces, and an array of them that lives across loop iterations then stays in scratch memory instead of registers
-typedef unsigned ip_u4 __attribute__((ext_vector_type(4)));
 
 // Timing-only A/B switches (tools/build_alt.sh; the elimination numbers of DESIGN 4.10): -DIP_NOSTORE drops the global stores,
 // -DIP_NOWLOAD reloads W block 0 for every block, -DIP_NOMFMA issues one MFMA per block.  Outputs are wrong by construction.
@@ -43,32 +36,6 @@ constexpr int kIpCb = 32;            // output channels per block
 constexpr int kIpSets = SIMAMBA_INPROJ_SETS;
 constexpr int kIpTok = 128 * kIpSets;            // tokens per workgroup
 constexpr int kIpOPitch = kIpTok * 2 + 16;       // bytes per channel row of the output staging (+16: rows shift banks)
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void ip_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ip_static_for<I + 1, N>(f);
-  }
-}
-// A 16-byte LDS read the compiler can neither sink next to its use nor count: issued here, waited for by ip_lds_wait.
-// (Left to itself hipcc moved every A-fragment read directly in front of its MFMAs and waited lgkmcnt(0) each time --
-// one LDS latency per k step, 2.5 us per channel block at one wave per SIMD.)
-// Contract: the destination may only be READ through ip_lds_wait (which hands the compiler a new value): to hipcc the
-// register is defined the moment this statement issues.  A copy of it made before the wait -- a live-range split or a
-// spill into an AGPR under register pressure -- would copy stale contents; the current builds make none (checked in the
-// .s: every ds_read_b128 destination is next touched by the s_waitcnt statement or the MFMA behind it), and
-// tests/test_gpu_in_proj.py compares every output element on every build.
-template <int OFF>
-__device__ __forceinline__ void ip_lds_read16(ip_u4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-// LDS operations of a wave return in order: at most N of them still outstanding means every read older than the N youngest
-// has landed.  `v` ties the wait to the value about to be used.
-template <int N>
-__device__ __forceinline__ void ip_lds_wait(ip_u4& v) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-}
 
 struct IpArgs {
   const uint16_t* x;     // (batch, L, C)
@@ -103,13 +70,13 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
 
   // ---- B fragments: set u, k step s: x[b][t0 + 64 wave + 2 li + u][16 s + 8 hh .. + 7]; tokens past L read token L - 1
   // and are never stored ---------------------------------------------------------------------------------------------
-  ip_u4 bf[kIpSets][NS];
+  u32x4 bf[kIpSets][NS];
 #pragma unroll
   for (int u = 0; u < kIpSets; ++u) {
     const int t = t0 + 32 * kIpSets * wave + kIpSets * li + u;
     const uint16_t* row = p.x + (static_cast<size_t>(b) * L + (t < L ? t : L - 1)) * C + 8 * hh;
 #pragma unroll
-    for (int s = 0; s < NS; ++s) bf[u][s] = *reinterpret_cast<const ip_u4*>(row + 16 * s);
+    for (int s = 0; s < NS; ++s) bf[u][s] = *reinterpret_cast<const u32x4*>(row + 16 * s);
   }
 
   // ---- W block staging: chunk q = tid + 256 i of the block (row q / kChunks, chunk q % kChunks) -> LDS row-major with the
@@ -122,7 +89,7 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
     wsrc[i] = static_cast<unsigned>(r) * kRowB + 16u * c;
     wdst[i] = static_cast<unsigned>(r) * kWPitch + 16u * c;
   }
-  struct WS { ip_u4 v[kLd]; };
+  struct WS { u32x4 v[kLd]; };
   const unsigned char* wbase = reinterpret_cast<const unsigned char*>(p.w);
   auto load_w = [&](WS& st, int blk_) __attribute__((always_inline)) {                      // unconditional: a block past the end re-reads the last one
 #ifdef IP_NOWLOAD
@@ -132,11 +99,11 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
 #endif
     const unsigned char* src = wbase + static_cast<size_t>(blk) * kWBlk;
 #pragma unroll
-    for (int i = 0; i < kLd; ++i) st.v[i] = *reinterpret_cast<const ip_u4*>(src + wsrc[i]);
+    for (int i = 0; i < kLd; ++i) st.v[i] = *reinterpret_cast<const u32x4*>(src + wsrc[i]);
   };
   auto store_w = [&](const WS& st, int buf) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < kLd; ++i) *reinterpret_cast<ip_u4*>(&sW[buf][wdst[i]]) = st.v[i];
+    for (int i = 0; i < kLd; ++i) *reinterpret_cast<u32x4*>(&sW[buf][wdst[i]]) = st.v[i];
   };
   // A fragment of step s: row li, chunk 2 s + hh: a per-lane LDS address + the immediate 32 s (+ the buffer)
   const unsigned aaddr = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&sW[0][0])) +
@@ -148,7 +115,7 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
   uint16_t* const obase = p.xz + static_cast<size_t>(b) * M * L;
 
   // store-out of a parked block: chunk q = tid + 256 i of the [32 channels][tokens] image; the LDS reads are issued first
-  // (ip_lds_read16: asm, so the value must pass through ip_lds_wait before it is used), the stores some MFMAs later
+  // (lds_read16: asm, so the value must pass through lds_wait before it is used), the stores some MFMAs later
   constexpr int kNO = 2 * kIpSets;
   constexpr int kOBuf = kIpCb * kIpOPitch;
   unsigned oaddr[kNO];
@@ -161,38 +128,38 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
     oaddr[i] = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&sO[0][0])) +
                static_cast<unsigned>(orow[i]) * kIpOPitch + 16u * (q % (16 * kIpSets));
   }
-  auto out_read = [&](ip_u4 (&o)[kNO], auto buf_tag) __attribute__((always_inline)) {
+  auto out_read = [&](u32x4 (&o)[kNO], auto buf_tag) __attribute__((always_inline)) {
     constexpr int buf = decltype(buf_tag)::value;
 #pragma unroll
-    for (int i = 0; i < kNO; ++i) ip_lds_read16<buf * kOBuf>(o[i], oaddr[i]);
+    for (int i = 0; i < kNO; ++i) lds_read16<buf * kOBuf>(o[i], oaddr[i]);
   };
-  auto out_store = [&](ip_u4& v, int blk, int i) __attribute__((always_inline)) {
+  auto out_store = [&](u32x4& v, int blk, int i) __attribute__((always_inline)) {
 #ifdef IP_NOSTORE
     if (otok[i] < L && v.x == 0x12345678u)
 #else
     if (otok[i] < L)                                         // L % 8 == 0: a chunk is all in or all out
 #endif
-      *reinterpret_cast<ip_u4*>(obase + static_cast<size_t>(kIpCb * blk + orow[i]) * L + otok[i]) = v;
+      *reinterpret_cast<u32x4*>(obase + static_cast<size_t>(kIpCb * blk + orow[i]) * L + otok[i]) = v;
   };
   auto store_out = [&](int blk, auto buf_tag) __attribute__((always_inline)) {   // the unpipelined form (tail)
-    ip_u4 o[kNO];
+    u32x4 o[kNO];
     out_read(o, buf_tag);
 #pragma unroll
     for (int i = 0; i < kNO; ++i) {
-      ip_lds_wait<0>(o[i]);
+      lds_wait<0>(o[i]);
       out_store(o[i], blk, i);
     }
   };
 
   // park a finished block (rounded to bf16) channel-major: one (g, e) register pair = one dword per lane
   // (one set per wave: the neighbouring token sits in the neighbouring lane -- a quad_perm DPP read, even lanes write)
-  auto park = [&](const ip_f32x16 (&acc)[kIpSets], int buf, int i) __attribute__((always_inline)) {
+  auto park = [&](const f32x16 (&acc)[kIpSets], int buf, int i) __attribute__((always_inline)) {
     const int g = i >> 2, e = i & 3;
     const float lo = acc[0][4 * g + e];
     float hi;
     if constexpr (kIpSets == 2) hi = acc[kIpSets - 1][4 * g + e];
     else hi = dpp<0xb1>(lo, lo);                               // quad_perm [1, 0, 3, 2]: lane ^ 1
-    const unsigned v = static_cast<unsigned>(f32_to_bf16(lo)) | (static_cast<unsigned>(f32_to_bf16(hi)) << 16);
+    const unsigned v = bf16_pack2(lo, hi);
     if (kIpSets == 2 || (li & 1) == 0)
       *reinterpret_cast<unsigned*>(&sO[buf][ooff + static_cast<unsigned>(8 * g + e) * kIpOPitch]) = v;
   };
@@ -206,40 +173,40 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
   // (the two register sets -- accumulators and W stages -- are indexed by a compile-time parity: handed around as
   // references they ended up behind a run-time pointer, i.e. in scratch memory)
   WS st[2];
-  ip_f32x16 acc2[2][kIpSets];
+  f32x16 acc2[2][kIpSets];
   auto block = [&](int blk, auto par_tag) __attribute__((always_inline)) {
     constexpr int P = decltype(par_tag)::value;              // = blk & 1
-    ip_f32x16 (&acc)[kIpSets] = acc2[P];
-    const ip_f32x16 (&prev)[kIpSets] = acc2[P ^ 1];
+    f32x16 (&acc)[kIpSets] = acc2[P];
+    const f32x16 (&prev)[kIpSets] = acc2[P ^ 1];
     WS& stg = st[P ^ 1];                                     // holds W block blk + 1
     constexpr int buf = P;
     constexpr bool kSpread = NS >= kLd + kNO + 6;            // room to hand the side work out one piece per step
     const bool so = blk > 1;
-    ip_u4 o[kNO];
+    u32x4 o[kNO];
 #pragma unroll
     for (int u = 0; u < kIpSets; ++u)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[u][i] = 0.f;
-    ip_u4 a[NS];
-    ip_static_for<0, (kAhead < NS ? kAhead : NS)>([&](auto sc) {
+    u32x4 a[NS];
+    static_for<0, (kAhead < NS ? kAhead : NS)>([&](auto sc) {
       constexpr int S = decltype(sc)::value;
-      ip_lds_read16<buf * kWBuf + 32 * S>(a[S], aaddr);
+      lds_read16<buf * kWBuf + 32 * S>(a[S], aaddr);
     });
     if (!kSpread && so) store_out(blk - 2, par_tag);         // block blk - 2, parked in sO[buf] during block blk - 1
-    ip_static_for<0, NS>([&](auto sc) {
+    static_for<0, NS>([&](auto sc) {
       constexpr int S = decltype(sc)::value;
       // reads S + 1 .. min(S + kAhead, NS) - 1 may still be in flight (plus whatever the compiler has issued since: the
       // count is then merely stricter)
       constexpr int kInFlight = (S + kAhead < NS ? kAhead : NS - S) - 1;
-      ip_lds_wait<kInFlight>(a[S]);
+      lds_wait<kInFlight>(a[S]);
 #ifdef IP_NOMFMA
       if (S == 0)
 #endif
 #pragma unroll
       for (int u = 0; u < kIpSets; ++u)
-        acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ip_bf16x8, a[S]),
-                                                         __builtin_bit_cast(ip_bf16x8, bf[u][S]), acc[u], 0, 0, 0);
-      if constexpr (S + kAhead < NS) ip_lds_read16<buf * kWBuf + 32 * (S + kAhead)>(a[S + kAhead], aaddr);
+        acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[S]),
+                                                         __builtin_bit_cast(bf16x8, bf[u][S]), acc[u], 0, 0, 0);
+      if constexpr (S + kAhead < NS) lds_read16<buf * kWBuf + 32 * (S + kAhead)>(a[S + kAhead], aaddr);
       if (blk > 0) {                                           // 16 dwords of the previous block over the first steps
         constexpr int kPer = (16 + NS - 1) / NS;
 #pragma unroll
@@ -251,7 +218,7 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
         // piece per step, then the request for block blk + 3 into the same registers
         constexpr int kW0 = NS - 2 - kLd;
         if constexpr (S >= kW0 && S < kW0 + kLd)
-          *reinterpret_cast<ip_u4*>(&sW[buf ^ 1][wdst[S - kW0]]) = stg.v[S - kW0];
+          *reinterpret_cast<u32x4*>(&sW[buf ^ 1][wdst[S - kW0]]) = stg.v[S - kW0];
         if constexpr (S == kW0 + kLd) load_w(stg, blk + 3);
         // The stores of block blk - 2 go LAST: hipcc cannot count VMEM operations across the loop's back edge and waits
         // for all but the youngest few before it touches the W registers above -- with this block's stores already in
@@ -266,7 +233,7 @@ __global__ __launch_bounds__(kIpThreads, kIpSets == 1 ? 2 : 1) void in_proj_bf16
           if (so) {
 #pragma unroll
             for (int i = 0; i < kNO; ++i) {
-              ip_lds_wait<0>(o[i]);
+              lds_wait<0>(o[i]);
               out_store(o[i], blk - 2, i);
             }
           }

@@ -27,37 +27,16 @@
 // it; the library's kernel is hand-scheduled assembly at 0.92 of the pipe.  Kept as an explicit, parity-tested variant
 // (tests/test_gpu_in_proj.py; _lib.hand_in_proj(True) selects it).
 //
-// The A-fragment LDS reads are inline asm with counted waits for the reason given in csrc/in_proj_bf16.hip (hipcc sinks
-// them in front of their MFMAs otherwise); same contract: a read's destination is only used through ipf_lds_wait.
-#include <type_traits>
-
-#include "common.h"
+// The A-fragment LDS reads are lds_read16 / lds_wait of csrc/mfma_device.h (inline asm with counted waits: hipcc sinks
+// them in front of their MFMAs otherwise), under the contract stated there.
+#include "mfma_device.h"
 
 namespace simamba {
-
-typedef float ipf_f32x16 __attribute__((ext_vector_type(16)));
-typedef float ipf_f4 __attribute__((ext_vector_type(4)));        // native vectors: see csrc/in_proj_bf16.hip (no uint4)
 
 constexpr int kIpfThreads = 256;
 constexpr int kIpfTok = 128;         // tokens per workgroup
 constexpr int kIpfCb = 32;           // output channels per block
 constexpr int kIpfOPitch = kIpfTok * 4 + 16;     // bytes per channel row of the output staging
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void ipf_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ipf_static_for<I + 1, N>(f);
-  }
-}
-template <int OFF>
-__device__ __forceinline__ void ipf_lds_read16(ipf_f4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ipf_lds_wait(ipf_f4& v) {
-  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-}
 
 struct IpfArgs {
   const float* x;        // (batch, L, C)
@@ -95,12 +74,12 @@ __global__ __launch_bounds__(kIpfThreads, 1) void in_proj_f32_kernel(IpfArgs p) 
   const int nblk = M / kIpfCb;
 
   // ---- B fragments: group g: x[b][t0 + 32 wave + li][8 g + 4 hh .. + 3]; tokens past L read token L - 1, never stored
-  ipf_f4 bq[NG];
+  f32x4 bq[NG];
   {
     const int t = t0 + 32 * wave + li;
     const float* row = p.x + (static_cast<size_t>(b) * L + (t < L ? t : L - 1)) * C + 4 * hh;
 #pragma unroll
-    for (int g = 0; g < NG; ++g) bq[g] = *reinterpret_cast<const ipf_f4*>(row + 8 * g);
+    for (int g = 0; g < NG; ++g) bq[g] = *reinterpret_cast<const f32x4*>(row + 8 * g);
   }
 
   // ---- W block staging: piece i = chunk q = tid + 256 i of the block (row q / kChunks, chunk q % kChunks)
@@ -129,26 +108,26 @@ __global__ __launch_bounds__(kIpfThreads, 1) void in_proj_f32_kernel(IpfArgs p) 
     oaddr[i] = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&sO[0][0])) +
                static_cast<unsigned>(orow[i]) * kIpfOPitch + 16u * (q % (kIpfTok / 4));
   }
-  auto out_store = [&](ipf_f4& v, int blk, int i) __attribute__((always_inline)) {
+  auto out_store = [&](f32x4& v, int blk, int i) __attribute__((always_inline)) {
     if (otok[i] < L)                                         // L % 4 == 0: a chunk is all in or all out
-      *reinterpret_cast<ipf_f4*>(obase + static_cast<size_t>(kIpfCb * blk + orow[i]) * L + otok[i]) = v;
+      *reinterpret_cast<f32x4*>(obase + static_cast<size_t>(kIpfCb * blk + orow[i]) * L + otok[i]) = v;
   };
-  auto park = [&](const ipf_f32x16& acc, int buf, int i) __attribute__((always_inline)) {
+  auto park = [&](const f32x16& acc, int buf, int i) __attribute__((always_inline)) {
     const int gg = i >> 2, e = i & 3;
     *reinterpret_cast<float*>(&sO[buf][ooff + static_cast<unsigned>(8 * gg + e) * kIpfOPitch]) = acc[i];
   };
 
   // prologue: W block 0 into buffer 0
   {
-    ipf_f4 v[kLd];
+    f32x4 v[kLd];
 #pragma unroll
-    for (int i = 0; i < kLd; ++i) v[i] = *reinterpret_cast<const ipf_f4*>(wbase + wsrc[i]);
+    for (int i = 0; i < kLd; ++i) v[i] = *reinterpret_cast<const f32x4*>(wbase + wsrc[i]);
 #pragma unroll
-    for (int i = 0; i < kLd; ++i) *reinterpret_cast<ipf_f4*>(&sW[0][wdst[i]]) = v[i];
+    for (int i = 0; i < kLd; ++i) *reinterpret_cast<f32x4*>(&sW[0][wdst[i]]) = v[i];
   }
   __syncthreads();
 
-  ipf_f32x16 acc2[2];
+  f32x16 acc2[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc2[1][i] = 0.f;
 
@@ -157,42 +136,42 @@ __global__ __launch_bounds__(kIpfThreads, 1) void in_proj_f32_kernel(IpfArgs p) 
   // block blk - 1 (accumulators acc2[P ^ 1]) into sO[P ^ 1], and at the end the stores of block blk - 2 from sO[P].
   auto block = [&](int blk, auto par_tag) __attribute__((always_inline)) {
     constexpr int P = decltype(par_tag)::value;
-    ipf_f32x16& acc = acc2[P];
-    const ipf_f32x16& prev = acc2[P ^ 1];
+    f32x16& acc = acc2[P];
+    const f32x16& prev = acc2[P ^ 1];
     const bool so = blk > 1;
     const bool more = blk + 1 < nblk;
     const unsigned char* wnext = wbase + static_cast<size_t>(more ? blk + 1 : blk) * kWBlk;   // (re-read, unused, at the end)
     constexpr int kG0 = NG / kNB;                            // groups between batches
     constexpr int kLag = kG0 - 2 > 0 ? kG0 - 2 : 1;
-    ipf_f4 o[kNO];
+    f32x4 o[kNO];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    ipf_f4 a[NG];
-    ipf_f4 wv[kBatch];
-    ipf_static_for<0, kAhead>([&](auto gc) {
+    f32x4 a[NG];
+    f32x4 wv[kBatch];
+    static_for<0, kAhead>([&](auto gc) {
       constexpr int G = decltype(gc)::value;
-      ipf_lds_read16<P * kWBuf + 32 * G>(a[G], aaddr);
+      lds_read16<P * kWBuf + 32 * G>(a[G], aaddr);
     });
-    ipf_static_for<0, NG>([&](auto gc) {
+    static_for<0, NG>([&](auto gc) {
       constexpr int G = decltype(gc)::value;
       constexpr int kInFlight = (G + kAhead < NG ? kAhead : NG - G) - 1;
-      ipf_lds_wait<kInFlight>(a[G]);
+      lds_wait<kInFlight>(a[G]);
       // (one accumulation chain: two chains over even / odd k groups, summed at the end, measured the same)
 #pragma unroll
       for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[G][m], bq[G][m], acc, 0, 0, 0);
-      if constexpr (G + kAhead < NG) ipf_lds_read16<P * kWBuf + 32 * (G + kAhead)>(a[G + kAhead], aaddr);
+      if constexpr (G + kAhead < NG) lds_read16<P * kWBuf + 32 * (G + kAhead)>(a[G + kAhead], aaddr);
       // W block blk + 1: batch n = pieces kBatch n .. of it
       if constexpr (G % kG0 == 0 && G / kG0 < kNB) {
         constexpr int n = G / kG0;
 #pragma unroll
         for (int j = 0; j < kBatch; ++j)
-          if (kBatch * n + j < kLd) wv[j] = *reinterpret_cast<const ipf_f4*>(wnext + wsrc[kBatch * n + j]);
+          if (kBatch * n + j < kLd) wv[j] = *reinterpret_cast<const f32x4*>(wnext + wsrc[kBatch * n + j]);
       }
       if constexpr (G % kG0 == kLag && G / kG0 < kNB) {
         constexpr int n = G / kG0;
 #pragma unroll
         for (int j = 0; j < kBatch; ++j)
-          if (kBatch * n + j < kLd) *reinterpret_cast<ipf_f4*>(&sW[P ^ 1][wdst[kBatch * n + j]]) = wv[j];
+          if (kBatch * n + j < kLd) *reinterpret_cast<f32x4*>(&sW[P ^ 1][wdst[kBatch * n + j]]) = wv[j];
       }
       // the accumulator registers of block blk - 1, one (or, for a short K, a few) per group
       if constexpr (G >= 1) {
@@ -209,14 +188,14 @@ __global__ __launch_bounds__(kIpfThreads, 1) void in_proj_f32_kernel(IpfArgs p) 
       if constexpr (G == NG - 3) {
         if (so) {
 #pragma unroll
-          for (int i = 0; i < kNO; ++i) ipf_lds_read16<P * kOBuf>(o[i], oaddr[i]);
+          for (int i = 0; i < kNO; ++i) lds_read16<P * kOBuf>(o[i], oaddr[i]);
         }
       }
       if constexpr (G == NG - 1) {
         if (so) {
 #pragma unroll
           for (int i = 0; i < kNO; ++i) {
-            ipf_lds_wait<0>(o[i]);
+            lds_wait<0>(o[i]);
             out_store(o[i], blk - 2, i);
           }
         }
@@ -234,12 +213,12 @@ __global__ __launch_bounds__(kIpfThreads, 1) void in_proj_f32_kernel(IpfArgs p) 
   const int last = nblk - 1;
   auto store_parked = [&](int blk, auto buf_tag) __attribute__((always_inline)) {
     constexpr int buf = decltype(buf_tag)::value;
-    ipf_f4 o[kNO];
+    f32x4 o[kNO];
 #pragma unroll
-    for (int i = 0; i < kNO; ++i) ipf_lds_read16<buf * kOBuf>(o[i], oaddr[i]);
+    for (int i = 0; i < kNO; ++i) lds_read16<buf * kOBuf>(o[i], oaddr[i]);
 #pragma unroll
     for (int i = 0; i < kNO; ++i) {
-      ipf_lds_wait<0>(o[i]);
+      lds_wait<0>(o[i]);
       out_store(o[i], blk, i);
     }
   };

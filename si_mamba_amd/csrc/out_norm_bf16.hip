@@ -23,12 +23,10 @@
 // which delivers ~70 GB/s per CU (MI355X_MICROARCH.md, 'Indexed rows'): at 64 tokens per workgroup that stream alone
 // was 45 us of a 85 us main loop at the model shape (measured by loading W once instead: tools/bench_out_norm.py), at
 // 128 it is half of that and about the MFMA time.
-#include "common.h"
+#include "mfma_device.h"
 
 namespace simamba {
 
-typedef float on_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 on_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short on_s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kOnThreads = 512;
@@ -51,20 +49,6 @@ struct OnArgs {
   int batch, K, L, C;
   float eps;
 };
-
-using on_rsrc_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ on_rsrc_t on_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
-}
-__device__ __forceinline__ uint4 on_bload16(on_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float on_wave_sum(float v) {
-  v = row_allreduce_sum(v);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
 
 // CB: 16-channel blocks per wave (C = 128 CB); TO: type of `normed`; kRms: RMSNorm epilogue (SIMAMBA_NORM_RMS, the
 // arithmetic of add_ln_fwd_kernel<.., true>: no mean, no beta, `mean` not written)
@@ -89,10 +73,10 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
   // 64-byte image row the two 16-token halves are swapped for rows with bit 4 of d set, so that the two 16-lane groups
   // of one transposing read pass (rows 16 apart = 1 KiB = the same banks) fall into different halves.
   const int yd = tid >> 4, yt = 8 * (tid & 15);
-  const on_rsrc_t rs_y = on_rsrc(p.y + static_cast<size_t>(b) * K * L, static_cast<unsigned>(K) * L * 2u);
+  const rsrc_t rs_y = make_rsrc(p.y + static_cast<size_t>(b) * K * L, static_cast<unsigned>(K) * L * 2u);
   const bool yin = t0 + yt < L;                                // L % 8 == 0
-  const unsigned yvoff0 = yin ? (static_cast<unsigned>(yd) * L + t0 + yt) * 2u : 0xfffff000u;
-  const unsigned yvoff1 = yin ? (static_cast<unsigned>(yd + 32) * L + t0 + yt) * 2u : 0xfffff000u;
+  const unsigned yvoff0 = yin ? (static_cast<unsigned>(yd) * L + t0 + yt) * 2u : kOob;
+  const unsigned yvoff1 = yin ? (static_cast<unsigned>(yd + 32) * L + t0 + yt) * 2u : kOob;
   uint16_t* const ydst0 =
       &sY[0][(yt >> 5) * kOnImg + yd * 32 + (((((yt >> 4) & 1) ^ ((yd >> 4) & 1))) << 4) + (yt & 15)];
   constexpr int kYBuf = 4 * kOnImg;                            // elements per buffer
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
   const int troff0 = (16 * q + tqq) * 32 + ((q & 1) << 4) + 4 * tpp;          // even token blocks (half 0 ^ (q & 1))
   const int troff1 = (16 * q + tqq) * 32 + (((q & 1) ^ 1) << 4) + 4 * tpp;    // odd token blocks
 
-  on_f32x4 acc[CB][kTB];
+  f32x4 acc[CB][kTB];
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -136,8 +120,8 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
   };
   auto load_y = [&](YF& y, int ks) {                          // out-of-range steps: an out-of-range offset (zeros)
     const unsigned so = static_cast<unsigned>(ks < nk ? ks : 0) * ystep;
-    y.v[0] = on_bload16(rs_y, ks < nk ? yvoff0 : 0xfffff000u, so);
-    y.v[1] = on_bload16(rs_y, ks < nk ? yvoff1 : 0xfffff000u, so);
+    y.v[0] = bload16<uint4>(rs_y, ks < nk ? yvoff0 : kOob, so);
+    y.v[1] = bload16<uint4>(rs_y, ks < nk ? yvoff1 : kOob, so);
   };
   auto store_y = [&](const YF& y, int buf) {
     *reinterpret_cast<uint4*>(ydst0 + buf * kYBuf) = y.v[0];
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
     for (int m = 0; m < 2; ++m) {
 #pragma unroll
       for (int th = 0; th < 2; ++th) {                         // four token blocks at a time (16 fragment registers)
-        on_bf16x8 bf[4];
+        bf16x8 bf[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int tb = 4 * th + j;
@@ -159,14 +143,14 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
           const on_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
               (on_s16x4 __attribute__((address_space(3)))*)(a0 + 4 * 32));
           const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-          bf[j] = __builtin_bit_cast(on_bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
+          bf[j] = __builtin_bit_cast(bf16x8, make_uint4(l2.x, l2.y, h2.x, h2.y));
         }
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             acc[cb][4 * th + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                __builtin_bit_cast(on_bf16x8, w.f[cb][m]), bf[j], acc[cb][4 * th + j], 0, 0, 0);
+                __builtin_bit_cast(bf16x8, w.f[cb][m]), bf[j], acc[cb][4 * th + j], 0, 0, 0);
       }
     }
   };
@@ -225,10 +209,8 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
 #pragma unroll
     for (int tb = 0; tb < kTB; ++tb) {
       const int c = 16 * (CB * wave + cb) + 4 * q;
-      const unsigned lo = static_cast<unsigned>(f32_to_bf16(acc[cb][tb][0])) |
-                          (static_cast<unsigned>(f32_to_bf16(acc[cb][tb][1])) << 16);
-      const unsigned hi = static_cast<unsigned>(f32_to_bf16(acc[cb][tb][2])) |
-                          (static_cast<unsigned>(f32_to_bf16(acc[cb][tb][3])) << 16);
+      const unsigned lo = bf16_pack2(acc[cb][tb][0], acc[cb][tb][1]);
+      const unsigned hi = bf16_pack2(acc[cb][tb][2], acc[cb][tb][3]);
       *reinterpret_cast<uint2*>(&sH[(16 * tb + li) * kHP + c]) = make_uint2(lo, hi);
     }
   __syncthreads();
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
           x[k] = make_float4(0, 0, 0, 0);
         }
       }
-      const float mean = kRms ? 0.f : on_wave_sum(sum) * inv_dim;
+      const float mean = kRms ? 0.f : wave_allreduce_sum(sum) * inv_dim;
       float sq = 0.f;
 #pragma unroll
       for (int k = 0; k < kChunks; ++k) {
@@ -282,7 +264,7 @@ __global__ __launch_bounds__(kOnThreads, 2) void out_proj_add_ln_kernel(OnArgs p
           sq += (a * a + bb * bb) + (cc * cc + d * d);
         }
       }
-      const float rstd = rsqrtf(on_wave_sum(sq) * inv_dim + p.eps);
+      const float rstd = rsqrtf(wave_allreduce_sum(sq) * inv_dim + p.eps);
 #pragma unroll
       for (int k = 0; k < kChunks; ++k) {
         const int c = lane + 64 * k;

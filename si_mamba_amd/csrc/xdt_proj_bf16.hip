@@ -1,5 +1,5 @@
-// bf16 form of the fused conv1d + SiLU -> x_proj -> dt_proj kernel (xdt_proj.hip holds the fp32 form and the story of
-// the schedule): bf16 operands and results, v_mfma_f32_32x32x16_bf16, fp32 accumulation.
+// bf16 form of the fused conv1d + SiLU -> x_proj -> dt_proj kernel (xdt_proj.hip holds the fp32 form, xdt_walk.h the
+// walk and the story of the schedule): bf16 operands and results, v_mfma_f32_32x32x16_bf16, fp32 accumulation.
 //
 // What the reference's mixer does under torch.autocast (tools/runner_pretrain.py:243; upstream mamba_inner_fn reached
 // from models/block.py:72): the conv output, x_dbl and delta are bf16 tensors, each product accumulates in fp32 and
@@ -17,13 +17,9 @@
 //   * delta leaves as 2-byte stores, 32 lanes on 64 contiguous bytes of a row (the other half of the line follows from
 //     the unit of the neighbouring token block, two iterations later).
 // A step moves half the bytes of the fp32 form and needs an eighth of its MFMAs; registers allow 3 workgroups per CU.
-#include "common.h"
-#include <type_traits>
+#include "xdt_walk.h"
 
 namespace simamba {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kHThreads = 256;
 constexpr int kHTok = 64;           // tokens per tile
@@ -32,7 +28,6 @@ constexpr int kHXP = kHTok;         // x tile pitch (bf16 elements): 128-byte ro
 constexpr int kHWP = kHKS + 8;      // Wx tile pitch: 80 bytes
 constexpr int kHDP = 32 + 8;        // dt image pitch: 80 bytes
 constexpr int kHMaxDConv = 1024;
-constexpr unsigned kHOob = 0xfffff000u;
 
 struct XdtHArgs {
   const uint16_t* x;      // (batch, D, L) bf16; with kConv the conv INPUT
@@ -47,31 +42,9 @@ struct XdtHArgs {
   long long x_bs;
 };
 
-using hrsrc_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ hrsrc_t hmake_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
-}
-using hvec4_t = decltype(__builtin_amdgcn_raw_buffer_load_b128(hmake_rsrc(nullptr, 0u), 0u, 0u, 0));
-using hvec2_t = decltype(__builtin_amdgcn_raw_buffer_load_b64(hmake_rsrc(nullptr, 0u), 0u, 0u, 0));
-__device__ __forceinline__ uint4 hload16(hrsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ void hstore16(uint4 v, hrsrc_t r, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(hvec4_t, v), r, voff, soff, 0);
-}
-__device__ __forceinline__ void hstore2(unsigned short v, hrsrc_t r, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_buffer_store_b16(v, r, voff, soff, 0);
-}
-__device__ __forceinline__ float hlo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float hhi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ unsigned hpack(float a, float b) {
-  return static_cast<unsigned>(f32_to_bf16(a)) | (static_cast<unsigned>(f32_to_bf16(b)) << 16);
-}
 __device__ __forceinline__ unsigned hdpp_prev(unsigned v) {
   return static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), DPP_ROW_SHR + 1, 0xf, 0xf, false));
 }
-
-struct HCursor { int j, ks, q, r; };
 
 template <bool kConv>
 __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p) {
@@ -86,15 +59,12 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
   const int li = lane & 31, hh = lane >> 5;
   const int sblk = wave & 1, tblk = wave >> 1;
   const int D = p.D, L = p.L, S = p.S, R = p.R;
-  const int tps = __builtin_amdgcn_readfirstlane((L + kHTok - 1) / kHTok);
-  const int ntiles = p.batch * tps;
+  const XdtWalk w = xdt_walk(p.batch, (L + kHTok - 1) / kHTok, D / kHKS);   // steps per tile: even (host: D % 64 == 0)
+  if (w.ntw <= 0) return;
+  const int nk = w.nk, tps = w.tps, ntw = w.ntw;
   const int nwg = static_cast<int>(gridDim.x), wg = static_cast<int>(blockIdx.x);
-  const int ntw = __builtin_amdgcn_readfirstlane((ntiles - wg + nwg - 1) / nwg);
-  if (ntw <= 0) return;
-  const int nk = D / kHKS;                                 // even (host: D % 64 == 0)
   const int ndb = D / 32;
   const int nunits = wave < ndb ? 2 * ((ndb - wave + 3) / 4) : 0;
-  const int gq = __builtin_amdgcn_readfirstlane(nwg / tps), gr = nwg - gq * tps;
   const unsigned sample_bytes = static_cast<unsigned>(D) * static_cast<unsigned>(L) * 2u;
 
   for (int i = tid; i < kHTok * kHDP; i += kHThreads) sDt[i] = 0;
@@ -106,56 +76,35 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
   }
   __syncthreads();
 
-  auto advance = [&](HCursor& c, int n) {
-    c.ks += n;
-    const bool wrap = c.ks >= nk;
-    c.ks -= wrap ? nk : 0;
-    c.j += wrap ? 1 : 0;
-    c.r += wrap ? gr : 0;
-    c.q += wrap ? gq : 0;
-    const bool carry = c.r >= tps;
-    c.r -= carry ? tps : 0;
-    c.q += carry ? 1 : 0;
-  };
-
   // ---- staging identities: x tile 32 d x 64 t = 256 packs of 8; thread -> (d = tid >> 3, t8 = 8 (tid & 7)) -----------
   const int xd = tid >> 3, xt = 8 * (tid & 7);
   const bool first = (tid & 7) == 0;
   const unsigned xoff = (static_cast<unsigned>(xd) * L + xt) * 2u;
   // Wx tile 64 s x 32 d = 256 packs of 8; thread -> (s = tid >> 2, d8 = 8 (tid & 3))
   const int ws = tid >> 2, wd = 8 * (tid & 3);
-  const unsigned woff = ws < S ? (static_cast<unsigned>(ws) * D + wd) * 2u : kHOob;
-  const hrsrc_t rs_wx = hmake_rsrc(p.wx, static_cast<unsigned>(S) * D * 2u);
-  const hrsrc_t rs_wdt = hmake_rsrc(p.wdt, static_cast<unsigned>(D) * R * 2u);
+  const unsigned woff = ws < S ? (static_cast<unsigned>(ws) * D + wd) * 2u : kOob;
+  const rsrc_t rs_wx = make_rsrc(p.wx, static_cast<unsigned>(S) * D * 2u);
+  const rsrc_t rs_wdt = make_rsrc(p.wdt, static_cast<unsigned>(D) * R * 2u);
 
   struct Stage { uint4 rx, rw, rh; };
   struct Ops { uint4 a[2], b[2]; };
 
-  // Cursor fields enter descriptors and scalar offsets.  In the loop they live in SGPRs anyway; in the prologue hipcc
-  // had them in VGPRs, could not prove them uniform and wrapped those buffer loads in waterfall loops -- whose loads
-  // its s_waitcnt bookkeeping counts once although the counter sees every trip: the first conv read its neighbours'
-  // packs (DPP) before they had landed, on some workgroups, on some runs (tests/test_gpu_xdt_proj.py caught it on
-  // the bf16 form; the fp32 form had the same loops).  readfirstlane makes the uniformity explicit: no waterfall.
-  auto uniform = [](const HCursor& c) {                    // the same values, provably wave-uniform (SGPRs)
-    return HCursor{__builtin_amdgcn_readfirstlane(c.j), __builtin_amdgcn_readfirstlane(c.ks),
-                  __builtin_amdgcn_readfirstlane(c.q), __builtin_amdgcn_readfirstlane(c.r)};
-  };
-  auto issue = [&](Stage& st, const HCursor& c_) {
-    const HCursor c = uniform(c_);
-    const hrsrc_t rs = hmake_rsrc(p.x + static_cast<size_t>(c.q) * p.x_bs, c.j < ntw ? sample_bytes : 0u);
+  auto issue = [&](Stage& st, const Cursor& c_) {
+    const Cursor c = uniform(c_);
+    const rsrc_t rs = make_rsrc(p.x + static_cast<size_t>(c.q) * p.x_bs, c.j < ntw ? sample_bytes : 0u);
     const int t0 = c.r * kHTok;
     const unsigned soff = (static_cast<unsigned>(c.ks) * kHKS * L + t0) * 2u;
     const bool xok = t0 + xt < L;                          // L % 8 == 0: a pack is all in or all out
-    st.rx = hload16(rs, xok ? xoff : kHOob, soff);
+    st.rx = bload16<uint4>(rs, xok ? xoff : kOob, soff);
     // the pack in front of the tile for the row's first lane (t0 > 0: soff >= 128, so soff - 16 does not wrap)
-    if (kConv) st.rh = hload16(rs, (first && t0 > 0) ? xoff : kHOob, soff - 16u);
-    st.rw = hload16(rs_wx, woff, static_cast<unsigned>(c.ks) * kHKS * 2u);
+    if (kConv) st.rh = bload16<uint4>(rs, (first && t0 > 0) ? xoff : kOob, soff - 16u);
+    st.rw = bload16<uint4>(rs_wx, woff, static_cast<unsigned>(c.ks) * kHKS * 2u);
   };
-  auto stage = [&](const Stage& st, const HCursor& c_, int buf) {
-    const HCursor c = uniform(c_);
+  auto stage = [&](const Stage& st, const Cursor& c_, int buf) {
+    const Cursor c = uniform(c_);
     uint4 v = st.rx;
     if (kConv) {
-      const hrsrc_t rs_xc = hmake_rsrc(p.xconv + static_cast<size_t>(c.q) * D * L, c.j < ntw ? sample_bytes : 0u);
+      const rsrc_t rs_xc = make_rsrc(p.xconv + static_cast<size_t>(c.q) * D * L, c.j < ntw ? sample_bytes : 0u);
       const int t0 = c.r * kHTok;
       const unsigned soff = (static_cast<unsigned>(c.ks) * kHKS * L + t0) * 2u;
       const bool xok = t0 + xt < L;
@@ -165,8 +114,8 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
       unsigned qz = hdpp_prev(v.z), qw = hdpp_prev(v.w);
       asm volatile("" : "+v"(qz), "+v"(qw));
       const unsigned pz = first ? st.rh.z : qz, pw = first ? st.rh.w : qw;
-      const float win[11] = {hhi(pz), hlo(pw), hhi(pw), hlo(v.x), hhi(v.x), hlo(v.y), hhi(v.y),
-                             hlo(v.z), hhi(v.z), hlo(v.w), hhi(v.w)};
+      const float win[11] = {bf16_hi(pz),  bf16_lo(pw),  bf16_hi(pw),  bf16_lo(v.x), bf16_hi(v.x), bf16_lo(v.y),
+                             bf16_hi(v.y), bf16_lo(v.z), bf16_hi(v.z), bf16_lo(v.w), bf16_hi(v.w)};
       const float4 tp = *reinterpret_cast<const float4*>(&sTap[4 * d]);
       const float w4[4] = {tp.x, tp.y, tp.z, tp.w};
       const float bias = sBias[d];
@@ -178,8 +127,9 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
         for (int q = 0; q < 4; ++q) acc = fmaf(w4[q], win[e + q], acc);
         o[e] = acc * sigmoid_f(acc);
       }
-      v = make_uint4(hpack(o[0], o[1]), hpack(o[2], o[3]), hpack(o[4], o[5]), hpack(o[6], o[7]));
-      hstore16(v, rs_xc, xok ? xoff : kHOob, soff);
+      v = make_uint4(bf16_pack2(o[0], o[1]), bf16_pack2(o[2], o[3]), bf16_pack2(o[4], o[5]),
+                     bf16_pack2(o[6], o[7]));
+      bstore16(v, rs_xc, xok ? xoff : kOob, soff);
       if (!xok) v = make_uint4(0u, 0u, 0u, 0u);
     }
     *reinterpret_cast<uint4*>(&sX[buf][xd * kHXP + xt]) = v;
@@ -204,14 +154,14 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
   // Wdt row of 2 R bytes: MFMA 0 takes r = 8 hh .. + 7, MFMA 1 r = 16 + 8 hh .. + 7 (past R: zeros)
   unsigned wdoff[2];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) wdoff[j] = (16 * j + 8 * hh < R) ? (static_cast<unsigned>(li) * R + 16 * j + 8 * hh) * 2u : kHOob;
+  for (int j = 0; j < 2; ++j) wdoff[j] = (16 * j + 8 * hh < R) ? (static_cast<unsigned>(li) * R + 16 * j + 8 * hh) * 2u : kOob;
   const unsigned dvoff = (static_cast<unsigned>(4 * hh) * L + li) * 2u;
   auto wload = [&](int u_) {
     const int u = __builtin_amdgcn_readfirstlane(u_);
     const int db = wave + 4 * (u >> 1);
     const unsigned soff = db < ndb ? static_cast<unsigned>(db) * 32u * R * 2u : 0u;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) wa[j] = hload16(rs_wdt, db < ndb ? wdoff[j] : kHOob, soff);
+    for (int j = 0; j < 2; ++j) wa[j] = bload16<uint4>(rs_wdt, db < ndb ? wdoff[j] : kOob, soff);
   };
   auto unit_mfma = [&](int u, f32x16& o) {
     const uint16_t* dt = &sDt[((u & 1) * 32 + li) * kHDP + 8 * hh];
@@ -228,38 +178,37 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
     const int u = __builtin_amdgcn_readfirstlane(u_), q = __builtin_amdgcn_readfirstlane(q_),
               r = __builtin_amdgcn_readfirstlane(r_);
     const int db = wave + 4 * (u >> 1);
-    const hrsrc_t rs = hmake_rsrc(p.delta + static_cast<size_t>(q) * D * L, db < ndb ? sample_bytes : 0u);
+    const rsrc_t rs = make_rsrc(p.delta + static_cast<size_t>(q) * D * L, db < ndb ? sample_bytes : 0u);
     const int tb0 = r * kHTok + (u & 1) * 32;
-    const unsigned voff = tb0 + li < L ? dvoff : kHOob;
+    const unsigned voff = tb0 + li < L ? dvoff : kOob;
     const unsigned base = (static_cast<unsigned>(db) * 32u * L + tb0) * 2u;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      hstore2(f32_to_bf16(o[i]), rs, voff, base + static_cast<unsigned>((i & 3) + 8 * (i >> 2)) * L * 2u);
+      bstore2(f32_to_bf16(o[i]), rs, voff, base + static_cast<unsigned>((i & 3) + 8 * (i >> 2)) * L * 2u);
   };
 
-  // ---- the pipeline (same walk as the fp32 form) ---------------------------------------------------------------------
+  // ---- the pipeline: the statements of xdt_pipeline (xdt_walk.h), kept here because moved into that template this form
+  // compiles to one or two more VGPRs than it does below (profiles/xdt_walk.json); a change there is made here too ----
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
   Stage s0, s1;
   Ops o0;
-  // uniform values kept in SGPRs (integer division runs on the VALU): descriptors built from them are provably
-  // wave-uniform, no waterfall loop wraps the prologue's buffer loads and hipcc's vmcnt counts stay exact
   const int q0 = __builtin_amdgcn_readfirstlane(wg / tps);
-  HCursor cm{0, 0, q0, wg - q0 * tps};
-  HCursor cr = cm, cs = cm, cl = cm;
-  advance(cr, 1);
-  advance(cs, 1); advance(cs, 1);
+  Cursor cm{0, 0, q0, wg - q0 * tps};
+  Cursor cr = cm, cs = cm, cl = cm;
+  advance(cr, w);
+  advance(cs, w); advance(cs, w);
   {
     issue(s0, cm);
     issue(s1, cr);
-    if (kConv) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // as in xdt_proj.hip: before the first DPP conv
+    if (kConv) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // as in xdt_pipeline (xdt_walk.h): see the note there
     stage(s0, cm, 0);
     issue(s0, cs);
     stage(s1, cr, 1);
-    cl = cs; advance(cl, 1);
+    cl = cs; advance(cl, w);
     issue(s1, cl);
-    advance(cl, 1);
+    advance(cl, w);
     __syncthreads();
     read_ops(o0, 0);
     __syncthreads();
@@ -281,7 +230,7 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
     }
     issue(st, cl);
     read_ops(cur, buf ^ 1);
-    advance(cm, 1); advance(cr, 1); advance(cs, 1); advance(cl, 1);
+    advance(cm, w); advance(cr, w); advance(cs, w); advance(cl, w);
     __syncthreads();
   };
   using T = std::true_type;
@@ -318,7 +267,8 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int s = sblk * 32 + 8 * g + 4 * hh;
-        const uint2 pk = make_uint2(hpack(acc[4 * g], acc[4 * g + 1]), hpack(acc[4 * g + 2], acc[4 * g + 3]));
+        const uint2 pk =
+            make_uint2(bf16_pack2(acc[4 * g], acc[4 * g + 1]), bf16_pack2(acc[4 * g + 2], acc[4 * g + 3]));
         if (t < L && s < S) *reinterpret_cast<uint2*>(row + s) = pk;        // S % 4 == 0
         if (sblk == 0)                                                        // r = s: rows past R pad K with zeros
           *reinterpret_cast<uint2*>(&sDt[(tblk * 32 + li) * kHDP + 8 * g + 4 * hh]) = s < R ? pk : make_uint2(0u, 0u);
@@ -349,17 +299,11 @@ int xdt_launch_bf16(const void* x, const float* cw, const float* cb, const void*
   a.wx = static_cast<const uint16_t*>(wx); a.wdt = static_cast<const uint16_t*>(wdt);
   a.xdbl = static_cast<uint16_t*>(xdbl); a.delta = static_cast<uint16_t*>(delta);
   a.batch = batch; a.D = D; a.L = L; a.S = S; a.R = R; a.x_bs = x_bs;
-  const long long ntiles = static_cast<long long>(batch) * ((L + kHTok - 1) / kHTok);
-  long long g = ntiles;
-  if (ntiles > 768) {                                      // 3 workgroups per CU resident; even tile counts when a
-    const long long per0 = (ntiles + 767) / 768;           // divisor is near (never a collapsed grid: xdt_proj.hip)
-    long long per = per0;
-    while (ntiles % per && per < 2 * per0) ++per;
-    g = (ntiles % per == 0) ? ntiles / per : 768;
-  }
+  // all workgroups resident together: 3 per CU, 256 CUs
+  const dim3 grid(xdt_grid(static_cast<long long>(batch) * ((L + kHTok - 1) / kHTok), 768));
   if (conv)
-    hipLaunchKernelGGL(xdt_proj_bf16_kernel<true>, dim3(static_cast<unsigned>(g)), dim3(kHThreads), 0, stream, a);
+    hipLaunchKernelGGL(xdt_proj_bf16_kernel<true>, grid, dim3(kHThreads), 0, stream, a);
   else
-    hipLaunchKernelGGL(xdt_proj_bf16_kernel<false>, dim3(static_cast<unsigned>(g)), dim3(kHThreads), 0, stream, a);
+    hipLaunchKernelGGL(xdt_proj_bf16_kernel<false>, grid, dim3(kHThreads), 0, stream, a);
   return static_cast<int>(hipGetLastError());
 }

@@ -12,11 +12,14 @@ def nerr(got, want):
     return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
-# the last three walk several tiles per workgroup (> 512 tiles): D = 64 has two steps per tile (the four-step lookahead
-# crosses two tile seams), D = 192 leaves a wave delta blocks past the in-loop slots, L = 616 has a ragged last tile
+# the last four walk several tiles per workgroup (> 512 tiles): D = 64 has two steps per tile (the four-step lookahead
+# crosses two tile seams), D = 192 leaves a wave delta blocks past the in-loop slots, L = 616 has a ragged last tile;
+# (7, 64, 9512): 1043 tiles (149 per sample, the last ragged) have no divisor near the resident grid, so workgroups walk
+# UNEVEN tile counts (fp32: grid 512, 19 workgroups walk 3 tiles, the rest 2; bf16: grid 768, 275 walk 2, the rest 1)
 @pytest.mark.parametrize("B,D,L,N,R", [(2, 768, 1024, 16, 24), (3, 256, 64, 16, 8), (1, 768, 208, 16, 24),
                                        (2, 128, 36, 16, 8), (64, 768, 1024, 16, 24), (1, 64, 4, 16, 4),
-                                       (40, 64, 1024, 16, 4), (60, 192, 640, 16, 12), (130, 128, 616, 16, 8)])
+                                       (40, 64, 1024, 16, 4), (60, 192, 640, 16, 12), (130, 128, 616, 16, 8),
+                                       (7, 64, 9512, 16, 4)])
 def test_xdt_proj_matches_float64_products(B, D, L, N, R, device):
     from si_mamba_amd.mamba_inner import xdt_proj_fused_ok, xdt_proj_fwd
     S = R + 2 * N
@@ -74,7 +77,7 @@ def test_mixer_uses_the_fused_kernel_and_matches_the_library_route(device, monke
 
 
 @pytest.mark.parametrize("B,D,L", [(2, 768, 1024), (3, 256, 68), (1, 64, 4), (64, 768, 1024), (40, 64, 1024),
-                                   (60, 192, 616)])
+                                   (60, 192, 616), (7, 64, 9512)])
 @pytest.mark.parametrize("bias", [True, False])
 def test_conv_fused_into_the_staging_matches_the_conv_kernel(B, D, L, bias, device):
     """simamba_conv_xdt_proj_fwd: the conv output written as a by-product equals the stand-alone conv kernel's bit for
@@ -109,7 +112,7 @@ def test_conv_fused_into_the_staging_matches_the_conv_kernel(B, D, L, bias, devi
 # ---- bf16 form (v_mfma_f32_32x32x16_bf16; the reference's autocast roundings) ---------------------------------------
 @pytest.mark.parametrize("B,D,L,N,R", [(2, 768, 1024, 16, 24), (3, 256, 72, 16, 8), (1, 768, 208, 16, 24),
                                        (1, 64, 8, 16, 4), (64, 768, 1024, 16, 24), (40, 64, 1024, 16, 4),
-                                       (60, 192, 640, 16, 12), (130, 128, 616, 16, 8)])
+                                       (60, 192, 640, 16, 12), (130, 128, 616, 16, 8), (7, 64, 9512, 16, 4)])
 def test_xdt_proj_bf16_matches_rounded_products(B, D, L, N, R, device):
     """bf16 operands: x_dbl is the float64 product of the bf16 values rounded once to bf16, delta the product of Wdt with
     those ROUNDED dt rows, rounded once (what x_proj followed by dt_proj give under autocast).  1e-2 is the north-star
@@ -138,7 +141,7 @@ def test_xdt_proj_bf16_matches_rounded_products(B, D, L, N, R, device):
 
 
 @pytest.mark.parametrize("B,D,L", [(2, 768, 1024), (3, 256, 72), (1, 64, 8), (64, 768, 1024), (40, 64, 1024),
-                                   (60, 192, 616)])
+                                   (60, 192, 616), (7, 64, 9512)])
 @pytest.mark.parametrize("bias", [True, False])
 def test_conv_fused_bf16_matches_the_conv_kernel(B, D, L, bias, device):
     """bf16 conv-fused form: x_conv bit-identical to the stand-alone bf16 conv kernel (same fp32 fmaf chain, one rounding),
