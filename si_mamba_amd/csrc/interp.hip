@@ -96,10 +96,13 @@ __global__ __launch_bounds__(256) void interp_fwd_kernel(const T* __restrict__ f
 }
 
 // Backward as a gather (deterministic, no atomics): one workgroup per (sample, centre).  Phase 1 scans the
-// sample's 3 N neighbour entries and compacts, in order, the (point, weight) pairs that name this centre into LDS
+// sample's N points and compacts, in order, one (point, weight) pair for every point that names this centre into LDS
 // (wave ballots + a 4-entry prefix over the waves); phase 2 gives every lane 4 channels and sums
 // weight * dout[point] over that list with coalesced row reads.  Every dout row is read 3 times in total -- the
 // float-atomic scatter this replaces took 1.55 ms at (16, 2048, 1152) against 0.1 ms for the reads.
+// A point's weight is the sum of its entries that name the centre, taken in slot order from 0: with S >= 3 the three
+// indices of a point are distinct, so that is 0 + w = w exactly; with S < 3 three_nn repeats the last centre, a point
+// names it two or three times, and the list still holds at most N pairs (one per entry would need up to 3 N).
 template <typename T>
 __global__ __launch_bounds__(256) void interp_bwd_kernel(const T* __restrict__ dout, const int* __restrict__ idx,
                                                          const float* __restrict__ wgt, float* __restrict__ dfeats,
@@ -115,18 +118,24 @@ __global__ __launch_bounds__(256) void interp_bwd_kernel(const T* __restrict__ d
   const float* w = wgt + static_cast<size_t>(b) * N * 3;
   if (tid == 0) sBase = 0;
   __syncthreads();
-  for (int base = 0; base < 3 * N; base += 256) {
-    const int e = base + tid;
-    const bool match = e < 3 * N && id[e] == s;
+  for (int base = 0; base < N; base += 256) {
+    const int n = base + tid;
+    bool match = false;
+    float wn = 0.f;
+    if (n < N) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (id[3 * n + k] == s) { match = true; wn += w[3 * n + k]; }
+    }
     const unsigned long long bal = __ballot(match);
     if (lane == 0) sWave[wave] = __popcll(bal);
     __syncthreads();
     int off = sBase;
     for (int k = 0; k < wave; ++k) off += sWave[k];
     if (match) {
-      const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
-      sPt[pos] = e / 3;
-      sWt[pos] = w[e];
+      const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));   // < N: at most one pair per point
+      sPt[pos] = n;
+      sWt[pos] = wn;
     }
     __syncthreads();
     if (tid == 0) sBase += sWave[0] + sWave[1] + sWave[2] + sWave[3];
@@ -200,6 +209,8 @@ extern "C" int simamba_three_interpolate_bwd(const void* dout, const int* idx, c
   }
   if (!dout || !idx || !weight) return SIMAMBA_E_NULLPTR;
   const size_t smem = 8 * static_cast<size_t>(N);
+  // N = 8192: 64 KiB of lists plus the kernel's five static words.  The runtime takes that launch as it is (rc 0 and
+  // the right dfeats on an MI355X), so no hipFuncSetAttribute here; tests/test_gpu_lattice_selection.py runs the shape.
   with_io_type(io_dtype, [&](auto tag) {
     using T = decltype(tag);
     hipLaunchKernelGGL(interp_bwd_kernel<T>, dim3(S, batch), dim3(256), smem, s, static_cast<const T*>(dout), idx, weight,
