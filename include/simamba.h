@@ -476,6 +476,26 @@ int simamba_three_interpolate_bwd(const void* dout, const int* idx, const float*
                                   int N, int S, int C, int io_dtype, void* stream);
 
 /*
+ * Gather-sum-scatter over the rows of a sequence: the per-layer cross-merge of the SAST orderings (reference
+ * models/point_mamba.py:350-370 cross_merg and :394-409, the model option add_after_layer) in one pass, and its adjoint.
+ *   x, y        : (batch, L, C) io_dtype, contiguous; y must not alias x.  Every row of y named by scatter_idx is
+ *                 written, no other.
+ *   gather_idx  : (batch, M, G) int32, rows of x ; scatter_idx : (batch, M, G) int32, rows of y.
+ * For every (b, g), with H = M / 2, gi_m = gather_idx[b, m, g] and si_m = scatter_idx[b, m, g]:
+ *   s = ((x[b, gi_0] + x[b, gi_H]) + (x[b, gi_1] + x[b, gi_{H+1}])) + ... + (x[b, gi_{H-1}] + x[b, gi_{M-1}])
+ *   y[b, si_m] = s for m = 0 .. M-1
+ * in fp32, in exactly that order of additions, rounded once to io_dtype.  No atomics: the same bits every time.  With
+ * maps that are bijections of [0, L) per sample the adjoint is the same call with the two maps swapped.
+ * M even, 2 <= M <= 16, L == M * G, C % 4 == 0, batch <= 65535 (else SIMAMBA_E_SHAPE); x and y aligned to one lane's
+ * four elements (else SIMAMBA_E_ALIGN).  Checks in the order dtype, empty (batch == 0: SIMAMBA_OK, nothing read),
+ * shape, null pointers, alignment; all precede the launch.  The index VALUES are the caller's contract (0 <= value < L):
+ * they are not validated on the device, and a value outside that range reads or writes outside the tensors.
+ * Still ABI version 9: a symbol added, none changed.
+ */
+int simamba_gather_sum_scatter(const void* x, const int* gather_idx, const int* scatter_idx, void* y, int batch, int L,
+                               int G, int M, int C, int io_dtype, void* stream);
+
+/*
  * Chamfer distance of the MAE pre-training loss (reference models/point_mamba.py:2950, :3203:
  * pytorch3d.loss.chamfer_distance(pred, gt, batch_reduction=None) -- squared L2 to the nearest neighbour, mean over
  * each set's points, both directions summed; one value per pair of sets).

@@ -114,6 +114,7 @@ SIGNATURES = {
     "simamba_three_nn": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "simamba_three_interpolate_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "simamba_three_interpolate_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "simamba_gather_sum_scatter": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "simamba_chamfer_fwd": (c_int, [_P, _P, _P, _P, _P, _LL, c_int, c_int, _P]),
     "simamba_chamfer_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _LL, c_int, c_int, _P]),
     "simamba_chamfer_large_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _LL, c_int, c_int, _P]),

@@ -4,6 +4,7 @@
   create_block   reference models/point_mamba.py:147-175
   _init_weights  reference models/point_mamba.py:115-144
   MixerModel     reference models/point_mamba.py:178-272
+  MixerModel_add reference models/point_mamba.py:281-428   (add_after_layer: cross-merge after every block)
 
 Same constructor arguments, forward signatures, return values and parameter names, so a
 state_dict of the reference's ``blocks.*`` loads unchanged.  The Triton fused add+norm path
@@ -22,6 +23,7 @@ from torch import Tensor
 
 from . import _lib
 from .add_norm import add_layer_norm_fn
+from .cross_merge import cross_merge, cross_merge_composed, cross_merge_maps
 from .mamba_simple import Mamba
 from .out_norm import out_proj_add_ln_fn, out_proj_add_ln_ok
 from .rms_norm import RMSNorm
@@ -281,6 +283,51 @@ class MixerModel(nn.Module):
         if hidden_states.is_cuda and type(self.norm_f) in _KERNEL_NORMS and hidden_states.dim() == 3:
             # the stack's output norm returns the parameter dtype (fp32) under autocast too, as F.layer_norm does
             # there; the block norms feed a GEMM and may hand over the autocast dtype directly
+            return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
+        residual = (hidden_states + residual) if residual is not None else hidden_states
+        return self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))
+
+
+class MixerModel_add(MixerModel):
+    """reference models/point_mamba.py:281-428, the stack behind ``add_after_layer: True``: after every block the 2 k
+    copies of each patch token in the SAST sequence are summed and laid out again in the same 2 k orderings
+    (cross_merge.py).  Constructor, parameter names, state-dict keys (``layers.*``, ``norm_f.*``) and initialisation are
+    MixerModel's.  The stack runs layer by layer in every precision: the fused out_proj + add + LayerNorm chain of
+    MixerModel does not apply, the merge sits between out_proj and the add.
+
+    ``composed`` (a test and benchmark hook): True runs the reference's own sequence of torch ops in place of the
+    kernel."""
+
+    composed = False
+
+    def forward(self, input_ids, pos, top_k_eigenvectors, N_k_top_eigenvectors, reverse, inference_params=None, *,
+                order=None):
+        """Reference signature (:383).  ``input_ids`` / ``pos`` (B, L, C) in SAST sequence order, L = 2 k G;
+        ``top_k_eigenvectors`` (B, G, k).  ``order`` (B, k, G), optional and specific to this implementation: the
+        argsort of the eigenvectors when the caller already holds it (``spectral.spectral_order``); the reference
+        re-sorts at every layer."""
+        if not reverse:
+            raise ValueError("MixerModel_add: add_after_layer needs reverse=True (with reverse=False the reference "
+                             "discards the merge)")
+        k = int(N_k_top_eigenvectors)
+        if order is None:
+            from . import spectral
+            vecs = top_k_eigenvectors[:, :, :k]
+            B, G = vecs.shape[:2]
+            order = spectral.argsort_rows(vecs.transpose(1, 2).reshape(B * k, G)).view(B, k, G)
+        if order.shape[1] != k or 2 * k * order.shape[2] != input_ids.shape[1]:
+            raise ValueError(f"MixerModel_add: a sequence of {input_ids.shape[1]} tokens is not 2 k G with orders "
+                             f"{tuple(order.shape)} and k = {k}")
+        maps = None if self.composed else cross_merge_maps(order)      # once per forward, shared by all layers
+        hidden_states = input_ids + pos
+        residual = None
+        A_all = self._precompute_A()
+        for i, layer in enumerate(self.layers):
+            hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params, A=A_all[i])
+            hidden_states = self.drop_out_in_block(hidden_states)
+            hidden_states = (cross_merge_composed(hidden_states, order) if self.composed
+                             else cross_merge(hidden_states, maps))
+        if hidden_states.is_cuda and type(self.norm_f) in _KERNEL_NORMS and hidden_states.dim() == 3:
             return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
         residual = (hidden_states + residual) if residual is not None else hidden_states
         return self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))

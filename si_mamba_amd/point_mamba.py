@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import grouping, spectral
-from .block import MixerModel
+from .block import MixerModel, MixerModel_add
 from .add_norm import add_layer_norm_fn
 from .encoder_ops import bn_relu_fn, group_max_fn, token_linear, token_linear_group_max
 
@@ -149,8 +149,16 @@ class PointMamba(nn.Module):
         self.rms_norm = getattr(config, "rms_norm", False)
         self.drop_out_in_block = getattr(config, "drop_out_in_block", 0.)
         self.pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, self.trans_dim))
-        self.blocks = MixerModel(d_model=self.trans_dim, n_layer=self.depth, rms_norm=self.rms_norm,
-                                 drop_out_in_block=self.drop_out_in_block, drop_path=self.drop_path)
+        # add_after_layer (reference :465-480): the stack that cross-merges the orderings after every block
+        self.add_after_layer = getattr(config, "add_after_layer", False)
+        if self.add_after_layer and not (config.method == "SAST" and config.reverse):
+            raise ValueError(f"add_after_layer=True needs method='SAST' and reverse=True, got method="
+                             f"{config.method!r}, reverse={config.reverse!r}: the merge sums the 2 k orderings of a "
+                             "SAST sequence (with reverse=False the reference discards it, and an HLT or MAMBA "
+                             "sequence is not 2 k orderings)")
+        stack = MixerModel_add if self.add_after_layer else MixerModel
+        self.blocks = stack(d_model=self.trans_dim, n_layer=self.depth, rms_norm=self.rms_norm,
+                            drop_out_in_block=self.drop_out_in_block, drop_path=self.drop_path)
         self.norm = nn.LayerNorm(self.trans_dim)
         self.cls_head_finetune = nn.Sequential(
             nn.Linear(self.trans_dim, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
@@ -263,8 +271,16 @@ class PointMamba(nn.Module):
             main.wait_stream(side)
             for t in spec:
                 t.record_stream(main)
-        idx = self.token_index(center, order)
-        if idx is not None and not (self.training and self.drop_out.p > 0):
+        idx = None if self.add_after_layer else self.token_index(center, order)
+        if self.add_after_layer:
+            # :1118-1119: the stack merges the orderings after every block, so it takes the whole sequence (every
+            # position through block 0, not the distinct tokens) plus the eigenvectors and their argsort
+            if spec is None:
+                spec = self.spectral_eigs(center)
+            x, pos = self.order_tokens(tokens, pos, center, spec[2])
+            x = self.drop_out(x)
+            x = self.blocks(x, pos, spec[1], self.k_top_eigenvectors, self.reverse, order=spec[2])
+        elif idx is not None and not (self.training and self.drop_out.p > 0):
             # the sequence is a gather of the G patch tokens: the stack takes the distinct tokens plus the index map
             # and runs the first block's per-token head on G instead of L positions (seq_expand.py); same result
             x = self.blocks(tokens, pos, token_index=idx, balanced_index=True)     # concatenated permutations
