@@ -564,6 +564,32 @@ int simamba_chamfer_ragged_bwd(const float* x, const float* y, const int* xlen, 
                                int queries, void* stream);
 
 /*
+ * Earth mover's distance between pairs of equal-sized point sets (csrc/emd.hip): the cost of the cheapest one-to-one
+ * matching under squared Euclidean distance, c_ij = (dx*dx + dy*dy) + dz*dz, by the forward auction with Jacobi rounds
+ * and epsilon-scaling.  The x points bid, the y points are the objects; every cost is formed on the fly from LDS.
+ *   x, y      : (pairs, n, 3) fp32, contiguous ; 1 <= n <= 1024 ; pairs >= 1.
+ *   assign    : (pairs, n) int32, assign[p][i] = the y point matched to x[p][i]; always a permutation of 0 .. n-1.
+ *   dist      : (pairs) fp32 = mean_i |x_i - y_assign[i]|^2.
+ *   rounds    : (pairs) int32, bidding rounds run, over all phases.
+ *   converged : (pairs) uint8, 1 when the last phase ended with every bidder assigned: then the matching's total cost
+ *               is within n * eps_final of the optimum.  0: the round cap was reached first; the bidders still
+ *               unassigned took the objects still free, both in index order, and nothing is promised about the cost.
+ *   eps       : eps_final, absolute, in cost units; 0 = 2^-14 * cmax of each pair, cmax the pair's largest cost (1e-30
+ *               where cmax is 0).  Phases run with cmax/2, cmax/8, ... down to eps_final; prices carry over.
+ *   max_rounds: the cap on `rounds` per pair; every loop of the kernel is bounded by it, whatever the input.
+ * A winning bid raises the price to max(bid, nextafter(old price)), so a round always makes progress, also with eps
+ * below the price's ulp.  Equal bids on one object go to the lowest bidder index: no result depends on timing, the same
+ * bits every time.  Non-finite coordinates: no index is ever derived from a float, the kernel ends at the cap at the
+ * latest and assign is still a permutation; dist is then whatever that matching costs (inf or NaN), converged
+ * usually 0.  n <= 64: one wave per pair, four pairs per workgroup; above: one workgroup per pair.  No workspace, no
+ * global atomics, no allocation or synchronisation.
+ * Checks: SIMAMBA_E_SHAPE (n outside [1, 1024], pairs < 1, max_rounds < 1, eps negative or NaN), then null pointers.
+ * Still ABI version 9: a symbol added, none changed.
+ */
+int simamba_emd_fwd(const float* x, const float* y, int* assign, float* dist, int* rounds, unsigned char* converged,
+                    long long pairs, int n, float eps, int max_rounds, void* stream);
+
+/*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,
  * K=group_size, return_sorted=False)): idx[b][g][0..K) = the K points of cloud b nearest to centre g, ascending
  * squared distance (direct differences), ties to the lower point index.

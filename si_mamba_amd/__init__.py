@@ -10,8 +10,9 @@ from .block import Block, MixerModel, create_block, DropPath
 from .rms_norm import RMSNorm
 from . import spectral
 from .shim import install_shim
+from .emd import earth_movers_distance
 from ._lib import deterministic, deterministic_enabled, set_deterministic
 
 __all__ = ["causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
-           "set_deterministic"]
+           "set_deterministic", "earth_movers_distance"]

@@ -123,6 +123,7 @@ SIGNATURES = {
     "simamba_chamfer_large_bwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_chamfer_ragged_fwd": (c_int, [_P] * 9 + [_LL] + [c_int] * 6 + [_P]),
     "simamba_chamfer_ragged_bwd": (c_int, [_P] * 11 + [_LL] + [c_int] * 6 + [_P]),
+    "simamba_emd_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _LL, c_int, c_float, c_int, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from . import _lib, grouping, spectral
 from .block import MixerModel
+from .emd import earth_movers_distance
 from .point_mamba import Encoder, Group
 
 
@@ -349,7 +350,9 @@ class MambaDecoder_SST(nn.Module):
 
 
 class Point_MAE_Mamba(nn.Module):
-    """reference :2870-3219, eigenvector-order route; forward(pts (B,N,3)) -> scalar Chamfer-L2 loss."""
+    """reference :2870-3219, eigenvector-order route; forward(pts (B,N,3)) -> scalar Chamfer-L2 loss, or with
+    ``config.loss == "emd"`` the earth mover's distance of the rebuilt patches (an extension: the reference raises
+    for that value, its ``emd()`` line is commented out, :2947-2956)."""
 
     def __init__(self, config):
         super().__init__()
@@ -368,7 +371,7 @@ class Point_MAE_Mamba(nn.Module):
         self.group_divider = Group(num_group=self.num_group, group_size=self.group_size)
         self.increase_dim = nn.Sequential(nn.Conv1d(self.trans_dim, 3 * self.group_size, 1))
         nn.init.trunc_normal_(self.mask_token, std=.02)
-        if config.loss not in ("cdl1", "cdl2"):
+        if config.loss not in ("cdl1", "cdl2", "emd"):
             raise NotImplementedError(config.loss)
         self.loss = config.loss
         self.method = tc.method
@@ -380,6 +383,12 @@ class Point_MAE_Mamba(nn.Module):
         self.symmetric = tc.symmetric
         self.self_loop = tc.self_loop
         self.binary = tc.binary
+
+    def patch_loss(self, rebuild, gt):
+        """(B * Mtok, M, 3) rebuilt and ground-truth patches -> (B * Mtok,) fp32: the configured loss of every patch."""
+        if self.loss == "emd":
+            return earth_movers_distance(rebuild.float(), gt.float())
+        return chamfer_distance(rebuild.float(), gt.float())
 
     def spectral_orders(self, center):
         """:3097 graph (create_graph_from_centers) -> k smallest eigenvectors -> ascending argsort, (B,k,G)."""
@@ -430,7 +439,7 @@ class Point_MAE_Mamba(nn.Module):
         rebuild = F.linear(x_rec.reshape(B * Mtok, C), w.weight.squeeze(-1), w.bias).reshape(B * Mtok, -1, 3)
         gt = torch.gather(neighborhood, 1, enc["msk_src"].view(B, Mtok, 1, 1).expand(-1, -1, M, 3))
         gt = gt.reshape(B * Mtok, M, 3)
-        loss = chamfer_distance(rebuild.float(), gt.float()).mean()
+        loss = self.patch_loss(rebuild, gt).mean()
         if return_parts:
             return loss, dict(enc, rebuild=rebuild, gt=gt, x_full=x_full, neighborhood=neighborhood, center=center)
         return loss
@@ -443,7 +452,8 @@ class Point_MAE_Mamba(nn.Module):
         the number ``nm`` of masked patches, and ``(G - nm)`` below is ``(G - Mtok)``.
           rebuilt      (B, Mtok * M, 3)     the rebuilt masked patches moved back to their centres
           visible      (B, (G - nm) * M, 3) the visible patches at their centres
-          loss_patches (B, Mtok)            the Chamfer loss of every rebuilt patch; its mean is forward()'s loss
+          loss_patches (B, Mtok)            the configured loss (Chamfer, or the earth mover's distance with
+                                            ``loss: emd``) of every rebuilt patch; its mean is forward()'s loss
         The whole-cloud score of a pre-trained model in one line:
           ``chamfer_distance(torch.cat([visible, rebuilt], 1), pts)``
         ``mask`` (B,G) bool, the same number of True in every row, replaces the random mask.  Dropout and drop-path
@@ -460,5 +470,5 @@ class Point_MAE_Mamba(nn.Module):
         rebuilt = (rebuild.view(B, Mtok, M, 3) + centre.unsqueeze(2)).reshape(B, Mtok * M, 3)
         keep = ~parts["mask"]
         visible = (neighborhood[keep] + center[keep].unsqueeze(1)).reshape(B, -1, 3)
-        loss_patches = chamfer_distance(rebuild, parts["gt"].float()).view(B, Mtok)
+        loss_patches = self.patch_loss(rebuild, parts["gt"]).view(B, Mtok)
         return rebuilt, visible, loss_patches

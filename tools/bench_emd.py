@@ -1,0 +1,146 @@
+"""Earth mover's distance (csrc/emd.hip) on one GPU: call times and round counts at the pre-training loss shape
+(39 424 pairs of 32 points: 64 clouds x 616 masked tokens) and at (64 pairs, 1024 points), the one-wave Chamfer kernel at
+the first shape for scale, and the MAE pre-training step (tools/bench_mae.py) with ``loss: cdl2`` and ``loss: emd``.
+
+Every kernel time is a call time: device events around ``reps`` back-to-back calls (reps sized so that a window lasts
+about 0.2 s), 5 windows per operation taken in alternation over the operations, median and spread.  The step times are
+those of fresh tools/bench_mae.py processes, ``--runs`` per variant, the variants alternating so that they see the same
+machine in the same minutes.  ``--parent DIR`` (a built checkout of the parent commit) adds that tree's cdl2 step to the
+alternation: no code on the cdl2 path changes, so the two must agree within their own spread.
+
+``--alt-lib PATH`` (tools/build_alt.sh noshared emd.hip "-DSIMAMBA_EMD_SHARED_SCAN=0") adds the forward of a library
+built without the shared object scan, same inputs, same windows: what spreading one bidder's scan over the wave buys.
+
+    python tools/bench_emd.py [--parent DIR] [--alt-lib PATH] [--runs 3] [--out profiles/emd.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(39424, 32), (64, 1024)]
+
+
+def window_ms(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def alternate(ops, target_ms=200.0, windows=5):
+    """name -> (median, min, max) ms per call; one window of every operation, then the next round of windows."""
+    reps = {}
+    for name, fn in ops.items():
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        reps[name] = max(1, min(2000, int(target_ms / max(window_ms(fn, 2), 1e-3))))
+    ts = {name: [] for name in ops}
+    for _ in range(windows):
+        for name, fn in ops.items():
+            ts[name].append(window_ms(fn, reps[name]))
+    return {name: [round(sorted(v)[len(v) // 2], 4), round(min(v), 4), round(max(v), 4)] for name, v in ts.items()}
+
+
+def raw_forward(lib_path, x, y, max_rounds):
+    """The bare C call of another build of the library, outputs allocated once -> (call, outputs)."""
+    import ctypes
+    from si_mamba_amd import _lib
+    fn = ctypes.CDLL(lib_path).simamba_emd_fwd
+    fn.restype, fn.argtypes = _lib.SIGNATURES["simamba_emd_fwd"]
+    pairs, n, _ = x.shape
+    out = [torch.empty(pairs, n, device=x.device, dtype=torch.int32), torch.empty(pairs, device=x.device),
+           torch.empty(pairs, device=x.device, dtype=torch.int32),
+           torch.empty(pairs, device=x.device, dtype=torch.uint8)]
+
+    def call():
+        rc = fn(x.data_ptr(), y.data_ptr(), *[t.data_ptr() for t in out], pairs, n, 0.0, max_rounds,
+                _lib.stream_ptr(x.device))
+        assert rc == 0, rc
+    return call, out
+
+
+def kernels(alt_lib=None):
+    from si_mamba_amd import earth_movers_distance
+    from si_mamba_amd.emd import default_max_rounds
+    from si_mamba_amd.mae import chamfer_distance
+    dev = torch.device("cuda:0")
+    rows = []
+    for pairs, n in SHAPES:
+        g = torch.Generator().manual_seed(n)
+        x, y = torch.randn(pairs, n, 3, generator=g).to(dev), torch.randn(pairs, n, 3, generator=g).to(dev)
+        w = torch.rand(pairs, device=dev)
+
+        def fwd_bwd(f):
+            xa = x.detach().requires_grad_()
+            (f(xa, y) * w).sum().backward()
+
+        ops = {"emd_fwd": lambda: earth_movers_distance(x, y), "emd_fwd_bwd": lambda: fwd_bwd(earth_movers_distance)}
+        if n <= 64:
+            ops["chamfer_patch_fwd"] = lambda: chamfer_distance(x, y)
+            ops["chamfer_patch_fwd_bwd"] = lambda: fwd_bwd(chamfer_distance)
+        if alt_lib:
+            ops["emd_fwd_no_shared_scan"], alt_out = raw_forward(alt_lib, x, y, default_max_rounds(n))
+        row = dict(shape=[pairs, n], ms_median_min_max=alternate(ops))
+        dist, assign, rounds, conv = earth_movers_distance(x, y, return_assignment=True)
+        if alt_lib:
+            row["no_shared_scan_same_bits"] = all(torch.equal(a, b) for a, b in
+                                                  zip(alt_out, (assign, dist, rounds, conv)))
+        row.update(rounds_mean=round(float(rounds.float().mean()), 1), rounds_max=int(rounds.max()),
+                   max_rounds=default_max_rounds(n), converged_share=float(conv.float().mean()))
+        rows.append(row)
+    return rows
+
+
+def steps(parent, runs):
+    variants = [("this_cdl2", ROOT, ["--loss", "cdl2"]), ("this_emd", ROOT, ["--loss", "emd"])]
+    if parent:
+        variants.insert(0, ("parent_cdl2", os.path.abspath(parent), []))
+    out = {name: [] for name, _, _ in variants}
+    for r in range(runs):
+        for name, tree, extra in variants:
+            print(f"run {r + 1} of {runs}: {name}", file=sys.stderr, flush=True)
+            txt = subprocess.run([sys.executable, os.path.join(tree, "tools", "bench_mae.py")] + extra, check=True,
+                                 capture_output=True, text=True, timeout=600, cwd=tree).stdout
+            out[name].append(json.loads(txt.strip().splitlines()[-1])["ms_per_step"])
+    res = {name: dict(median=sorted(v)[len(v) // 2], runs=v) for name, v in out.items()}
+    if not parent:
+        res["parent_cdl2"] = "not measured (no --parent)"
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--alt-lib", default=None, help="a library built with -DSIMAMBA_EMD_SHARED_SCAN=0")
+    ap.add_argument("--runs", type=int, default=3, help="bench_mae.py processes per variant")
+    ap.add_argument("--no-steps", action="store_true", help="kernel times only")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_emd.py needs a ROCm device: a time from anything else says nothing")
+    # the step processes first: this process has not opened the device yet, so they have the GPU to themselves
+    step_ms = None if args.no_steps else steps(args.parent, args.runs)
+    line = json.dumps(dict(what="earth_movers_distance and the one-wave chamfer_distance, fp32, gaussian clouds, one "
+                                "MI355X; call times (events around back-to-back calls, 5 windows of ~0.2 s per "
+                                "operation, the operations alternating): [median, min, max] ms; MAE step (B = 64, bf16, "
+                                "fwd + bwd + AdamW) per fresh process, variants alternating",
+                           device=torch.cuda.get_device_name(0), kernels=kernels(args.alt_lib), mae_step_ms=step_ms))
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

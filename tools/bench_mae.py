@@ -11,11 +11,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--steps", type=int, default=8)
+ap.add_argument("--loss", default="cdl2", help="config.loss: cdl1, cdl2 or emd")
 ap.add_argument("--graph", action="store_true", help="capture the whole step in one hipGraph (GraphedTrainStep)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
-m = Point_MAE_Mamba(default_mae_config()).to(dev).train()
+m = Point_MAE_Mamba(default_mae_config(loss=args.loss)).to(dev).train()
 params = [p for k, p in m.named_parameters() if not k.startswith("decoder_pos_embed.")]
 opt = torch.optim.AdamW(params, lr=1e-3, weight_decay=0.05, fused=True, capturable=args.graph)
 pts = make_clouds(args.batch, 1024, 0).to(dev)
@@ -47,5 +48,5 @@ for _ in range(args.steps):
     loss = step()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / args.steps
-print(json.dumps({"workload": f"MAE pre-train step, B={args.batch}, 1024 pts -> 64 patches, {args.dtype}" + (", hipGraph" if args.graph else ""),
+print(json.dumps({"workload": f"MAE pre-train step, B={args.batch}, 1024 pts -> 64 patches, {args.dtype}, loss {args.loss}" + (", hipGraph" if args.graph else ""),
                   "ms_per_step": round(dt * 1e3, 2), "clouds_per_s": round(args.batch / dt, 1), "loss": float(loss)}))
