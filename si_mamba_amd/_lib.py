@@ -187,6 +187,26 @@ def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def call(name, *args, device, time_as=None):
+    """Launch C-ABI entry ``name`` on ``device``'s current stream.  ``args`` are the ABI's arguments WITHOUT the trailing
+    stream (every launching entry point ends in ``void* stream``): a tensor stands for its data_ptr(), None for NULL,
+    everything else (ints, floats, pre-offset addresses) passes through.  ``time_as``: bracket the call with
+    ``timed(time_as, device)``.  A non-zero return raises through ``check(rc, name)``."""
+    import torch
+    fn = getattr(load(), name)
+    Tensor = torch.Tensor
+    argv = [a.data_ptr() if isinstance(a, Tensor) else a for a in args]
+    argv.append(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        if time_as is None:
+            rc = fn(*argv)
+        else:
+            with timed(time_as, device):
+                rc = fn(*argv)
+    if rc:
+        check(rc, name)
+
+
 def require_gpu(t, what):
     if not t.is_cuda:
         raise RuntimeError(

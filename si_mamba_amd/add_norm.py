@@ -15,11 +15,22 @@ import torch
 from . import _lib
 
 
+def add_norm_bwd(dn, dro, res_out, mean, rstd, w, rs, dres, dhid, Bsz, rows, dim, hcode, ocode, flags):
+    """The add + norm backward pass (simamba_add_layer_norm_bwd_ex) into ``dres`` / ``dhid`` (either may be None);
+    -> the fp32 (dweight, dbias) rows, summed over the kernel's per-workgroup partials (RMSNorm: dweight only)."""
+    dev = res_out.device
+    grid = _lib.load().simamba_add_layer_norm_grid(Bsz, rows)
+    part = torch.empty(grid, 2, dim, device=dev, dtype=torch.float32)
+    _lib.call("simamba_add_layer_norm_bwd_ex", dn, dro, res_out, mean, rstd, w, rs, dres, dhid, part, Bsz, rows, dim,
+              hcode, ocode, flags, device=dev, time_as="add_rms_bwd" if flags else "add_ln_bwd")
+    # RMS: only the dweight half of the partials is written
+    return part[:, :1].sum(0) if flags else part.sum(0)
+
+
 class AddLayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, residual, weight, bias, eps, rowscale, out_dtype, rms=False):
         _lib.require_gpu(hidden, "add_layer_norm_fn")
-        lib = _lib.load()
         h = hidden.contiguous()
         Bsz, rows, dim = h.shape[0], h[0].numel() // h.shape[-1], h.shape[-1]
         dev = h.device
@@ -35,12 +46,9 @@ class AddLayerNormFn(torch.autograd.Function):
         normed = torch.empty(h.shape, device=dev, dtype=out_dtype)
         mean = None if rms else torch.empty(Bsz * rows, device=dev, dtype=torch.float32)   # RMSNorm has no mean
         rstd = torch.empty(Bsz * rows, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("add_rms_fwd" if rms else "add_ln_fwd", dev):
-            rc = lib.simamba_add_layer_norm_fwd_ex(h.data_ptr(), _lib.ptr(res), _lib.ptr(rs), w.data_ptr(),
-                                                   _lib.ptr(b), None if alias else res_out.data_ptr(),
-                                                   normed.data_ptr(), _lib.ptr(mean), rstd.data_ptr(), Bsz, rows, dim,
-                                                   float(eps), hcode, ocode, flags, _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_add_layer_norm_fwd_ex")
+        _lib.call("simamba_add_layer_norm_fwd_ex", h, res, rs, w, b, None if alias else res_out, normed, mean, rstd,
+                  Bsz, rows, dim, float(eps), hcode, ocode, flags, device=dev,
+                  time_as="add_rms_fwd" if rms else "add_ln_fwd")
         ctx.save_for_backward(res_out, mean, rstd, w, rs)
         ctx.meta = (Bsz, rows, dim, hcode, ocode, h.dtype, residual is not None,
                     None if residual is None else residual.dtype, weight.dtype, bias is not None, flags)
@@ -50,7 +58,6 @@ class AddLayerNormFn(torch.autograd.Function):
     def backward(ctx, dnormed, dres_out):
         res_out, mean, rstd, w, rs = ctx.saved_tensors
         Bsz, rows, dim, hcode, ocode, hdtype, has_res, res_dtype, wdtype, has_bias, flags = ctx.meta
-        lib = _lib.load()
         dev = res_out.device
         dn = dnormed.contiguous()
         dro = None if dres_out is None else dres_out.float().contiguous()
@@ -59,16 +66,7 @@ class AddLayerNormFn(torch.autograd.Function):
         need_split = (rs is not None) or (hdtype != torch.float32) or not has_res
         dres = torch.empty(res_out.shape, device=dev, dtype=torch.float32) if has_res else None
         dhid = torch.empty(res_out.shape, device=dev, dtype=hdtype) if need_split else None
-        grid = lib.simamba_add_layer_norm_grid(Bsz, rows)
-        part = torch.empty(grid, 2, dim, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("add_rms_bwd" if flags else "add_ln_bwd", dev):
-            rc = lib.simamba_add_layer_norm_bwd_ex(dn.data_ptr(), _lib.ptr(dro), res_out.data_ptr(), _lib.ptr(mean),
-                                                   rstd.data_ptr(), w.data_ptr(), _lib.ptr(rs), _lib.ptr(dres),
-                                                   _lib.ptr(dhid), part.data_ptr(), Bsz, rows, dim, hcode, ocode,
-                                                   flags, _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_add_layer_norm_bwd_ex")
-        # RMS: only the dweight half of the partials is written
-        dwb = part[:, :1].sum(0) if flags else part.sum(0)
+        dwb = add_norm_bwd(dn, dro, res_out, mean, rstd, w, rs, dres, dhid, Bsz, rows, dim, hcode, ocode, flags)
         if dhid is None:
             dhid = dres
         return (dhid, None if not has_res else dres.to(res_dtype), dwb[0].to(wdtype),

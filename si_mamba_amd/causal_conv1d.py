@@ -17,7 +17,6 @@ class CausalConv1dFn(torch.autograd.Function):
         if activation not in (None, "silu", "swish"):
             raise NotImplementedError("activation must be None, silu, or swish")
         _lib.require_gpu(x, "causal_conv1d_fn")
-        lib = _lib.load()
         if x.dim() != 3 or weight.dim() != 2 or weight.shape[0] != x.shape[1]:
             raise ValueError("causal_conv1d_fn: x must be (batch, dim, seqlen), weight (dim, width)")
         batch, dim, L = x.shape
@@ -27,11 +26,8 @@ class CausalConv1dFn(torch.autograd.Function):
         bc = None if bias is None else bias.float().contiguous()
         out = torch.empty(batch, dim, L, device=x.device, dtype=x.dtype)
         silu = int(activation is not None)
-        with torch.cuda.device(x.device), _lib.timed("conv1d_fwd", x.device):
-            rc = lib.simamba_causal_conv1d_fwd(_lib.ptr(xc), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(out),
-                                               batch, dim, L, W, silu, _lib.dtype_code(x.dtype),
-                                               xc.stride(0), _lib.stream_ptr(x.device))
-        _lib.check(rc, "simamba_causal_conv1d_fwd")
+        _lib.call("simamba_causal_conv1d_fwd", xc, wc, bc, out, batch, dim, L, W, silu, _lib.dtype_code(x.dtype),
+                  xc.stride(0), device=x.device, time_as="conv1d_fwd")
         ctx.silu = silu
         ctx.w_dtype = weight.dtype
         ctx.b_dtype = None if bias is None else bias.dtype
@@ -51,12 +47,8 @@ class CausalConv1dFn(torch.autograd.Function):
         # deterministic: partials + fixed-order sum instead of float atomics
         flags, ws, nws = _lib.det_args(lib.simamba_causal_conv1d_bwd_workspace_floats, batch, dim, L, W, device=xc.device)
         _lib.count("conv1d_bwd_det" if flags else "conv1d_bwd_atomic")
-        with torch.cuda.device(xc.device), _lib.timed("conv1d_bwd", xc.device):
-            rc = lib.simamba_causal_conv1d_bwd_ex(_lib.ptr(xc), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(dout),
-                                                  _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
-                                                  batch, dim, L, W, ctx.silu, _lib.dtype_code(xc.dtype),
-                                                  xc.stride(0), 0, flags, _lib.ptr(ws), nws, _lib.stream_ptr(xc.device))
-        _lib.check(rc, "simamba_causal_conv1d_bwd_ex")
+        _lib.call("simamba_causal_conv1d_bwd_ex", xc, wc, bc, dout, dx, dw, db, batch, dim, L, W, ctx.silu,
+                  _lib.dtype_code(xc.dtype), xc.stride(0), 0, flags, ws, nws, device=xc.device, time_as="conv1d_bwd")
         return dx, dw.to(ctx.w_dtype), None if db is None else db.to(ctx.b_dtype), None
 
 

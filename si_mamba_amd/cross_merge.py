@@ -40,14 +40,11 @@ def cross_merge_maps(order):
 
 
 def _gather_sum_scatter(x, gather_idx, scatter_idx, what):
-    lib = _lib.load()
     B, L, C = x.shape
     M, G = gather_idx.shape[1:]
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device), _lib.timed(what, x.device):
-        rc = lib.simamba_gather_sum_scatter(x.data_ptr(), gather_idx.data_ptr(), scatter_idx.data_ptr(), y.data_ptr(),
-                                            B, L, G, M, C, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device))
-    _lib.check(rc, "simamba_gather_sum_scatter")
+    _lib.call("simamba_gather_sum_scatter", x, gather_idx, scatter_idx, y, B, L, G, M, C, _lib.dtype_code(x.dtype),
+              device=x.device, time_as=what)
     return y
 
 

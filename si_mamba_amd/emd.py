@@ -27,7 +27,6 @@ class EmdFn(torch.autograd.Function):
     def forward(ctx, x, y, eps, max_rounds):
         _lib.require_gpu(x, "earth_movers_distance")
         _lib.require_gpu(y, "earth_movers_distance")
-        lib = _lib.load()
         xf = x.float().contiguous()
         yf = y.float().contiguous()
         pairs, n, _ = xf.shape
@@ -37,11 +36,8 @@ class EmdFn(torch.autograd.Function):
         rounds = torch.empty(pairs, device=dev, dtype=torch.int32)
         converged = torch.empty(pairs, device=dev, dtype=torch.uint8)
         _lib.count("emd")
-        with torch.cuda.device(dev), _lib.timed("emd_fwd", dev):
-            rc = lib.simamba_emd_fwd(xf.data_ptr(), yf.data_ptr(), assign.data_ptr(), dist.data_ptr(),
-                                     rounds.data_ptr(), converged.data_ptr(), pairs, n, eps, max_rounds,
-                                     _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_emd_fwd")
+        _lib.call("simamba_emd_fwd", xf, yf, assign, dist, rounds, converged, pairs, n, eps, max_rounds,
+                  device=dev, time_as="emd_fwd")
         ctx.save_for_backward(xf, yf, assign)
         ctx.dtypes = (x.dtype, y.dtype)
         ctx.mark_non_differentiable(assign, rounds, converged)

@@ -93,10 +93,6 @@ def _off(t, elems):
     return None if t is None else t.data_ptr() + elems * t.element_size()
 
 
-def _abi(name, *args):
-    _lib.check(getattr(_lib.load(), name)(*args), name)
-
-
 def _slice_of(g, c0, c1, C):
     return None if g is None else (g if (c0 == 0 and c1 == C) else g[:, c0:c1].contiguous())
 
@@ -164,10 +160,10 @@ class BnReluFn(torch.autograd.Function):
         part = _bn_partial(lib, rows, C, dev)
         with torch.cuda.device(dev), _lib.timed("bn_relu_fwd", dev):
             for c0, c1 in _slices(C):
-                _abi("simamba_bn_relu_fwd", _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(w, c0),
-                     _off(b, c0), _off(running_mean, c0), _off(running_var, c0), float(momentum), float(eps),
-                     int(bool(training)), _off(y, c0), _off(mean, c0), _off(invstd, c0), part.data_ptr(), rows, c1 - c0,
-                     C, code, _lib.stream_ptr(dev))
+                _lib.call("simamba_bn_relu_fwd", _off(xc, c0), _slice_of(g, c0, c1, C), int(group), _off(w, c0),
+                          _off(b, c0), _off(running_mean, c0), _off(running_var, c0), float(momentum), float(eps),
+                          int(bool(training)), _off(y, c0), _off(mean, c0), _off(invstd, c0), part, rows, c1 - c0,
+                          C, code, device=dev)
         ctx.save_for_backward(xc, g, w, b, mean, invstd)
         ctx.meta = (int(group), bool(training), code, _dtypes(x, gterm, weight, bias))
         ctx.part = part
@@ -185,9 +181,9 @@ class BnReluFn(torch.autograd.Function):
         db = torch.empty(C, device=dev, dtype=torch.float32)
 
         def one(c0, c1, gsl, dg, dgroup):
-            _abi("simamba_bn_relu_bwd", _off(dyc, c0), _off(xc, c0), _lib.ptr(gsl), group, _off(w, c0), _off(b, c0),
-                 _off(mean, c0), _off(invstd, c0), _off(dx, c0), _lib.ptr(dg), dgroup, _off(dw, c0), _off(db, c0),
-                 ctx.part.data_ptr(), rows, c1 - c0, C, code, int(training), _lib.stream_ptr(dev))
+            _lib.call("simamba_bn_relu_bwd", _off(dyc, c0), _off(xc, c0), gsl, group, _off(w, c0), _off(b, c0),
+                      _off(mean, c0), _off(invstd, c0), _off(dx, c0), dg, dgroup, _off(dw, c0), _off(db, c0),
+                      ctx.part, rows, c1 - c0, C, code, int(training), device=dev)
         with torch.cuda.device(dev), _lib.timed("bn_relu_bwd", dev):
             dgt = _bn_dx_slices(xc, g, group, one)
         return _bn_grads(dtypes, dx, dgt, dw, db)
@@ -197,47 +193,46 @@ class BnReluFn(torch.autograd.Function):
 def bn_stats_local(xc, g, group, stats, part):
     """This rank's (count, mean, M2) per channel of xc (rows, C) (+ g[row // group]) into ``stats`` (3, C) float64."""
     rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    code, dev = _lib.dtype_code(xc.dtype), xc.device
     for c0, c1 in _slices(C):
-        _abi("simamba_bn_stats_local", _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(stats, c0), C,
-             part.data_ptr(), rows, c1 - c0, C, code, st)
+        _lib.call("simamba_bn_stats_local", _off(xc, c0), _slice_of(g, c0, c1, C), int(group), _off(stats, c0), C,
+                  part, rows, c1 - c0, C, code, device=dev)
 
 
 def bn_stats_merge(gathered, running_mean, running_var, momentum, eps, mean, invstd, count):
     """(W, 3, C) float64 blocks of all ranks -> mean, invstd (C) float32, count (1) float64, running statistics."""
     world, _, C = gathered.shape
-    _abi("simamba_bn_stats_merge", gathered.data_ptr(), world, _lib.ptr(running_mean), _lib.ptr(running_var),
-         float(momentum), float(eps), mean.data_ptr(), invstd.data_ptr(), count.data_ptr(), C,
-         _lib.stream_ptr(gathered.device))
+    _lib.call("simamba_bn_stats_merge", gathered, world, running_mean, running_var, float(momentum), float(eps),
+              mean, invstd, count, C, device=gathered.device)
 
 
 def bn_relu_apply(xc, g, group, w, b, mean, invstd, y):
     rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    code, dev = _lib.dtype_code(xc.dtype), xc.device
     for c0, c1 in _slices(C):
-        _abi("simamba_bn_relu_apply", _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group), _off(w, c0),
-             _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(y, c0), rows, c1 - c0, C, code, st)
+        _lib.call("simamba_bn_relu_apply", _off(xc, c0), _slice_of(g, c0, c1, C), int(group), _off(w, c0),
+                  _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(y, c0), rows, c1 - c0, C, code, device=dev)
 
 
 def bn_relu_bwd_sums(dyc, xc, g, group, w, b, mean, invstd, sums, part):
     """This rank's sum dy*mask (``sums[0]``) and sum dy*mask*xhat (``sums[1]``); ``sums`` (2, C) float32."""
     rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    code, dev = _lib.dtype_code(xc.dtype), xc.device
     for c0, c1 in _slices(C):
-        _abi("simamba_bn_relu_bwd_sums", _off(dyc, c0), _off(xc, c0), _lib.ptr(_slice_of(g, c0, c1, C)), int(group),
-             _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(sums[1], c0), _off(sums[0], c0),
-             part.data_ptr(), rows, c1 - c0, C, code, st)
+        _lib.call("simamba_bn_relu_bwd_sums", _off(dyc, c0), _off(xc, c0), _slice_of(g, c0, c1, C), int(group),
+                  _off(w, c0), _off(b, c0), _off(mean, c0), _off(invstd, c0), _off(sums[1], c0), _off(sums[0], c0),
+                  part, rows, c1 - c0, C, code, device=dev)
 
 
 def bn_relu_bwd_dx(dyc, xc, g, group, w, b, mean, invstd, sums, count, dx):
     """dx with the sums and the row count of ALL ranks; returns the gradient of g (rows / group, C) float32 or None."""
     rows, C = xc.shape
-    code, st = _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device)
+    code, dev = _lib.dtype_code(xc.dtype), xc.device
 
     def one(c0, c1, gsl, dg, dgroup):
-        _abi("simamba_bn_relu_bwd_dx", _off(dyc, c0), _off(xc, c0), _lib.ptr(gsl), int(group), _off(w, c0), _off(b, c0),
-             _off(mean, c0), _off(invstd, c0), _off(sums[1], c0), _off(sums[0], c0), count.data_ptr(), _off(dx, c0),
-             _lib.ptr(dg), dgroup, rows, c1 - c0, C, code, st)
+        _lib.call("simamba_bn_relu_bwd_dx", _off(dyc, c0), _off(xc, c0), gsl, int(group), _off(w, c0), _off(b, c0),
+                  _off(mean, c0), _off(invstd, c0), _off(sums[1], c0), _off(sums[0], c0), count, _off(dx, c0),
+                  dg, dgroup, rows, c1 - c0, C, code, device=dev)
     return _bn_dx_slices(xc, g, group, one)
 
 
@@ -370,9 +365,7 @@ class GroupMaxFn(torch.autograd.Function):
         code = _lib.dtype_code(xc.dtype)
         out = torch.empty(groups, C, device=dev, dtype=xc.dtype)
         idx = torch.empty(groups, C, device=dev, dtype=torch.uint8)
-        with torch.cuda.device(dev):
-            _abi("simamba_group_max_fwd", xc.data_ptr(), out.data_ptr(), idx.data_ptr(), groups, n, C, code,
-                 _lib.stream_ptr(dev))
+        _lib.call("simamba_group_max_fwd", xc, out, idx, groups, n, C, code, device=dev)
         ctx.save_for_backward(idx)
         ctx.meta = (groups, n, C, code, xc.dtype)
         return out
@@ -383,9 +376,7 @@ class GroupMaxFn(torch.autograd.Function):
         groups, n, C, code, dtype = ctx.meta
         d = dout.to(dtype).contiguous()
         dx = torch.empty(groups, n, C, device=d.device, dtype=dtype)
-        with torch.cuda.device(d.device):
-            _abi("simamba_group_max_bwd", d.data_ptr(), idx.data_ptr(), dx.data_ptr(), groups, n, C, code,
-                 _lib.stream_ptr(d.device))
+        _lib.call("simamba_group_max_bwd", d, idx, dx, groups, n, C, code, device=d.device)
         return dx
 
 
@@ -431,9 +422,7 @@ class TokenLinearGroupMaxFn(torch.autograd.Function):
         code = _lib.dtype_code(y.dtype)
         out = torch.empty(groups, cout, device=dev, dtype=y.dtype)
         idx = torch.empty(groups, cout, device=dev, dtype=torch.uint8)
-        with torch.cuda.device(dev):
-            _abi("simamba_group_max_fwd", y.data_ptr(), out.data_ptr(), idx.data_ptr(), groups, n, cout, code,
-                 _lib.stream_ptr(dev))
+        _lib.call("simamba_group_max_fwd", y, out, idx, groups, n, cout, code, device=dev)
         ctx.save_for_backward(x, weight, idx)
         ctx.meta = (groups, int(n), code, y.dtype, bias is not None)
         return out
@@ -446,22 +435,18 @@ class TokenLinearGroupMaxFn(torch.autograd.Function):
         dev = dout.device
         d = dout.to(io).contiguous()
         dx = dw = db = None
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            if ctx.needs_input_grad[0]:
-                w = weight.detach().to(io).contiguous()
-                dx = torch.empty(groups * n, cin, device=dev, dtype=io)
-                _abi("simamba_max_linear_bwd_dx", d.data_ptr(), idx.data_ptr(), w.data_ptr(), dx.data_ptr(), groups, n,
-                     cin, cout, code, st)
-                dx = dx.to(x.dtype)
-            if ctx.needs_input_grad[1]:
-                xc = x.detach().to(io).contiguous()
-                slabs = _lib.load().simamba_max_linear_bwd_slabs(groups, cin)
-                part = torch.empty(slabs, cout, cin, device=dev, dtype=torch.float32)
-                dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
-                _abi("simamba_max_linear_bwd_dw", d.data_ptr(), idx.data_ptr(), xc.data_ptr(), dw.data_ptr(),
-                     part.data_ptr(), groups, n, cin, cout, code, st)
-                dw = dw.to(weight.dtype)
+        if ctx.needs_input_grad[0]:
+            w = weight.detach().to(io).contiguous()
+            dx = torch.empty(groups * n, cin, device=dev, dtype=io)
+            _lib.call("simamba_max_linear_bwd_dx", d, idx, w, dx, groups, n, cin, cout, code, device=dev)
+            dx = dx.to(x.dtype)
+        if ctx.needs_input_grad[1]:
+            xc = x.detach().to(io).contiguous()
+            slabs = _lib.load().simamba_max_linear_bwd_slabs(groups, cin)
+            part = torch.empty(slabs, cout, cin, device=dev, dtype=torch.float32)
+            dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
+            _lib.call("simamba_max_linear_bwd_dw", d, idx, xc, dw, part, groups, n, cin, cout, code, device=dev)
+            dw = dw.to(weight.dtype)
         if has_bias and ctx.needs_input_grad[2]:
             db = d.sum(0, dtype=torch.float32).to(weight.dtype)          # over the patches, not the points
         return dx, dw, db, None

@@ -35,7 +35,6 @@ def sample_farthest_points(points, K, lengths=None, start_idx=None):
     ``idx`` are -1 and the remaining ``centers`` 0 (pytorch3d's padding).  ``start_idx`` (B,): the first pick of every
     cloud, ``0 <= start_idx[b] < lengths[b]``, instead of point 0."""
     _lib.require_gpu(points, "sample_farthest_points")
-    lib = _lib.load()
     p = points.detach().float().contiguous()
     B, N, F = p.shape
     if F != 3:
@@ -44,10 +43,8 @@ def sample_farthest_points(points, K, lengths=None, start_idx=None):
     st = _per_cloud(start_idx, B, p.device, "sample_farthest_points: start_idx")
     idx = torch.empty(B, K, device=p.device, dtype=torch.int64)
     centers = torch.empty(B, K, 3, device=p.device, dtype=torch.float32)
-    with torch.cuda.device(p.device), _lib.timed("fps", p.device):
-        rc = lib.simamba_farthest_point_sample_ex(_lib.ptr(p), _lib.ptr(ln), _lib.ptr(st), _lib.ptr(idx),
-                                                  _lib.ptr(centers), B, N, int(K), _lib.stream_ptr(p.device))
-    _lib.check(rc, "simamba_farthest_point_sample_ex")
+    _lib.call("simamba_farthest_point_sample_ex", p, ln, st, idx, centers, B, N, int(K), device=p.device,
+              time_as="fps")
     return centers.to(points.dtype), idx
 
 
@@ -57,7 +54,6 @@ def knn_group(centers, points, K, lengths=None, center_lengths=None):
     the point count of every cloud; with fewer than K points the first ``lengths[b]`` slots of a row are filled and the
     rest is 0.  ``center_lengths`` (B,): the number of centre rows of every cloud; the rows beyond it are 0."""
     _lib.require_gpu(points, "knn_group")
-    lib = _lib.load()
     p = points.detach().float().contiguous()
     c = centers.detach().float().contiguous()
     B, N, _ = p.shape
@@ -65,8 +61,5 @@ def knn_group(centers, points, K, lengths=None, center_lengths=None):
     ln = _per_cloud(lengths, B, p.device, "knn_group: lengths")
     lc = _per_cloud(center_lengths, B, p.device, "knn_group: center_lengths")
     idx = torch.empty(B, G, int(K), device=p.device, dtype=torch.int64)
-    with torch.cuda.device(p.device), _lib.timed("knn_group", p.device):
-        rc = lib.simamba_knn_group_ex(_lib.ptr(p), _lib.ptr(c), _lib.ptr(ln), _lib.ptr(lc), _lib.ptr(idx), B, N, G,
-                                      int(K), _lib.stream_ptr(p.device))
-    _lib.check(rc, "simamba_knn_group_ex")
+    _lib.call("simamba_knn_group_ex", p, c, ln, lc, idx, B, N, G, int(K), device=p.device, time_as="knn_group")
     return idx

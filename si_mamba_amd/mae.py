@@ -46,64 +46,34 @@ CHAMFER_SMALL_MAX = 64       # points per set of the one-wave kernels (csrc/cham
 
 
 class ChamferFn(torch.autograd.Function):
-    """Two routes.  Sets of up to 64 points whose ``gt`` needs no gradient (the MAE patch loss) run the one-wave
-    kernels; everything else, up to 8192 points per set, the tiled kernels, which also differentiate ``gt``."""
+    """The one-wave kernels (csrc/chamfer.hip): sets of up to 64 points whose ``gt`` needs no gradient (the MAE patch
+    loss).  Everything else, up to 8192 points per set, runs the tiled kernels (ChamferRaggedFn)."""
 
     @staticmethod
     def forward(ctx, pred, gt):
         _lib.require_gpu(pred, "chamfer_distance")
-        lib = _lib.load()
+        _lib.count("chamfer_small")
         p = pred.float().contiguous()
         g = gt.detach().float().contiguous()
         pairs, n, _ = p.shape
         m = g.shape[1]
         dev = p.device
-        ctx.small = n <= CHAMFER_SMALL_MAX and m <= CHAMFER_SMALL_MAX and not ctx.needs_input_grad[1]
-        ctx.in_dtype, ctx.gt_dtype = pred.dtype, gt.dtype
+        ctx.in_dtype = pred.dtype
         dist = torch.empty(pairs, device=dev, dtype=torch.float32)
-        if ctx.small:
-            _lib.count("chamfer_small")
-            i1 = torch.empty(pairs, n, device=dev, dtype=torch.uint8)
-            i2 = torch.empty(pairs, m, device=dev, dtype=torch.uint8)
-            with torch.cuda.device(dev):
-                rc = lib.simamba_chamfer_fwd(p.data_ptr(), g.data_ptr(), dist.data_ptr(), i1.data_ptr(), i2.data_ptr(),
-                                             pairs, n, m, _lib.stream_ptr(dev))
-            _lib.check(rc, "simamba_chamfer_fwd")
-        else:
-            _lib.count("chamfer_large")
-            i1 = torch.empty(pairs, n, device=dev, dtype=torch.int32)
-            i2 = torch.empty(pairs, m, device=dev, dtype=torch.int32)
-            d1 = torch.empty(pairs, n, device=dev, dtype=torch.float32)
-            d2 = torch.empty(pairs, m, device=dev, dtype=torch.float32)
-            with torch.cuda.device(dev):
-                rc = lib.simamba_chamfer_large_fwd(p.data_ptr(), g.data_ptr(), dist.data_ptr(), i1.data_ptr(),
-                                                   i2.data_ptr(), d1.data_ptr(), d2.data_ptr(), pairs, n, m,
-                                                   _lib.stream_ptr(dev))
-            _lib.check(rc, "simamba_chamfer_large_fwd")
+        i1 = torch.empty(pairs, n, device=dev, dtype=torch.uint8)
+        i2 = torch.empty(pairs, m, device=dev, dtype=torch.uint8)
+        _lib.call("simamba_chamfer_fwd", p, g, dist, i1, i2, pairs, n, m, device=dev)
         ctx.save_for_backward(p, g, i1, i2)
         return dist
 
     @staticmethod
     def backward(ctx, ddist):
         p, g, i1, i2 = ctx.saved_tensors
-        lib = _lib.load()
         pairs, n, _ = p.shape
-        m = g.shape[1]
         dd = ddist.float().contiguous()
-        if ctx.small:
-            dp = torch.empty_like(p)
-            with torch.cuda.device(p.device):
-                rc = lib.simamba_chamfer_bwd(p.data_ptr(), g.data_ptr(), dd.data_ptr(), i1.data_ptr(), i2.data_ptr(),
-                                             dp.data_ptr(), pairs, n, m, _lib.stream_ptr(p.device))
-            _lib.check(rc, "simamba_chamfer_bwd")
-            return dp.to(ctx.in_dtype), None
-        dp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
-        dg = torch.empty_like(g) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(p.device):
-            rc = lib.simamba_chamfer_large_bwd(p.data_ptr(), g.data_ptr(), dd.data_ptr(), i1.data_ptr(), i2.data_ptr(),
-                                               _lib.ptr(dp), _lib.ptr(dg), pairs, n, m, _lib.stream_ptr(p.device))
-        _lib.check(rc, "simamba_chamfer_large_bwd")
-        return (None if dp is None else dp.to(ctx.in_dtype)), (None if dg is None else dg.to(ctx.gt_dtype))
+        dp = torch.empty_like(p)
+        _lib.call("simamba_chamfer_bwd", p, g, dd, i1, i2, dp, pairs, n, g.shape[1], device=p.device)
+        return dp.to(ctx.in_dtype), None
 
 
 _CHAMFER_REDUCTIONS = {"mean": 0, "sum": 1, None: 2}
@@ -118,14 +88,12 @@ def _pair_lengths(t, pairs, device, what):
 
 class ChamferRaggedFn(torch.autograd.Function):
     """The tiled kernels with per-pair lengths, norm 1 or 2, mean / sum / no point reduction and one-way matching
-    (simamba_chamfer_ragged_*).  Returns dist (pairs,), or with no reduction d1 (pairs, n) and, unless one-way,
-    d2 (pairs, m)."""
+    (simamba_chamfer_ragged_*; with no lengths, norm 2, mean and both ways exactly simamba_chamfer_large_*).  Returns
+    dist (pairs,), or with no reduction d1 (pairs, n) and, unless one-way, d2 (pairs, m)."""
 
     @staticmethod
     def forward(ctx, pred, gt, xlen, ylen, norm, reduction, one_way):
         _lib.require_gpu(pred, "chamfer_distance")
-        lib = _lib.load()
-        _lib.count("chamfer_ragged")
         p = pred.float().contiguous()
         g = gt.detach().float().contiguous()
         pairs, n, _ = p.shape
@@ -138,12 +106,8 @@ class ChamferRaggedFn(torch.autograd.Function):
         d1 = torch.empty(pairs, n, device=dev, dtype=torch.float32)
         i2 = None if one_way else torch.empty(pairs, m, device=dev, dtype=torch.int32)
         d2 = None if one_way else torch.empty(pairs, m, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            rc = lib.simamba_chamfer_ragged_fwd(p.data_ptr(), g.data_ptr(), _lib.ptr(xlen), _lib.ptr(ylen),
-                                                _lib.ptr(dist), i1.data_ptr(), _lib.ptr(i2), d1.data_ptr(),
-                                                _lib.ptr(d2), pairs, n, m, norm, reduction, int(one_way), 0,
-                                                _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_chamfer_ragged_fwd")
+        _lib.call("simamba_chamfer_ragged_fwd", p, g, xlen, ylen, dist, i1, i2, d1, d2, pairs, n, m, norm, reduction,
+                  int(one_way), 0, device=dev)
         ctx.save_for_backward(p, g, i1, i2, xlen, ylen)
         if reduction != 2:
             return dist
@@ -153,7 +117,6 @@ class ChamferRaggedFn(torch.autograd.Function):
     def backward(ctx, *grads):
         p, g, i1, i2, xlen, ylen = ctx.saved_tensors
         norm, reduction, one_way = ctx.mode
-        lib = _lib.load()
         pairs, n, _ = p.shape
         m = g.shape[1]
         up = [None if t is None else t.float().contiguous() for t in grads]
@@ -168,12 +131,8 @@ class ChamferRaggedFn(torch.autograd.Function):
                 dd2 = torch.zeros(pairs, m, device=p.device, dtype=torch.float32)
         dp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
         dg = torch.empty_like(g) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(p.device):
-            rc = lib.simamba_chamfer_ragged_bwd(p.data_ptr(), g.data_ptr(), _lib.ptr(xlen), _lib.ptr(ylen),
-                                                _lib.ptr(dd), _lib.ptr(dd1), _lib.ptr(dd2), i1.data_ptr(),
-                                                _lib.ptr(i2), _lib.ptr(dp), _lib.ptr(dg), pairs, n, m, norm, reduction,
-                                                one_way, 0, _lib.stream_ptr(p.device))
-        _lib.check(rc, "simamba_chamfer_ragged_bwd")
+        _lib.call("simamba_chamfer_ragged_bwd", p, g, xlen, ylen, dd, dd1, dd2, i1, i2, dp, dg, pairs, n, m, norm,
+                  reduction, one_way, 0, device=p.device)
         return (None if dp is None else dp.to(ctx.in_dtype)), (None if dg is None else dg.to(ctx.gt_dtype)), \
             None, None, None, None, None
 
@@ -205,8 +164,11 @@ def chamfer_distance(pred, gt, *, x_lengths=None, y_lengths=None, weights=None, 
             raise ValueError(f"chamfer_distance: weights must be a tensor of shape ({pairs},)")
         if not weights.dtype.is_floating_point:
             raise TypeError(f"chamfer_distance: weights must hold floats, got {weights.dtype}")
-    if xlen is None and ylen is None and weights is None and norm == 2 and point_reduction == "mean" and not one_way:
+    dense = xlen is None and ylen is None and weights is None and norm == 2 and point_reduction == "mean" \
+        and not one_way
+    if dense and max(pred.shape[1], gt.shape[1]) <= CHAMFER_SMALL_MAX and not gt.requires_grad:
         return ChamferFn.apply(pred, gt)
+    _lib.count("chamfer_large" if dense else "chamfer_ragged")
     out = ChamferRaggedFn.apply(pred, gt, xlen, ylen, norm, _CHAMFER_REDUCTIONS[point_reduction], one_way)
     if point_reduction is not None:
         return out if weights is None else out * weights

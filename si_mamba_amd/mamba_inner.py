@@ -85,14 +85,11 @@ def tokens_times_weight(x, w):
     through the library."""
     if (x.dtype in (torch.bfloat16, torch.float32) and w.dtype == x.dtype and x.is_cuda and x.dim() == 3
             and x.is_contiguous() and in_proj_hand_ok(x, w)):
-        lib = _lib.load()
         Bsz, L, C = x.shape
         wcc = w.contiguous()
         out = torch.empty(Bsz, w.shape[0], L, device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device), _lib.timed("in_proj_fwd", x.device):
-            rc = lib.simamba_in_proj_fwd(x.data_ptr(), wcc.data_ptr(), out.data_ptr(), Bsz, L, C, w.shape[0],
-                                         _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device))
-        _lib.check(rc, "simamba_in_proj_fwd")
+        _lib.call("simamba_in_proj_fwd", x, wcc, out, Bsz, L, C, w.shape[0], _lib.dtype_code(x.dtype),
+                  device=x.device, time_as="in_proj_fwd")
         _lib.count("in_proj_hand")
         return out
     return _wx(w, x.transpose(1, 2))
@@ -129,23 +126,18 @@ def xdt_proj_fwd(x, wx, wdt, conv=None, want_delta=True):
     (simamba_selective_scan_dt_fwd).  ``conv=(w (D, 4) fp32, bias (D) or None, out (B, D, L))``: the causal depthwise
     conv1d + SiLU is applied to x on the way in and its result written to ``out``.  No autograd: called from inside
     MambaInnerFn.forward, whose backward differentiates the products itself."""
-    lib = _lib.load()
     Bsz, D, L = x.shape
     S, R = wx.shape[0], wdt.shape[1]
     wxc, wdc = wx.contiguous(), wdt.contiguous()
     x_dbl = torch.empty(Bsz, L, S, device=x.device, dtype=x.dtype)
     delta = torch.empty(Bsz, D, L, device=x.device, dtype=x.dtype) if want_delta else None
-    with torch.cuda.device(x.device), _lib.timed("xdt_proj_fwd", x.device):
-        if conv is None:
-            rc = lib.simamba_xdt_proj_fwd(x.data_ptr(), wxc.data_ptr(), wdc.data_ptr(), x_dbl.data_ptr(),
-                                          _lib.ptr(delta), Bsz, D, L, S, R, _lib.dtype_code(x.dtype), x.stride(0),
-                                          _lib.stream_ptr(x.device))
-        else:
-            cw, cb, out = conv
-            rc = lib.simamba_conv_xdt_proj_fwd(x.data_ptr(), cw.data_ptr(), _lib.ptr(cb), wxc.data_ptr(), wdc.data_ptr(),
-                                               out.data_ptr(), x_dbl.data_ptr(), _lib.ptr(delta), Bsz, D, L, S, R,
-                                               _lib.dtype_code(x.dtype), x.stride(0), _lib.stream_ptr(x.device))
-    _lib.check(rc, "simamba_xdt_proj_fwd")
+    if conv is None:
+        _lib.call("simamba_xdt_proj_fwd", x, wxc, wdc, x_dbl, delta, Bsz, D, L, S, R, _lib.dtype_code(x.dtype),
+                  x.stride(0), device=x.device, time_as="xdt_proj_fwd")
+    else:
+        cw, cb, out = conv
+        _lib.call("simamba_conv_xdt_proj_fwd", x, cw, cb, wxc, wdc, out, x_dbl, delta, Bsz, D, L, S, R,
+                  _lib.dtype_code(x.dtype), x.stride(0), device=x.device, time_as="xdt_proj_fwd")
     return x_dbl, delta
 
 
@@ -154,7 +146,6 @@ class MambaInnerFn(torch.autograd.Function):
     def forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, out_proj_w, out_proj_b, A, D, delta_bias,
                 dt_rank, d_state, grad_mode=True):
         _lib.require_gpu(xz, "mamba_inner_fn")
-        lib = _lib.load()
         if xz.stride(2) != 1 or xz.stride(1) != xz.shape[2]:
             xz = xz.contiguous()
         io = xz.dtype
@@ -164,7 +155,6 @@ class MambaInnerFn(torch.autograd.Function):
         R, N = dt_rank, d_state
         S = R + 2 * N
         dev = xz.device
-        stream = _lib.stream_ptr(dev)
         xbs = xz.stride(0)
         x_in, z = xz[:, :Dm], xz[:, Dm:]
 
@@ -200,10 +190,8 @@ class MambaInnerFn(torch.autograd.Function):
             _lib.count("xdt_conv_fused")
         else:
             fuse_dt = False
-            with torch.cuda.device(dev), _lib.timed("conv1d_fwd", dev):
-                rc = lib.simamba_causal_conv1d_fwd(x_in.data_ptr(), cw.data_ptr(), _lib.ptr(cb), x_conv.data_ptr(),
-                                                   Bsz, Dm, L, W, 1, code, xbs, stream)
-            _lib.check(rc, "simamba_causal_conv1d_fwd")
+            _lib.call("simamba_causal_conv1d_fwd", x_in, cw, cb, x_conv, Bsz, Dm, L, W, 1, code, xbs,
+                      device=dev, time_as="conv1d_fwd")
             if xdt_proj_fused_ok(x_conv, xw_c, dtw_c):
                 x_dbl, delta = xdt_proj_fwd(x_conv, xw_c, dtw_c)
                 _lib.count("xdt_fused")
@@ -217,21 +205,15 @@ class MambaInnerFn(torch.autograd.Function):
 
         y = torch.empty(Bsz, Dm, L, device=dev, dtype=io)
         dtw_k = dtw_c.contiguous() if fuse_dt else None
-        with torch.cuda.device(dev), _lib.timed("scan_fwd", dev):
-            if fuse_dt:
-                _lib.count("scan_dt_fwd")
-                rc = lib.simamba_selective_scan_dt_fwd(
-                    x_conv.data_ptr(), x_dbl.data_ptr(), dtw_k.data_ptr(), Af.data_ptr(), _lib.ptr(Df),
-                    z.data_ptr(), _lib.ptr(bf), y.data_ptr(), _lib.ptr(x_ckpt), None,
-                    Bsz, Dm, L, N, R, code, xbs, x_dbl.stride(0), x_dbl.stride(1),
-                    ckpt_step, _lib.current_scan_variant(), stream)
-            else:
-                rc = lib.simamba_selective_scan_fwd(
-                    x_conv.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bv.data_ptr(), Cv.data_ptr(), _lib.ptr(Df),
-                    z.data_ptr(), _lib.ptr(bf), y.data_ptr(), _lib.ptr(x_ckpt), None,
-                    Bsz, Dm, L, N, code, 1, xbs, x_dbl.stride(0), 1, x_dbl.stride(1),
-                    ckpt_step, _lib.current_scan_variant(), stream)
-        _lib.check(rc, "simamba_selective_scan_fwd")
+        if fuse_dt:
+            _lib.count("scan_dt_fwd")
+            _lib.call("simamba_selective_scan_dt_fwd", x_conv, x_dbl, dtw_k, Af, Df, z, bf, y, x_ckpt, None,
+                      Bsz, Dm, L, N, R, code, xbs, x_dbl.stride(0), x_dbl.stride(1),
+                      ckpt_step, _lib.current_scan_variant(), device=dev, time_as="scan_fwd")
+        else:
+            _lib.call("simamba_selective_scan_fwd", x_conv, delta, Af, Bv, Cv, Df, z, bf, y, x_ckpt, None,
+                      Bsz, Dm, L, N, code, 1, xbs, x_dbl.stride(0), 1, x_dbl.stride(1),
+                      ckpt_step, _lib.current_scan_variant(), device=dev, time_as="scan_fwd")
 
         if no_out:
             out = y
@@ -262,7 +244,6 @@ class MambaInnerFn(torch.autograd.Function):
         Dm = twoD // 2
         S = R + 2 * N
         dev = xz.device
-        stream = _lib.stream_ptr(dev)
         xbs = xz.stride(0)
         dout = dout.to(io)
         f32 = dict(device=dev, dtype=torch.float32)
@@ -291,23 +272,16 @@ class MambaInnerFn(torch.autograd.Function):
         flags, ws, nws = _lib.det_args(lib.simamba_scan_bwd_workspace_floats, Bsz, Dm, L, N,
                                        _lib.CKPT_SEQ if ctx.dtw_k is not None else ctx.ckpt_step, device=dev)
         _lib.count("scan_bwd_det" if flags else "scan_bwd_atomic")
-        with torch.cuda.device(dev), _lib.timed("scan_bwd", dev):
-            if ctx.dtw_k is not None:
-                rc = lib.simamba_selective_scan_dt_bwd_ex(
-                    x_conv.data_ptr(), x_dbl.data_ptr(), ctx.dtw_k.data_ptr(), Af.data_ptr(), _lib.ptr(Df),
-                    z.data_ptr(), _lib.ptr(bf), dy.data_ptr(), _lib.ptr(x_ckpt),
-                    du.data_ptr(), ddelta.data_ptr(), dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), _lib.ptr(dD),
-                    dz.data_ptr(), _lib.ptr(dbias), Bsz, Dm, L, N, R, code,
-                    xbs, dxz.stride(0), x_dbl.stride(0), x_dbl.stride(1), flags, _lib.ptr(ws), nws, stream)
-            else:
-                rc = lib.simamba_selective_scan_bwd_ex(
-                    x_conv.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bv.data_ptr(), Cv.data_ptr(), _lib.ptr(Df),
-                    z.data_ptr(), _lib.ptr(bf), dy.data_ptr(), _lib.ptr(x_ckpt),
-                    du.data_ptr(), ddelta.data_ptr(), dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), _lib.ptr(dD),
-                    dz.data_ptr(), _lib.ptr(dbias), Bsz, Dm, L, N, code, 1,
-                    xbs, dxz.stride(0), x_dbl.stride(0), 1, x_dbl.stride(1), ctx.ckpt_step, flags, _lib.ptr(ws), nws,
-                    stream)
-        _lib.check(rc, "simamba_selective_scan_bwd_ex")
+        if ctx.dtw_k is not None:
+            _lib.call("simamba_selective_scan_dt_bwd_ex", x_conv, x_dbl, ctx.dtw_k, Af, Df, z, bf, dy, x_ckpt,
+                      du, ddelta, dA, dB, dC, dD, dz, dbias, Bsz, Dm, L, N, R, code,
+                      xbs, dxz.stride(0), x_dbl.stride(0), x_dbl.stride(1), flags, ws, nws,
+                      device=dev, time_as="scan_bwd")
+        else:
+            _lib.call("simamba_selective_scan_bwd_ex", x_conv, delta, Af, Bv, Cv, Df, z, bf, dy, x_ckpt,
+                      du, ddelta, dA, dB, dC, dD, dz, dbias, Bsz, Dm, L, N, code, 1,
+                      xbs, dxz.stride(0), x_dbl.stride(0), 1, x_dbl.stride(1), ctx.ckpt_step, flags, ws, nws,
+                      device=dev, time_as="scan_bwd")
 
         # dt_proj / x_proj
         dx_dbl = torch.empty(Bsz, L, S, device=dev, dtype=io)
@@ -329,12 +303,8 @@ class MambaInnerFn(torch.autograd.Function):
         dcb = dconv[Dm * W:] if cb is not None else None
         flags, ws, nws = _lib.det_args(lib.simamba_causal_conv1d_bwd_workspace_floats, Bsz, Dm, L, W, device=dev)
         _lib.count("conv1d_bwd_det" if flags else "conv1d_bwd_atomic")
-        with torch.cuda.device(dev), _lib.timed("conv1d_bwd", dev):
-            rc = lib.simamba_causal_conv1d_bwd_ex(xz.data_ptr(), cw.data_ptr(), _lib.ptr(cb), du.data_ptr(),
-                                                  dxz.data_ptr(), dcw.data_ptr(), _lib.ptr(dcb),
-                                                  Bsz, Dm, L, W, 1, code, xbs, dxz.stride(0), flags, _lib.ptr(ws), nws,
-                                                  stream)
-        _lib.check(rc, "simamba_causal_conv1d_bwd_ex")
+        _lib.call("simamba_causal_conv1d_bwd_ex", xz, cw, cb, du, dxz, dcw, dcb, Bsz, Dm, L, W, 1, code,
+                  xbs, dxz.stride(0), flags, ws, nws, device=dev, time_as="conv1d_bwd")
 
         t_cw, t_cb, t_xw, t_dtw, t_ow, t_A, t_D, t_b = ctx.param_dtypes
         return (dxz, dcw.to(t_cw), None if dcb is None else dcb.to(t_cb), d_x_w.to(t_xw), d_dt_w.to(t_dtw),

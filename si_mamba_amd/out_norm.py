@@ -19,6 +19,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from .add_norm import add_norm_bwd
 from .mamba_inner import _sum_bmm, tokens_times_weight
 
 
@@ -34,7 +35,6 @@ class OutProjAddLnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, out_w, residual, ln_w, ln_b, eps, rowscale, out_dtype, rms=False):
         _lib.require_gpu(y, "out_proj_add_ln_fn")
-        lib = _lib.load()
         Bsz, D, L = y.shape
         C = out_w.shape[0]
         dev = y.device
@@ -48,12 +48,9 @@ class OutProjAddLnFn(torch.autograd.Function):
         normed = torch.empty(Bsz, L, C, device=dev, dtype=out_dtype)
         mean = None if rms else torch.empty(Bsz * L, device=dev, dtype=torch.float32)      # RMSNorm has no mean
         rstd = torch.empty(Bsz * L, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("out_proj_add_rms_fwd" if rms else "out_proj_add_ln_fwd", dev):
-            rc = lib.simamba_out_proj_add_ln_fwd_ex(y.data_ptr(), wc.data_ptr(), _lib.ptr(res), _lib.ptr(rs),
-                                                    lw.data_ptr(), _lib.ptr(lb), res_out.data_ptr(), normed.data_ptr(),
-                                                    _lib.ptr(mean), rstd.data_ptr(), Bsz, D, L, C, float(eps),
-                                                    _lib.dtype_code(out_dtype), flags, _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_out_proj_add_ln_fwd_ex")
+        _lib.call("simamba_out_proj_add_ln_fwd_ex", y, wc, res, rs, lw, lb, res_out, normed, mean, rstd, Bsz, D, L, C,
+                  float(eps), _lib.dtype_code(out_dtype), flags, device=dev,
+                  time_as="out_proj_add_rms_fwd" if rms else "out_proj_add_ln_fwd")
         ctx.save_for_backward(y, wc, res_out, mean, rstd, lw, rs)
         ctx.meta = (Bsz, L, C, _lib.dtype_code(out_dtype), residual is not None,
                     None if residual is None else residual.dtype, ln_w.dtype, ln_b is not None, out_w.dtype, flags)
@@ -63,21 +60,12 @@ class OutProjAddLnFn(torch.autograd.Function):
     def backward(ctx, dnormed, dres_out):
         y, wc, res_out, mean, rstd, lw, rs = ctx.saved_tensors
         Bsz, L, C, ocode, has_res, res_dtype, lwdtype, has_bias, owdtype, flags = ctx.meta
-        lib = _lib.load()
         dev = y.device
         dn = dnormed.contiguous()
         dro = None if dres_out is None else dres_out.float().contiguous()
         dres = torch.empty(res_out.shape, device=dev, dtype=torch.float32) if has_res else None
         dhid = torch.empty(res_out.shape, device=dev, dtype=torch.bfloat16)     # gradient of the bf16 out_proj output
-        grid = lib.simamba_add_layer_norm_grid(Bsz, L)
-        part = torch.empty(grid, 2, C, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev), _lib.timed("add_rms_bwd" if flags else "add_ln_bwd", dev):
-            rc = lib.simamba_add_layer_norm_bwd_ex(dn.data_ptr(), _lib.ptr(dro), res_out.data_ptr(), _lib.ptr(mean),
-                                                   rstd.data_ptr(), lw.data_ptr(), _lib.ptr(rs), _lib.ptr(dres),
-                                                   dhid.data_ptr(), part.data_ptr(), Bsz, L, C, _lib.BF16, ocode,
-                                                   flags, _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_add_layer_norm_bwd_ex")
-        dwb = part[:, :1].sum(0) if flags else part.sum(0)                        # RMS: dweight half only
+        dwb = add_norm_bwd(dn, dro, res_out, mean, rstd, lw, rs, dres, dhid, Bsz, L, C, _lib.BF16, ocode, flags)
         dy = tokens_times_weight(dhid, wc.t())                                    # (B, D, L)
         d_out_w = _sum_bmm(dhid.transpose(1, 2), y.transpose(1, 2))               # (C, D)
         return (dy, d_out_w.to(owdtype), None if not has_res else dres.to(res_dtype), dwb[0].to(lwdtype),

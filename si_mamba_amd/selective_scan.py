@@ -32,7 +32,6 @@ class SelectiveScanFn(torch.autograd.Function):
     def forward(ctx, u, delta, A, B, C, D=None, z=None, delta_bias=None,
                 delta_softplus=False, return_last_state=False, grad_mode=True):
         _lib.require_gpu(u, "selective_scan_fn")
-        lib = _lib.load()
         io = u.dtype
         code = _lib.dtype_code(io)
         if A.is_complex():
@@ -66,14 +65,10 @@ class SelectiveScanFn(torch.autograd.Function):
                                            z_bs=0 if zc is None else zc.stride(0), bc_strides=Bc.stride())
         last = (torch.empty(batch, dim, N, device=u.device, dtype=torch.float32)
                 if return_last_state else None)
-        with torch.cuda.device(u.device), _lib.timed("scan_fwd", u.device):
-            rc = lib.simamba_selective_scan_fwd(
-                _lib.ptr(uc), _lib.ptr(dc), _lib.ptr(Ac), _lib.ptr(Bc), _lib.ptr(Cc), _lib.ptr(Dc),
-                _lib.ptr(zc), _lib.ptr(bc), _lib.ptr(out), _lib.ptr(x_ckpt), _lib.ptr(last),
-                batch, dim, L, N, code, int(bool(delta_softplus)),
-                0 if zc is None else zc.stride(0), Bc.stride(0), Bc.stride(1), Bc.stride(2),
-                ckpt_step, _lib.current_scan_variant(), _lib.stream_ptr(u.device))
-        _lib.check(rc, "simamba_selective_scan_fwd")
+        _lib.call("simamba_selective_scan_fwd", uc, dc, Ac, Bc, Cc, Dc, zc, bc, out, x_ckpt, last,
+                  batch, dim, L, N, code, int(bool(delta_softplus)),
+                  0 if zc is None else zc.stride(0), Bc.stride(0), Bc.stride(1), Bc.stride(2),
+                  ckpt_step, _lib.current_scan_variant(), device=u.device, time_as="scan_fwd")
         ctx.delta_softplus = bool(delta_softplus)
         ctx.ckpt_step = ckpt_step
         ctx.has = (D is not None, z is not None, delta_bias is not None)
@@ -104,16 +99,11 @@ class SelectiveScanFn(torch.autograd.Function):
         flags, ws, nws = _lib.det_args(lib.simamba_scan_bwd_workspace_floats, batch, dim, L, N, ctx.ckpt_step,
                                        device=uc.device)
         _lib.count("scan_bwd_det" if flags else "scan_bwd_atomic")
-        with torch.cuda.device(uc.device), _lib.timed("scan_bwd", uc.device):
-            rc = lib.simamba_selective_scan_bwd_ex(
-                _lib.ptr(uc), _lib.ptr(dc), _lib.ptr(Ac), _lib.ptr(Bc), _lib.ptr(Cc), _lib.ptr(Dc),
-                _lib.ptr(zc), _lib.ptr(bc), _lib.ptr(dout), _lib.ptr(x_ckpt),
-                _lib.ptr(du), _lib.ptr(ddelta), _lib.ptr(dA), _lib.ptr(dB), _lib.ptr(dC), _lib.ptr(dD),
-                _lib.ptr(dz), _lib.ptr(dbias), batch, dim, L, N, _lib.dtype_code(io),
-                int(ctx.delta_softplus), 0 if zc is None else zc.stride(0), 0,
-                Bc.stride(0), Bc.stride(1), Bc.stride(2), ctx.ckpt_step, flags, _lib.ptr(ws), nws,
-                _lib.stream_ptr(uc.device))
-        _lib.check(rc, "simamba_selective_scan_bwd_ex")
+        _lib.call("simamba_selective_scan_bwd_ex", uc, dc, Ac, Bc, Cc, Dc, zc, bc, dout, x_ckpt,
+                  du, ddelta, dA, dB, dC, dD, dz, dbias, batch, dim, L, N, _lib.dtype_code(io),
+                  int(ctx.delta_softplus), 0 if zc is None else zc.stride(0), 0,
+                  Bc.stride(0), Bc.stride(1), Bc.stride(2), ctx.ckpt_step, flags, ws, nws,
+                  device=uc.device, time_as="scan_bwd")
         dt_delta, dt_B, dt_C, dt_D, dt_z, dt_bias, dt_A = ctx.in_dtypes
         dB = dB.to(dt_B)
         dC = dC.to(dt_C)

@@ -38,15 +38,12 @@ class SeqGatherLastFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, idx32, inv32):
         _lib.require_gpu(x, "seq_gather_last")
-        lib = _lib.load()
         xc = x.contiguous()
         B, C, G = xc.shape
         L = idx32.shape[1]
         out = torch.empty(B, C, L, device=xc.device, dtype=xc.dtype)
-        with torch.cuda.device(xc.device), _lib.timed("seq_gather_fwd", xc.device):
-            rc = lib.simamba_seq_gather_fwd(xc.data_ptr(), idx32.data_ptr(), out.data_ptr(), B, C, G, L, 0,
-                                            _lib.dtype_code(xc.dtype), _lib.stream_ptr(xc.device))
-        _lib.check(rc, "simamba_seq_gather_fwd")
+        _lib.call("simamba_seq_gather_fwd", xc, idx32, out, B, C, G, L, 0, _lib.dtype_code(xc.dtype),
+                  device=xc.device, time_as="seq_gather_fwd")
         ctx.save_for_backward(inv32)
         ctx.meta = (B, C, G, L)
         return out
@@ -55,15 +52,12 @@ class SeqGatherLastFn(torch.autograd.Function):
     def backward(ctx, dout):
         (inv32,) = ctx.saved_tensors
         B, C, G, L = ctx.meta
-        lib = _lib.load()
         d = dout
         if d.stride(2) != 1 or d.stride(1) != L or d.stride(0) % 4:
             d = d.contiguous()
         din = torch.empty(B, C, G, device=d.device, dtype=d.dtype)
-        with torch.cuda.device(d.device), _lib.timed("seq_gather_bwd", d.device):
-            rc = lib.simamba_seq_gather_bwd(d.data_ptr(), inv32.data_ptr(), din.data_ptr(), B, C, G, L, L // G,
-                                            d.stride(0), _lib.dtype_code(d.dtype), _lib.stream_ptr(d.device))
-        _lib.check(rc, "simamba_seq_gather_bwd")
+        _lib.call("simamba_seq_gather_bwd", d, inv32, din, B, C, G, L, L // G, d.stride(0), _lib.dtype_code(d.dtype),
+                  device=d.device, time_as="seq_gather_bwd")
         return din, None, None
 
 

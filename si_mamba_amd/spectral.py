@@ -36,15 +36,11 @@ def _flags(symmetric=False, self_loop=False, binary=False, matrix_sym=False, sma
 
 def _knn_graph(points, k, alpha, flags):
     _lib.require_gpu(points, "create_graph")
-    lib = _lib.load()
     pts = points.detach().float().contiguous()
     B, G, F = pts.shape
     adj = torch.empty(B, G, G, device=pts.device, dtype=torch.float32)
     ws = torch.empty(256, device=pts.device, dtype=torch.uint8)
-    with torch.cuda.device(pts.device):
-        rc = lib.simamba_knn_graph(_lib.ptr(pts), _lib.ptr(adj), _lib.ptr(ws), ws.numel(), B, G, F, int(k),
-                                   float(alpha), flags, _lib.stream_ptr(pts.device))
-    _lib.check(rc, "simamba_knn_graph")
+    _lib.call("simamba_knn_graph", pts, adj, ws, ws.numel(), B, G, F, int(k), float(alpha), flags, device=pts.device)
     return adj
 
 
@@ -85,17 +81,10 @@ def _eig(adj, k, smallest, matrix_sym, want_all=True, want_order=False):
         nbytes = lib.simamba_laplacian_topk_workspace_bytes(B, G)
         ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
         _lib.count("spectral_large_g")
-        with torch.cuda.device(dev):
-            rc = lib.simamba_laplacian_topk_ex(_lib.ptr(a), _lib.ptr(vals), _lib.ptr(vecs), _lib.ptr(order),
-                                               _lib.ptr(ws), nbytes, B, G, int(k), flags | _lib.SPEC_LARGE_G,
-                                               _lib.stream_ptr(dev))
-        _lib.check(rc, "simamba_laplacian_topk_ex")
+        _lib.call("simamba_laplacian_topk_ex", a, vals, vecs, order, ws, nbytes, B, G, int(k),
+                  flags | _lib.SPEC_LARGE_G, device=dev)
         return vals, vecs, all_vals, all_vecs, order
-    with torch.cuda.device(dev):
-        rc = lib.simamba_laplacian_topk(_lib.ptr(a), _lib.ptr(vals), _lib.ptr(vecs), _lib.ptr(order),
-                                        _lib.ptr(all_vals), _lib.ptr(all_vecs), B, G, int(k),
-                                        flags, _lib.stream_ptr(dev))
-    _lib.check(rc, "simamba_laplacian_topk")
+    _lib.call("simamba_laplacian_topk", a, vals, vecs, order, all_vals, all_vecs, B, G, int(k), flags, device=dev)
     return vals, vecs, all_vals, all_vecs, order
 
 
@@ -113,13 +102,10 @@ def calc_top_k_eigenvalues_eigenvectors_symmetric(adj_matrices, k, smallest):
 def argsort_rows(vals):
     """(rows, n) fp32 -> (rows, n) int64 ascending argsort, ties by index (torch.sort at :820)."""
     _lib.require_gpu(vals, "argsort_rows")
-    lib = _lib.load()
     v = vals.detach().float().contiguous()
     rows, n = v.shape
     idx = torch.empty(rows, n, device=v.device, dtype=torch.int64)
-    with torch.cuda.device(v.device):
-        rc = lib.simamba_argsort_rows(_lib.ptr(v), _lib.ptr(idx), rows, n, _lib.stream_ptr(v.device))
-    _lib.check(rc, "simamba_argsort_rows")
+    _lib.call("simamba_argsort_rows", v, idx, rows, n, device=v.device)
     return idx
 
 
@@ -159,11 +145,8 @@ def spectral_order(center, knn_graph, alpha, k_top_eigenvectors, smallest=True, 
     nbytes = lib.simamba_spectral_workspace_bytes(B, G)
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     flags = _flags(symmetric, self_loop, binary, matrix_sym=(matrix != "laplacian"), smallest=smallest)
-    with torch.cuda.device(dev), _lib.timed("spectral_topk", dev):
-        rc = lib.simamba_spectral_topk(_lib.ptr(c), _lib.ptr(vals), _lib.ptr(vecs), _lib.ptr(order),
-                                       _lib.ptr(ws), nbytes, B, G, int(knn_graph), float(alpha), k, flags,
-                                       _lib.stream_ptr(dev))
-    _lib.check(rc, "simamba_spectral_topk")
+    _lib.call("simamba_spectral_topk", c, vals, vecs, order, ws, nbytes, B, G, int(knn_graph), float(alpha), k, flags,
+              device=dev, time_as="spectral_topk")
     return vals, vecs, order
 
 

@@ -20,6 +20,90 @@ def test_header_and_binding_agree():
     assert _declared() == sorted(_lib.SIGNATURES)
 
 
+def _declared_params():
+    """name -> the parameter declarations of every simamba_* prototype in the header, comments stripped."""
+    text = open(os.path.join(ROOT, "include", "simamba.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for name, params in re.findall(r"\b(simamba_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in out, name
+        params = [p.strip() for p in params.split(",")]
+        out[name] = [] if params == ["void"] else params
+    return out
+
+
+def _kind(ctype):
+    if ctype in (ctypes.c_void_p, ctypes.c_char_p):
+        return "pointer"
+    if ctype is ctypes.c_float:
+        return "float"
+    assert ctype in (ctypes.c_int, ctypes.c_uint, ctypes.c_longlong, ctypes.c_size_t), ctype
+    return "integer"
+
+
+def test_header_and_binding_agree_on_parameters():
+    """ctypes accepts surplus arguments silently and converts whatever argtypes says, so a binding that disagrees
+    with the header would first show on the device: count and kind (pointer / float / integer) of every parameter."""
+    declared = _declared_params()
+    assert sorted(declared) == sorted(_lib.SIGNATURES)
+    for name, params in declared.items():
+        argtypes = _lib.SIGNATURES[name][1]
+        assert len(params) == len(argtypes), name
+        for i, (param, ctype) in enumerate(zip(params, argtypes)):
+            want = "pointer" if "*" in param else "float" if re.match(r"(const\s+)?float\b", param) else "integer"
+            assert "double" not in param or "*" in param, (name, param)       # no by-value double in the ABI
+            assert _kind(ctype) == want, (name, i, param)
+    # every entry point _lib.call can launch takes the stream last
+    for name, params in declared.items():
+        if any("stream" in p for p in params):
+            assert re.fullmatch(r"void\s*\*\s*stream", params[-1]), name
+
+
+# direct calls that expand a sequence into the argument list: their arity is not countable from the source
+_STARRED_CALLS = {("_lib.py", "simamba_scan_seq_applicable")}
+
+
+def test_every_call_site_has_the_right_arity():
+    """Every C-ABI call in the package, from its source alone: _lib.call("simamba_x", ...) names a bound symbol with a
+    string literal and passes its arguments less the stream; a direct lib.simamba_x(...) call (the host-only queries)
+    passes all of them."""
+    import ast
+    pkg = os.path.join(ROOT, "si_mamba_amd")
+    sites, starred = 0, set()
+    for dp, _, files in os.walk(pkg):
+        for f in sorted(files):
+            if not f.endswith(".py"):
+                continue
+            path = os.path.join(dp, f)
+            for node in ast.walk(ast.parse(open(path).read(), path)):
+                if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)):
+                    continue
+                where = f"{os.path.relpath(path, pkg)}:{node.lineno}"
+                has_star = any(isinstance(a, ast.Starred) for a in node.args)
+                if node.func.attr == "call" and isinstance(node.func.value, ast.Name) and node.func.value.id == "_lib":
+                    name = node.args[0]
+                    assert isinstance(name, ast.Constant) and isinstance(name.value, str), where
+                    assert name.value in _lib.SIGNATURES, (where, name.value)
+                    assert not has_star, where
+                    assert {k.arg for k in node.keywords} <= {"device", "time_as"}, where
+                    assert "device" in {k.arg for k in node.keywords}, where
+                    # node.args holds the name and not the stream: positional arguments + 1 == len(argtypes)
+                    assert (len(node.args) - 1) + 1 == len(_lib.SIGNATURES[name.value][1]), (where, name.value)
+                    sites += 1
+                elif node.func.attr.startswith("simamba_"):
+                    name = node.func.attr
+                    assert name in _lib.SIGNATURES, (where, name)
+                    assert not node.keywords, where
+                    if has_star:
+                        starred.add((os.path.relpath(path, pkg), name))
+                    else:
+                        assert len(node.args) == len(_lib.SIGNATURES[name][1]), (where, name)
+                    sites += 1
+    assert starred == _STARRED_CALLS
+    assert sites >= 50, sites
+
+
 def test_library_exports_every_declared_symbol():
     assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
     lib = ctypes.CDLL(_lib.LIB_PATH)
