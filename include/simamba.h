@@ -590,6 +590,53 @@ int simamba_emd_fwd(const float* x, const float* y, int* assign, float* dist, in
                     long long pairs, int n, float eps, int max_rounds, void* stream);
 
 /*
+ * Debiased Sinkhorn divergence between pairs of point sets of unequal size (csrc/sinkhorn.hip), the entropic transport
+ * distance beside simamba_emd_fwd: uniform masses a = 1/nx, b = 1/ny, costs c_ij = (dx*dx + dy*dy) + dz*dz formed on
+ * the fly from LDS.  Per pair, diam2 = the squared diagonal of the bounding box of its nx + ny points (at least 1e-30);
+ * S = ceil(log2(1 / eps_rel)) scaling steps at eps_t = diam2 * 2^-t, t = 0 .. S-1, then `iters` steps at
+ * eps_fin = diam2 * eps_rel; one step, from g = 0:
+ *   f_i <- -eps log sum_j b_j exp((g_j - c_ij) / eps), then g_j <- -eps log sum_i a_i exp((f_i - c_ij) / eps).
+ * OT(x, y) = sum_i a_i f_i + sum_j b_j g_j at the final iterates; (x, x) and (y, y) run the same schedule with the
+ * pair's diam2.  The schedule is known on the host; no device value is read back.
+ *   x, y       : (pairs, n, 3), (pairs, m, 3) fp32, contiguous ; 1 <= n, m <= 8192 ; pairs >= 1 and
+ *                pairs * 2 * (ceil(n / 64) + ceil(m / 64)) < 2^31 (the largest grid).
+ *   xlen, ylen : (pairs) int32, device, or NULL (= n, m everywhere), as in simamba_chamfer_ragged_fwd: clamped to
+ *                [1, n], [1, m] by the kernels, nothing at or behind a length is read (the padding may hold NaN),
+ *                potentials and gradients behind a length are written as 0, and every pair's outputs are bit for bit
+ *                what it returns alone at its true lengths.
+ *   eps_rel    : 0 < eps_rel <= 1 ; iters >= 0 ; 1 <= S + iters <= 4096.
+ *   flags      : bit 0 = SIMAMBA_SINKHORN_DEBIAS: div = OT(x, y) - OT(x, x) / 2 - OT(y, y) / 2; without it div = OT(x, y),
+ *                g_xx, g_yy, f_yy are not touched and may be NULL.
+ *   div, ot_xy : (pairs) fp32.  fp64 partial sums in a fixed order.
+ *   merr       : (pairs) fp32 or NULL (then not computed): sum_i a_i |1 - exp((f_i - f_i+) / eps_fin)|, f+ one further
+ *                f-update of (x, y) that is not stored: the row-marginal error of the plan after the last step.
+ *   f_xy, g_xx : (pairs, n) ; g_xy, g_yy, f_yy : (pairs, m) fp32: the potentials after the last step.
+ * Backward, the potentials held fixed (exact at convergence), from ddiv (pairs):
+ *   dx_i = ddiv a_i 2 ( sum_j pi_xy(j|i) (x_i - y_j) - sum_k pi_xx(k|i) (x_i - x_k) ),
+ *   pi_xy(j|i) = softmax_j((g_xy_j - c_ij) / eps_fin), pi_xx the same from g_xx; dy_j likewise from f_xy and f_yy (the
+ *   potentials that are g_xy and g_xx bit for bit when y is x, so that the divergence of a set from itself is 0.0 and
+ *   both its gradients are exactly 0).  Without the flag the second sum is absent.  dx (pairs, n, 3) or dy
+ *   (pairs, m, 3) may be NULL: that gradient is skipped, and the potentials only it reads may be NULL too.
+ *   workspace  : device memory, 16-byte aligned (else SIMAMBA_E_ALIGN), at least simamba_sinkhorn_workspace_bytes()
+ *                bytes (else, or NULL, SIMAMBA_E_WORKSPACE): diam2, the per-row marginal errors and f_xx; the backward
+ *                needs 4 * pairs bytes of it.  The query answers 0 for arguments the calls refuse.
+ * A NaN coordinate inside a length makes that pair's outputs NaN and no other's; every loop has a host-known trip
+ * count.  No atomics: the same bits every call.
+ * Checks in the order flags (SIMAMBA_E_VARIANT), shape (SIMAMBA_E_SHAPE: sizes, pairs, eps_rel, iters), null pointers,
+ * workspace; all before any launch.  Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_SINKHORN_DEBIAS 1
+size_t simamba_sinkhorn_workspace_bytes(long long pairs, int n, int m, int flags);
+int simamba_sinkhorn_fwd(const float* x, const float* y, const int* xlen, const int* ylen, float* div, float* ot_xy,
+                         float* merr, float* f_xy, float* g_xy, float* g_xx, float* g_yy, float* f_yy, long long pairs,
+                         int n, int m, float eps_rel, int iters, int flags, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int simamba_sinkhorn_bwd(const float* x, const float* y, const int* xlen, const int* ylen, const float* ddiv,
+                         const float* f_xy, const float* g_xy, const float* g_xx, const float* f_yy, float* dx,
+                         float* dy, long long pairs, int n, int m, float eps_rel, int flags, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,
  * K=group_size, return_sorted=False)): idx[b][g][0..K) = the K points of cloud b nearest to centre g, ascending
  * squared distance (direct differences), ties to the lower point index.

@@ -33,6 +33,8 @@ CKPT_ROW, CKPT_SEQ = 128, 16
 BWD_DETERMINISTIC = 1
 # flags of the add + norm *_ex entry points: RMSNorm in place of LayerNorm
 NORM_RMS = 1
+# flags of simamba_sinkhorn_fwd / _bwd: subtract the two self-transport terms
+SINKHORN_DEBIAS = 1
 
 # name -> (restype, argtypes); mirrors include/simamba.h one to one
 _P = c_void_p
@@ -124,6 +126,9 @@ SIGNATURES = {
     "simamba_chamfer_ragged_fwd": (c_int, [_P] * 9 + [_LL] + [c_int] * 6 + [_P]),
     "simamba_chamfer_ragged_bwd": (c_int, [_P] * 11 + [_LL] + [c_int] * 6 + [_P]),
     "simamba_emd_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _LL, c_int, c_float, c_int, _P]),
+    "simamba_sinkhorn_workspace_bytes": (c_size_t, [_LL, c_int, c_int, c_int]),
+    "simamba_sinkhorn_fwd": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P]),
+    "simamba_sinkhorn_bwd": (c_int, [_P] * 11 + [_LL, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),

@@ -418,6 +418,8 @@ class Point_MAE_Mamba(nn.Module):
                                             ``loss: emd``) of every rebuilt patch; its mean is forward()'s loss
         The whole-cloud score of a pre-trained model in one line:
           ``chamfer_distance(torch.cat([visible, rebuilt], 1), pts)``
+        or, where it matters how the mass is distributed and not only how near the nearest point lies:
+          ``sinkhorn_divergence(torch.cat([visible, rebuilt], 1), pts)``
         ``mask`` (B,G) bool, the same number of True in every row, replaces the random mask.  Dropout and drop-path
         follow the module's mode: call ``eval()`` first for a repeatable result.  Built on
         ``forward(return_parts=True)``, whose dict carries ``neighborhood`` and ``center`` for this; the patch loss
