@@ -637,6 +637,42 @@ int simamba_sinkhorn_bwd(const float* x, const float* y, const int* xlen, const 
                          size_t workspace_bytes, void* stream);
 
 /*
+ * Part-segmentation scoring (csrc/part_metrics.hip; the reference's evaluation loop, part_segmentation/main.py:269-334):
+ * the argmax of every point's scores restricted to the labels of its shape's category, and the counts that accuracy,
+ * class-average accuracy and the two mean IoUs are made of.  One workgroup per shape, integers until the last division.
+ *   scores     : (batch, n, c) SIMAMBA_F32 or SIMAMBA_BF16, contiguous; log-probabilities or logits, only their order
+ *                matters.  1 <= c <= 256 ; n >= 1 ; 1 <= batch < 2^31.
+ *   target     : (batch, n) int64, the true label of every point.
+ *   part_first,
+ *   part_count : (batch) int32 each, device: the label range [first, first + count) of the shape's category,
+ *                1 <= count <= 16, first + count <= c.  The kernel clamps count into [1, min(16, c)] and first into
+ *                [0, c - count]; the library never reads them on the host.
+ *   lengths    : (batch) int64, device, or NULL (= n everywhere), as in simamba_farthest_point_sample_ex: shape b is
+ *                its first lengths[b] points, clamped to [1, n] by the kernel; neither scores nor target are read at or
+ *                behind a length (the padding may hold NaN and any label).
+ *   pred       : (batch, n) int64 or NULL (then not written): first + argmax(scores[b][i][first .. first + count)), -1
+ *                behind a length.  The FIRST maximum; a NaN counts as greater than every number and the first NaN wins
+ *                (numpy's argmax); +inf and -inf order as numbers.
+ *   inter, uni : (batch, 16) int32: for part k of the shape's category, l = first + k, the points with target == l and
+ *                pred == l, and those with target == l or pred == l.  Columns >= count are written as 0.
+ *   shape_iou  : (batch) fp64 = the mean over k < count of inter / uni, a part with uni == 0 (absent and unpredicted)
+ *                contributing 1.0: divided, added in part order and divided by count in double.
+ *   correct    : (batch) int32, the points with pred == target.
+ *   seen_class,
+ *   correct_class : (c) int64 each, ACCUMULATED INTO (the caller zeroes them): over all points, target == l, and
+ *                pred == l and target == l.  The only sums across workgroups: 64-bit integer atomics.
+ * A target outside the category's range matches no prediction but is still counted in seen_class; a target outside
+ * [0, c) is counted nowhere and indexes nothing.  No float or double atomic, no workspace, no allocation or
+ * synchronisation: the same bits every call.
+ * Checks in the order shape (SIMAMBA_E_SHAPE: batch, n, c), dtype (SIMAMBA_E_DTYPE), null pointers (all but lengths
+ * and pred are required); all before any launch.  Still ABI version 9: a symbol added, none changed.
+ */
+int simamba_part_seg_eval(const void* scores, const long long* target, const int* part_first, const int* part_count,
+                          const long long* lengths, long long* pred, int* inter, int* uni, double* shape_iou,
+                          int* correct, long long* seen_class, long long* correct_class, long long batch, int n, int c,
+                          int io_dtype, void* stream);
+
+/*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,
  * K=group_size, return_sorted=False)): idx[b][g][0..K) = the K points of cloud b nearest to centre g, ascending
  * squared distance (direct differences), ties to the lower point index.

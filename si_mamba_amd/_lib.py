@@ -129,6 +129,7 @@ SIGNATURES = {
     "simamba_sinkhorn_workspace_bytes": (c_size_t, [_LL, c_int, c_int, c_int]),
     "simamba_sinkhorn_fwd": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P]),
     "simamba_sinkhorn_bwd": (c_int, [_P] * 11 + [_LL, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
+    "simamba_part_seg_eval": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_int, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),
