@@ -83,7 +83,9 @@ extern "C" {
  *                          elements; anything else returns SIMAMBA_E_VARIANT).
  * simamba_scan_ckpt_step() is the library's own choice for a shape (host arithmetic only; the caller still has to
  * meet the alignment rules above or pass _ROW: simamba_scan_seq_applicable() answers that for a set of operands); simamba_scan_ckpt_floats() the size of x_ckpt in floats (0: none
- * needed, x_ckpt may be NULL).
+ * needed, x_ckpt may be NULL).  The choice is _SEQ from 49 152 rows (batch * dim) on, and, for fp32 I/O, from
+ * 36 864 rows on when seqlen >= 1024 (a mixer that runs on 48 .. 60 samples of a batch of 64: measured,
+ * csrc/scan_fwd.hip; bf16 and shorter sequences were not measured there and keep the line).
  */
 #define SIMAMBA_SCAN_CKPT_ROW 128
 #define SIMAMBA_SCAN_CKPT_SEQ 16
@@ -338,6 +340,41 @@ int simamba_add_layer_norm_bwd_ex(const void* dnormed, const float* dresidual_ou
                                   const float* weight, const float* rowscale, float* dresidual,
                                   void* dhidden, float* dwb_partial, int batch, int rows_per_batch,
                                   int dim, int hidden_dtype, int out_dtype, int flags, void* stream);
+
+/*
+ * ... on compact batches.  `hidden` / `dhidden` hold hidden_batch <= batch samples and `normed` / `dnormed` hold
+ * normed_batch <= batch samples, packed; everything else (residual, residual_out, dresidual_out, dresidual, mean,
+ * rstd, rowscale) stays (batch, ...), and so do the grid and the layout of dwb_partial.
+ *   hidden_slot : (batch) int32 on the device -- sample b's index inside hidden / dhidden, or -1: the sample has no
+ *                 hidden rows.  Forward: residual_out = residual for it, hidden is not read (what a rowscale of 0
+ *                 gives).  Backward: dhidden = rowscale * dresidual is written for the mapped samples only, at their
+ *                 slot (zeros where rowscale is 0).  Needs residual and residual_out.
+ *   normed_slot : (batch) int32 on the device -- sample b's index inside normed / dnormed, or -1: nobody needs the
+ *                 sample's normed rows.  Forward: neither normed nor mean / rstd are written for it.  Backward: its
+ *                 dresidual = dresidual_out (0 without one), it adds nothing to dwb_partial (what a zero dnormed
+ *                 gives), and its residual_out, mean, rstd and dnormed are not read.
+ * A NULL map says the tensor holds the whole batch and goes with a compact batch == batch (else SIMAMBA_E_NULLPTR);
+ * with NULL maps these are simamba_add_layer_norm_fwd_ex / _bwd_ex bit for bit.  A compact batch outside [0, batch]:
+ * SIMAMBA_E_SHAPE.  A compact batch of 0 is legal and its tensor may be NULL.  The maps live on the device and are not
+ * read by the host: the kernels treat a slot outside [-1, compact batch) as -1, and every slot in [0, compact batch)
+ * of dhidden that is read afterwards has to be some sample's.  simamba_add_layer_norm_check_slots checks a map that is
+ * still on the HOST (no stream): SIMAMBA_E_SHAPE for an entry outside [-1, compact_batch), a slot taken twice or a
+ * compact batch outside [0, batch], SIMAMBA_E_NULLPTR without a map.
+ */
+int simamba_add_layer_norm_check_slots(const int* slots_host, int batch, int compact_batch);
+int simamba_add_layer_norm_fwd_slots(const void* hidden, const float* residual, const float* rowscale,
+                                     const float* weight, const float* bias, float* residual_out,
+                                     void* normed, float* mean, float* rstd, const int* hidden_slot,
+                                     int hidden_batch, const int* normed_slot, int normed_batch, int batch,
+                                     int rows_per_batch, int dim, float eps, int hidden_dtype, int out_dtype,
+                                     int flags, void* stream);
+int simamba_add_layer_norm_bwd_slots(const void* dnormed, const float* dresidual_out,
+                                     const float* residual_out, const float* mean, const float* rstd,
+                                     const float* weight, const float* rowscale, float* dresidual,
+                                     void* dhidden, float* dwb_partial, const int* hidden_slot,
+                                     int hidden_batch, const int* normed_slot, int normed_batch, int batch,
+                                     int rows_per_batch, int dim, int hidden_dtype, int out_dtype, int flags,
+                                     void* stream);
 
 /*
  * out_proj -> (+ DropPath-scaled residual) -> LayerNorm in one kernel on the matrix cores, bf16 operands: the mixer's

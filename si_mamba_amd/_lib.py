@@ -92,6 +92,11 @@ SIGNATURES = {
                                               c_int, c_int, c_int, _P]),
     "simamba_add_layer_norm_bwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int,
                                               c_int, c_int, c_int, _P]),
+    "simamba_add_layer_norm_check_slots": (c_int, [_P, c_int, c_int]),
+    "simamba_add_layer_norm_fwd_slots": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int,
+                                                 c_int, c_float, c_int, c_int, c_int, _P]),
+    "simamba_add_layer_norm_bwd_slots": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int,
+                                                 c_int, c_int, c_int, c_int, c_int, _P]),
     "simamba_out_proj_add_ln_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,
                                             c_int, _P]),
     "simamba_out_proj_add_ln_fwd_ex": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
@@ -371,6 +376,22 @@ class fuse_out_norm(_Override):
 
 def fuse_out_norm_enabled():
     return _fuse_out_norm[0]
+
+
+_drop_path_compact = [os.environ.get("SIMAMBA_DROP_PATH_COMPACT", "1").strip().lower() not in ("0", "false", "off")]
+DROP_PATH_BUCKET = 4          # compact batches are rounded up to a multiple of this many samples
+compact_sizes = {}            # compact batch -> how many mixer calls ran at it (read by benchmarks and tests)
+
+
+class drop_path_compact(_Override):
+    """Context manager: let MixerModel run every mixer only on the samples the NEXT block's DropPath keeps (block.py,
+    compact add + norm kernels) or on the whole batch as the reference does.  On by default; the environment variable
+    SIMAMBA_DROP_PATH_COMPACT=0 switches it off for a whole process."""
+    cell = _drop_path_compact
+
+
+def drop_path_compact_enabled():
+    return _drop_path_compact[0]
 
 
 _sparse_max_linear = [None]   # None: the measured default (sparse_max_linear_enabled); True / False: forced

@@ -31,14 +31,14 @@ from .rms_norm import RMSNorm
 _KERNEL_NORMS = (nn.LayerNorm, RMSNorm)      # the norms the add + norm kernels compute
 
 
-def _fused_norm(hidden, residual, norm, rowscale=None, out_dtype=None):
+def _fused_norm(hidden, residual, norm, rowscale=None, out_dtype=None, **compact):
     """Add (+ DropPath) + ``norm`` (an nn.LayerNorm or an RMSNorm) through the add_norm kernel: -> (normed, residual).
-    RMSNorm routes are counted (``add_rms_norm``)."""
+    RMSNorm routes are counted (``add_rms_norm``).  ``compact``: add_layer_norm_fn's slot-map arguments."""
     rms = type(norm) is RMSNorm
     if rms:
         _lib.count("add_rms_norm")
     return add_layer_norm_fn(hidden, residual, norm.weight, norm.bias, norm.eps, rowscale=rowscale,
-                             out_dtype=out_dtype, rms=rms)
+                             out_dtype=out_dtype, rms=rms, **compact)
 
 
 class DropPath(nn.Module):
@@ -51,10 +51,15 @@ class DropPath(nn.Module):
 
     def rowscale(self, x):
         """Per-sample factor (B,) this layer would multiply x by, or None when it is the identity."""
+        return self.rowscale_for(x.shape[0], x.device)
+
+    def rowscale_for(self, batch, device):
+        """rowscale() from the batch size and the device alone: the same draw, for callers that make it before the
+        tensor exists (MixerModel.draw_drop_plan)."""
         if self.drop_prob == 0.0 or not self.training:
             return None
         keep = 1.0 - self.drop_prob
-        mask = torch.empty(x.shape[0], device=x.device, dtype=torch.float32).bernoulli_(keep)
+        mask = torch.empty(batch, device=device, dtype=torch.float32).bernoulli_(keep)
         if keep > 0.0 and self.scale_by_keep:
             mask.div_(keep)
         return mask
@@ -77,16 +82,31 @@ class Block(nn.Module):
         self.norm = norm_cls(dim)
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
 
-    def forward(self, hidden_states: Tensor, residual: Optional[Tensor] = None, inference_params=None, A=None):
+    def forward(self, hidden_states: Tensor, residual: Optional[Tensor] = None, inference_params=None, A=None, *,
+                rowscale=None, compact=None):
         """hidden_states = Mixer(LN(residual)); returns (hidden_states, residual).  ``A`` (optional, specific to this
         implementation): the mixer's -exp(A_log) when the caller has already formed it (MixerModel does, for all
         layers in one launch); handed on as an argument, never parked on the module.
 
         Add (+ DropPath) + LayerNorm (or RMSNorm) run as one HIP pass each way (add_norm.py) for such blocks on the
-        GPU; the composed torch form below is the reference's own and serves any other norm / device."""
-        if hidden_states.is_cuda and type(self.norm) in _KERNEL_NORMS and hidden_states.dim() == 3:
-            scale = self.drop_path.rowscale(hidden_states) if isinstance(self.drop_path, DropPath) else None
+        GPU; the composed torch form below is the reference's own and serves any other norm / device.
+
+        ``rowscale`` (B,), ``compact`` (both specific to this implementation, MixerModel's): the DropPath factors when
+        the caller has already drawn them, and add_layer_norm_fn's slot-map arguments when ``hidden_states`` holds only
+        some samples of the batch (None: none) and / or the mixer is to run only on some; the hidden_states returned
+        are then compact too, None when the mixer has no sample to run on."""
+        if compact is not None:
+            hidden_states, residual = _fused_norm(hidden_states, residual, self.norm, rowscale=rowscale, **compact)
+            if hidden_states.shape[0] == 0:
+                return None, residual
+        elif hidden_states.is_cuda and type(self.norm) in _KERNEL_NORMS and hidden_states.dim() == 3:
+            scale = rowscale
+            if scale is None and isinstance(self.drop_path, DropPath):
+                scale = self.drop_path.rowscale(hidden_states)
             hidden_states, residual = _fused_norm(hidden_states, residual, self.norm, rowscale=scale)
+        elif rowscale is not None:
+            raise NotImplementedError("Block.forward(rowscale=...): drawn DropPath factors are taken by the add + norm "
+                                      "kernel route only")
         else:
             residual = (self.drop_path(hidden_states) + residual) if residual is not None else hidden_states
             hidden_states = self.norm(residual.to(dtype=self.norm.weight.dtype))
@@ -130,6 +150,41 @@ def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, rms_norm=False, resid
     return block
 
 
+class _SkippedMixerFn(torch.autograd.Function):
+    """x, unchanged, with exact-zero gradients for ``params``: stands in for a mixer that ran on no sample, so that its
+    parameters receive what the full route gives them (zeros, not None -- optimisers and gradient reducers tell the
+    two apart)."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        ctx.save_for_backward(*params)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dx):
+        return (dx,) + tuple(torch.zeros_like(p) for p in ctx.saved_tensors)
+
+
+# One side stream per device, and per (device, blocks, batch) a pool of free pinned staging pairs (not module
+# attributes: modules get deep-copied and pickled).  A plan owns its pair from the draw until its maps are on their
+# way up, so plans in flight at the same time -- two stacks of one shape, or a plan drawn and never used -- never share
+# one; a plan that is dropped simply keeps its pair out of the pool.
+_drop_streams = {}
+_drop_hosts = {}
+
+
+class DropPlan:
+    """The DropPath factors of one forward of a MixerModel, drawn ahead of the blocks (MixerModel.draw_drop_plan), and
+    what follows from them once they are on the host (MixerModel._finish_plan).
+
+    ``masks[j - 1]`` (B,) fp32 on the device is block j's rowscale, j = 1 .. n - 1.  ``lead``: a draw for block 0
+    came first (the route on which block 0 runs through Block.forward draws one and never applies it).  After
+    _finish_plan, for every boundary j: ``sizes[j - 1]`` = the compact batch mixer j - 1 runs at (B: all of it, 0: not
+    at all) and ``maps[j - 1]`` = the (B,) int32 device map sample -> slot, None at B; ``sel`` (sizes[0],) int32 =
+    the samples of boundary 1 by slot, for the route that compacts block 0's tokens with index_select."""
+    __slots__ = ("masks", "lead", "batch", "event", "host", "sizes", "maps", "sel")
+
+
 class MixerModel(nn.Module):
     def __init__(self, d_model: int, n_layer: int, ssm_cfg=None, norm_epsilon: float = 1e-5,
                  rms_norm: bool = False, initializer_cfg=None, fused_add_norm=False,
@@ -149,21 +204,151 @@ class MixerModel(nn.Module):
                            **(initializer_cfg if initializer_cfg is not None else {})))
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
         self.drop_out_in_block = nn.Dropout(drop_out_in_block) if drop_out_in_block > 0. else nn.Identity()
+        # run each mixer only on the samples the next block's DropPath keeps (draw_drop_plan); stacks that have not
+        # been measured on the route switch it off (mae.py)
+        self.drop_path_compact = True
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         return {i: layer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)
                 for i, layer in enumerate(self.layers)}
 
-    def _first_block_on_distinct_tokens(self, tokens, pos, token_index, A=None, emit_y=False):
+    # ---- DropPath: mixers on the kept samples only -------------------------------------------------------------------
+    # Block j (j >= 1) forms residual = rowscale_j * hidden_{j-1} + residual, and rowscale_j[b] is 0 for the samples its
+    # DropPath drops: mixer j - 1 is computed for them and multiplied by zero, and backward their dhidden is zero, so
+    # the whole mixer backward runs on zeros.  With the factors known BEFORE the stack starts, mixer j - 1 runs on the
+    # kept samples only: block j - 1's add + norm writes `normed` compacted, block j's reads `hidden` compacted
+    # (add_norm.py's slot maps); the residual stream keeps the whole batch.
+
+    def _compact_ok(self, x, inference_params=None):
+        """Does a forward on ``x`` take the compact route?  Training with DropPath in every block, the layer-by-layer
+        route of plain blocks on the add + norm kernels, nothing between the blocks, no stream capture (the plan
+        needs the factors on the host), and not switched off (_lib.drop_path_compact, self.drop_path_compact)."""
+        if not (self.drop_path_compact and _lib.drop_path_compact_enabled() and self.training
+                and type(self) is MixerModel and inference_params is None and len(self.layers) > 1
+                and x.is_cuda and x.dim() == 3 and isinstance(self.drop_out_in_block, nn.Identity)
+                and type(self.norm_f) in _KERNEL_NORMS):
+            return False
+        for layer in self.layers:
+            dp = layer.drop_path
+            if not (type(layer) is Block and type(layer.norm) in _KERNEL_NORMS and type(layer.mixer) is Mamba
+                    and isinstance(dp, DropPath) and dp.training and 0.0 < dp.drop_prob < 1.0):
+                return False
+        return not torch.cuda.is_current_stream_capturing() and not self._chain_ok(x)
+
+    def _first_block_applies(self, tokens, seqlen):
+        """Will _first_block_on_distinct_tokens take (B, G, C) ``tokens`` expanded to ``seqlen`` positions?  Shapes and
+        types only, so that it can be answered before the index map exists (its other condition, L % G, is among
+        expansion_ok's)."""
+        from . import seq_expand
+        layer = self.layers[0]
+        return (tokens.is_cuda and type(layer.norm) in _KERNEL_NORMS and isinstance(layer.mixer, Mamba)
+                and layer.mixer.use_fast_path and seq_expand.expansion_len_ok(tokens, seqlen))
+
+    def draw_drop_plan(self, like, lead=False, drop_masks=None):
+        """Draw the DropPath factors of blocks 1 .. n - 1 for a batch like ``like``'s NOW -- the same bernoulli_ calls
+        in the same order as the blocks would make (``lead``: block 0's unused draw first, see DropPlan) -- and start
+        their copy to the host.  -> a DropPlan for forward(drop_plan=...), or None when a forward on ``like`` would not
+        take the compact route (then nothing is drawn).  ``drop_masks``: these factors instead of drawn ones."""
+        if not self._compact_ok(like):
+            return None
+        n, B, dev = len(self.layers), like.shape[0], like.device
+        plan = DropPlan()
+        if drop_masks is None:
+            with torch.cuda.stream(self._drop_stream(dev)):
+                if lead:
+                    self.layers[0].drop_path.rowscale_for(B, dev)
+                plan.masks = [self.layers[j].drop_path.rowscale_for(B, dev) for j in range(1, n)]
+        else:
+            if len(drop_masks) != n - 1:
+                raise ValueError(f"drop_masks: one (B,) rowscale for each of the blocks 1 .. {n - 1}, got "
+                                 f"{len(drop_masks)}")
+            plan.masks = [m.to(device=dev, dtype=torch.float32) for m in drop_masks]
+        plan.lead, plan.batch = bool(lead), B
+        free = _drop_hosts.setdefault((dev, n - 1, B), [])
+        # pinned staging, reused from step to step: the factors down, the maps (and boundary 1's samples) up.  Both
+        # copies run on the side stream, and a plan overwrites a pair it took from the pool only after it has waited
+        # for its own factors, which that stream copies down behind the previous owner's upload.
+        host = free.pop() if free else (torch.empty(n - 1, B, dtype=torch.float32).pin_memory(),
+                                        torch.empty(n, B, dtype=torch.int32).pin_memory())
+        plan.host = host
+        main, side = torch.cuda.current_stream(dev), self._drop_stream(dev)
+        if drop_masks is not None:
+            side.wait_stream(main)                          # handed-in factors come from the caller's stream
+        with torch.cuda.stream(side):
+            host[0].copy_(torch.stack(plan.masks), non_blocking=True)
+            plan.event = torch.cuda.Event()
+            plan.event.record(side)
+        for m in plan.masks:
+            m.record_stream(main)
+        plan.sizes = plan.maps = plan.sel = None
+        return plan
+
+    def _drop_stream(self, dev):
+        """The stream the factors are drawn and copied on.  A draw depends on nothing the device has still to compute
+        (the generator's offset advances on the host when the draw is launched), so it need not queue behind the
+        previous step's backward on the caller's stream: the host then waits for a few tiny kernels, not for the
+        device to catch up, and keeps running ahead of it as it does on the full route."""
+        st = _drop_streams.get(dev)
+        if st is None:
+            st = _drop_streams[dev] = torch.cuda.Stream(device=dev)
+        return st
+
+    def _finish_plan(self, plan, dev):
+        """Wait for the factors (the one host synchronisation of the step: for the side stream's copy, not for the
+        caller's stream), form every boundary's compact batch and slot map on the host and upload all maps in one
+        copy."""
+        plan.event.synchronize()
+        B, bucket = plan.batch, _lib.DROP_PATH_BUCKET
+        down, up = plan.host
+        check = _lib.load().simamba_add_layer_norm_check_slots
+        sizes, rows = [], []
+        for j, row in enumerate(down.tolist()):
+            kept = [b for b, v in enumerate(row) if v != 0.0]
+            k = len(kept)
+            size = min(B, bucket * ((k + bucket - 1) // bucket))
+            sizes.append(size)
+            if size == B:
+                rows.append([0] * B)                       # not used: the boundary runs on the whole batch
+                continue
+            # kept samples first, in order; the spare slots of the bucket go to dropped samples, which stay in with
+            # their factor of 0 exactly as on the full route
+            dropped = [b for b, v in enumerate(row) if v == 0.0]
+            members = kept + dropped[:size - k]
+            slot = [-1] * B
+            for s_, b in enumerate(members):
+                slot[b] = s_
+            rows.append(slot)
+            if j == 0:
+                sel = members + [0] * (B - size)
+        if sizes[0] == B:
+            sel = list(range(B))
+        up.copy_(torch.tensor(rows + [sel], dtype=torch.int32))
+        for j, size in enumerate(sizes):
+            if size < B:
+                _lib.check(check(up[j].data_ptr(), B, size), "simamba_add_layer_norm_check_slots")
+        main, side = torch.cuda.current_stream(dev), self._drop_stream(dev)
+        with torch.cuda.stream(side):
+            maps = up.to(dev, non_blocking=True)
+        main.wait_stream(side)                              # the maps, and the factors drawn before them
+        maps.record_stream(main)
+        _drop_hosts[(dev, len(sizes), B)].append(plan.host)  # back to the pool (see draw_drop_plan on the order)
+        plan.host = None
+        plan.sizes = sizes
+        plan.maps = [maps[j] if size < B else None for j, size in enumerate(sizes)]
+        plan.sel = maps[len(sizes), :sizes[0]]
+        return plan
+
+    def _first_block_on_distinct_tokens(self, tokens, pos, token_index, A=None, emit_y=False, keep=None):
         """Block 0 when the sequence is ``gather(tokens + pos, token_index)``: Add + LayerNorm + in_proj on the G
         distinct tokens, expanded to the L positions by a copy kernel (seq_expand.py).  -> (hidden, residual) of
         block 0 as the reference's Block.forward returns them (``emit_y``: the mixer's output before out_proj in
-        place of hidden, see _chain), or None when the route does not apply."""
+        place of hidden, see _chain), or None when the route does not apply.  ``keep`` = (samples (n,) int32, n): the
+        mixer runs on these samples only and ``hidden`` holds them in this order (None when n == 0); the residual
+        keeps the whole batch."""
         from . import seq_expand
         layer = self.layers[0]
         mixer = layer.mixer
-        if not (tokens.is_cuda and type(layer.norm) in _KERNEL_NORMS and isinstance(mixer, Mamba)
-                and mixer.use_fast_path and seq_expand.expansion_ok(tokens, token_index)):
+        if not self._first_block_applies(tokens, token_index.shape[1]):
             return None
         inv32 = seq_expand.inverse_positions(token_index, tokens.shape[1])
         if inv32 is None:
@@ -175,8 +360,15 @@ class MixerModel(nn.Module):
             normed, res0 = _fused_norm(tokens, pos, layer.norm)
         else:
             normed, res0 = _fused_norm(tokens + pos, None, layer.norm)
-        xz = seq_expand.seq_gather_last(mixer.in_proj_xz(normed), idx32, inv32)          # (B, 2D, L)
-        hidden = mixer.forward_xz(xz, A=A, emit_y=emit_y)
+        if keep is not None and keep[1] < tokens.shape[0]:
+            # the per-token head and the mixer on the kept samples: (n, G, C) rows of three small tensors
+            sel, nk = keep
+            normed, idx32, inv32 = (t.index_select(0, sel) for t in (normed, idx32, inv32)) if nk else (None,) * 3
+        if normed is None:
+            hidden = None
+        else:
+            xz = seq_expand.seq_gather_last(mixer.in_proj_xz(normed), idx32, inv32)      # (B, 2D, L)
+            hidden = mixer.forward_xz(xz, A=A, emit_y=emit_y)
         residual = torch.gather(res0, 1, token_index.unsqueeze(-1).expand(-1, -1, res0.shape[-1]))
         return hidden, residual
 
@@ -244,23 +436,49 @@ class MixerModel(nn.Module):
             y = mixer.forward_xz(mixer.in_proj_xz(normed), A=A_all[i], emit_y=True)
             i += 1
 
-    def forward(self, input_ids, pos, inference_params=None, token_index=None, balanced_index=False):
+    def forward(self, input_ids, pos, inference_params=None, token_index=None, balanced_index=False, *,
+                drop_plan=None, drop_masks=None):
         """Reference signature (models/point_mamba.py:247).  ``token_index`` (B, L) int64, optional and specific to
         this implementation: when given, ``input_ids`` / ``pos`` are the G DISTINCT tokens (B, G, C) and the sequence
         the reference would be handed is their gather by ``token_index``; the result is the same.
         ``balanced_index=True`` is the caller's statement that every token occurs exactly L / G times in every row of
         ``token_index`` (a concatenation of permutations, which is what the SAST / MAMBA assemblies are): only then
         does the first block's per-token head run on the G tokens (the adjoint of that expansion sums a fixed number
-        of positions per token); any other index takes the reference's route on the gathered sequence."""
+        of positions per token); any other index takes the reference's route on the gathered sequence.
+
+        ``drop_plan`` (keyword-only, specific to this implementation): what draw_drop_plan returned for this forward
+        when the caller drew the DropPath factors early (PointMamba does, ahead of its tokeniser, so that the copy to
+        the host is long done here); without one the factors are drawn on entry.  ``drop_masks``: a test hook, the
+        (B,) rowscales of blocks 1 .. n - 1 to use in place of drawn ones, on the compact and on the full route."""
         first = 0
         residual = None
+        first_on_tokens = (token_index is not None and balanced_index and inference_params is None
+                           and len(self.layers) > 0 and self._first_block_applies(input_ids, token_index.shape[1]))
+        plan = drop_plan
+        if plan is None:
+            plan = self.draw_drop_plan(input_ids, lead=not first_on_tokens, drop_masks=drop_masks)
+        elif plan.lead == first_on_tokens or plan.batch != input_ids.shape[0]:
+            raise ValueError("MixerModel.forward: drop_plan was drawn for another route or batch")
+        if plan is not None:
+            self._finish_plan(plan, input_ids.device)
+            _lib.count("drop_path_compact")
         A_all = self._precompute_A()
         chain = inference_params is None and len(self.layers) > 0 and self._chain_ok(input_ids)
+        if chain and drop_masks is not None:
+            raise NotImplementedError("MixerModel.forward(drop_masks=...): the fused bf16 chain draws its own factors")
         if token_index is not None:
-            done = (self._first_block_on_distinct_tokens(input_ids, pos, token_index, A=A_all[0], emit_y=chain)
+            keep = None if plan is None else (plan.sel, plan.sizes[0])
+            done = (self._first_block_on_distinct_tokens(input_ids, pos, token_index, A=A_all[0], emit_y=chain,
+                                                         keep=keep)
                     if (balanced_index and inference_params is None) else None)
             if done is not None:
                 hidden_states, residual = done
+                if plan is not None:
+                    if hidden_states is None:               # block 0's mixer ran on no sample
+                        residual = _SkippedMixerFn.apply(residual, *self.layers[0].mixer.parameters())
+                    else:
+                        size = hidden_states.shape[0]
+                        _lib.compact_sizes[size] = _lib.compact_sizes.get(size, 0) + 1
                 if chain:                                   # hidden_states is block 0's y (B, d_inner, L)
                     return self._chain(1, hidden_states, None, residual, A_all)
                 hidden_states = self.drop_out_in_block(hidden_states)
@@ -276,9 +494,13 @@ class MixerModel(nn.Module):
             scale = l0.drop_path.rowscale(hidden_states) if isinstance(l0.drop_path, DropPath) else None
             normed, residual = _fused_norm(hidden_states, None, l0.norm, rowscale=scale)
             return self._chain(0, None, normed, residual, A_all)
-        for i in range(first, len(self.layers)):
+        n = len(self.layers)
+        if plan is not None:
+            return self._compact_stack(first, hidden_states, residual, A_all, plan)
+        for i in range(first, n):
+            scale = drop_masks[i - 1] if (drop_masks is not None and i > 0) else None
             hidden_states, residual = self.layers[i](hidden_states, residual, inference_params=inference_params,
-                                                     A=A_all[i])
+                                                     A=A_all[i], rowscale=scale)
             hidden_states = self.drop_out_in_block(hidden_states)
         if hidden_states.is_cuda and type(self.norm_f) in _KERNEL_NORMS and hidden_states.dim() == 3:
             # the stack's output norm returns the parameter dtype (fp32) under autocast too, as F.layer_norm does
@@ -286,6 +508,33 @@ class MixerModel(nn.Module):
             return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
         residual = (hidden_states + residual) if residual is not None else hidden_states
         return self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))
+
+
+    def _compact_stack(self, first, hidden_states, residual, A_all, plan):
+        """Blocks ``first``.. and the final norm with every mixer on its boundary's compact batch (DropPlan).
+        ``hidden_states`` is block ``first - 1``'s compact output (None: it ran on no sample), or the stack's input
+        when ``first == 0``."""
+        n, B = len(self.layers), plan.batch
+        io = hidden_states.dtype if hidden_states is not None else self.layers[0].mixer.out_proj.weight.dtype
+        for i in range(first, n):
+            # always a dict, empty where neither side is compact: with a plan no block draws, block 0 included (on
+            # its own route through Block.forward it would draw a rowscale it never applies; the plan's ``lead`` draw
+            # stands for that one)
+            compact = {}
+            if i > 0 and plan.sizes[i - 1] < B:            # hidden holds boundary i's samples
+                compact.update(hidden_slot=plan.maps[i - 1], hidden_dtype=io)
+            if i < n - 1 and plan.sizes[i] < B:            # mixer i runs on boundary i + 1's
+                compact.update(normed_slot=plan.maps[i], normed_batch=plan.sizes[i])
+            size = plan.sizes[i] if i < n - 1 else B
+            hidden_states, residual = self.layers[i](hidden_states, residual, A=A_all[i],
+                                                     rowscale=plan.masks[i - 1] if i > 0 else None,
+                                                     compact=compact)
+            if size:
+                io = hidden_states.dtype
+                _lib.compact_sizes[size] = _lib.compact_sizes.get(size, 0) + 1
+            else:
+                residual = _SkippedMixerFn.apply(residual, *self.layers[i].mixer.parameters())
+        return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
 
 
 class MixerModel_add(MixerModel):

@@ -16,6 +16,14 @@
 // normed = x * rstd * w, no mean, no bias; backward with x^ = x * rstd, g = dnormed * w:
 // dx = rstd * (g - x^ * mean(g * x^)), dw = sum_rows dnormed * x^.  Same bytes each way; `mean` is neither read nor
 // written and the partial rows' dbias half is left as it is.
+//
+// Slot maps (the *_slots entry points): `hidden` / `dhidden` and `normed` / `dnormed` may hold only some of the batch's
+// samples, packed.  hidden_slot[b] / normed_slot[b] is sample b's index inside the compact tensor or -1.  A sample
+// without hidden rows takes residual_out = residual (what hidden * 0 + residual gives) and gets no dhidden; a sample
+// without normed rows gets no normed store and no statistics forward, and backward its dx is dresidual_out alone: its
+// residual_out, mean, rstd and dnormed are not read and it adds nothing to the weight / bias partials (what a zero
+// dnormed adds).  The row walk, the grid and with them the accumulation order of the partials are those of the full
+// batch; both lookups are one wave-uniform load per row.  A slot outside [0, compact batch) counts as -1.
 #include "common.h"
 
 namespace simamba {
@@ -39,6 +47,10 @@ struct LnArgs {
   float* dresidual;
   void* dhidden;
   float* dwb_partial;   // (gridDim.x, 2, dim)
+  // compact batches: (batch) sample -> index inside hidden / dhidden (normed / dnormed), -1 = none; null = identity
+  const int* hidden_slot;
+  const int* normed_slot;
+  int hidden_batch, normed_batch;
   int batch, rows_per_batch, dim;
   float eps;
 };
@@ -55,8 +67,32 @@ __device__ __forceinline__ void st4(T* p, float4 v) {
   *reinterpret_cast<Pack<T, 4>*>(p) = pk;
 }
 
+// Sample `b`'s index inside a compact tensor of `count` samples (wave-uniform: one scalar load), -1 for none.
+__device__ __forceinline__ int ln_slot(const int* __restrict__ map, int b, int count) {
+  if (!map) return b;
+  const int s = __builtin_amdgcn_readfirstlane(map[b]);
+  return (s >= 0 && s < count) ? s : -1;
+}
+
+// Where one row's hidden / normed live.  The kernels look a row's slots up one iteration ahead: a wave has one row in
+// flight, so a lookup in front of the row's loads (their addresses depend on it) would add its latency to every row.
+struct LnRow {
+  int b, hs, os;
+};
+__device__ __forceinline__ LnRow ln_row(const LnArgs& p, int row) {
+  LnRow r;
+  r.b = __builtin_amdgcn_readfirstlane(row / p.rows_per_batch);
+  r.hs = ln_slot(p.hidden_slot, r.b, p.hidden_batch);
+  r.os = ln_slot(p.normed_slot, r.b, p.normed_batch);
+  return r;
+}
+
+// One body serves both forms (`slots`, uniform over the launch): a mapped row and a whole-batch row run the same
+// instructions, which is what makes the two bitwise equal -- two instantiations would be free to contract their
+// multiply-adds differently.
 template <typename TH, typename TO, int kChunks, bool kRms>
 __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
+  const bool slots = p.hidden_slot || p.normed_slot;
   const int lane = threadIdx.x & 63;
   const int wave_global = (blockIdx.x * kLnThreads + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * kLnThreads) >> 6;
@@ -72,20 +108,38 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
     bs[k] = (!kRms && c < nch && p.bias) ? *reinterpret_cast<const float4*>(p.bias + 4 * c) : make_float4(0, 0, 0, 0);
   }
   const float inv_dim = 1.f / p.dim;
+  LnRow next = (slots && wave_global < rows) ? ln_row(p, wave_global) : LnRow{0, 0, 0};
   for (int row = wave_global; row < rows; row += nwaves) {
     const size_t base = static_cast<size_t>(row) * p.dim;
     const float scale = (p.rowscale && p.residual) ? p.rowscale[row / p.rows_per_batch] : 1.f;
+    // where this row's hidden / normed live (compact batches); the whole-batch kernel keeps `base` for both
+    size_t hbase = base, obase = base;
+    bool has_h = true, has_o = true;
+    if (slots) {
+      const LnRow cur = next;
+      const int ahead = row + nwaves;
+      next = ln_row(p, ahead < rows ? ahead : row);
+      const int r = __builtin_amdgcn_readfirstlane(row) - cur.b * p.rows_per_batch;
+      has_h = cur.hs >= 0; has_o = cur.os >= 0;
+      hbase = (static_cast<size_t>(has_h ? cur.hs : 0) * p.rows_per_batch + r) * p.dim;
+      obase = (static_cast<size_t>(has_o ? cur.os : 0) * p.rows_per_batch + r) * p.dim;
+    }
     float4 x[kChunks];
     float sum = 0.f;
 #pragma unroll
     for (int k = 0; k < kChunks; ++k) {
       const int c = lane + 64 * k;
       if (c < nch) {
-        float4 h = ld4<TH>(hg + base + 4 * c);
-        if (p.residual) {
-          const float4 r = *reinterpret_cast<const float4*>(p.residual + base + 4 * c);
-          h.x = fmaf(h.x, scale, r.x); h.y = fmaf(h.y, scale, r.y);
-          h.z = fmaf(h.z, scale, r.z); h.w = fmaf(h.w, scale, r.w);
+        float4 h;
+        if (!has_h) {                           // no hidden rows (the host requires a residual then)
+          h = *reinterpret_cast<const float4*>(p.residual + base + 4 * c);
+        } else {
+          h = ld4<TH>(hg + hbase + 4 * c);
+          if (p.residual) {
+            const float4 r = *reinterpret_cast<const float4*>(p.residual + base + 4 * c);
+            h.x = fmaf(h.x, scale, r.x); h.y = fmaf(h.y, scale, r.y);
+            h.z = fmaf(h.z, scale, r.z); h.w = fmaf(h.w, scale, r.w);
+          }
         }
         if (p.residual_out) *reinterpret_cast<float4*>(p.residual_out + base + 4 * c) = h;
         x[k] = h;
@@ -94,6 +148,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
         x[k] = make_float4(0, 0, 0, 0);
       }
     }
+    if (!has_o) continue;                                 // nobody reads this row's normed, mean or rstd
     // RMS: the constant 0 folds away (x - 0.f == x) and with it the row sum and its all-reduce
     const float mean = kRms ? 0.f : wave_allreduce_sum(sum) * inv_dim;
     float sq = 0.f;
@@ -114,7 +169,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
         y.y = fmaf((x[k].y - mean) * rstd, w[k].y, bs[k].y);
         y.z = fmaf((x[k].z - mean) * rstd, w[k].z, bs[k].z);
         y.w = fmaf((x[k].w - mean) * rstd, w[k].w, bs[k].w);
-        st4<TO>(og + base + 4 * c, y);
+        st4<TO>(og + obase + 4 * c, y);
       }
     }
     if (lane == 0) {
@@ -126,6 +181,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(LnArgs p) {
 
 template <typename TH, typename TO, int kChunks, bool kRms>
 __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
+  const bool slots = p.hidden_slot || p.normed_slot;
   extern __shared__ float sred[];          // [4 waves][2][dim]
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -144,8 +200,38 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
     db[k] = make_float4(0, 0, 0, 0);
   }
   const float inv_dim = 1.f / p.dim;
+  LnRow next = (slots && wave_global < rows) ? ln_row(p, wave_global) : LnRow{0, 0, 0};
   for (int row = wave_global; row < rows; row += nwaves) {
     const size_t base = static_cast<size_t>(row) * p.dim;
+    // where this row's hidden / normed live (compact batches); the whole-batch kernel keeps `base` for both
+    size_t hbase = base, obase = base;
+    bool has_h = true, has_o = true;
+    if (slots) {
+      const LnRow cur = next;
+      const int ahead = row + nwaves;
+      next = ln_row(p, ahead < rows ? ahead : row);
+      const int r = __builtin_amdgcn_readfirstlane(row) - cur.b * p.rows_per_batch;
+      has_h = cur.hs >= 0; has_o = cur.os >= 0;
+      hbase = (static_cast<size_t>(has_h ? cur.hs : 0) * p.rows_per_batch + r) * p.dim;
+      obase = (static_cast<size_t>(has_o ? cur.os : 0) * p.rows_per_batch + r) * p.dim;
+    }
+    if (!has_o) {
+      // no dnormed for this row: dx = dresidual_out (0 without one); residual_out, mean, rstd are not read and the
+      // weight / bias partials get nothing
+      const float scale = (p.rowscale && dhg) ? p.rowscale[row / p.rows_per_batch] : 1.f;
+#pragma unroll
+      for (int k = 0; k < kChunks; ++k) {
+        const int c = lane + 64 * k;
+        if (c < nch) {
+          const float4 dx = p.dresidual_out ? *reinterpret_cast<const float4*>(p.dresidual_out + base + 4 * c)
+                                            : make_float4(0, 0, 0, 0);
+          if (p.dresidual) *reinterpret_cast<float4*>(p.dresidual + base + 4 * c) = dx;
+          if (dhg && has_h)
+            st4<TH>(dhg + hbase + 4 * c, make_float4(dx.x * scale, dx.y * scale, dx.z * scale, dx.w * scale));
+        }
+      }
+      continue;
+    }
     const float mean = kRms ? 0.f : p.mean[row], rstd = p.rstd[row];
     float4 xh[kChunks], g[kChunks];
     float s1 = 0.f, s2 = 0.f;
@@ -154,7 +240,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
       const int c = lane + 64 * k;
       if (c < nch) {
         const float4 x = *reinterpret_cast<const float4*>(p.residual_out + base + 4 * c);
-        const float4 dy = ld4<TO>(dyg + base + 4 * c);
+        const float4 dy = ld4<TO>(dyg + obase + 4 * c);
         xh[k] = make_float4((x.x - mean) * rstd, (x.y - mean) * rstd, (x.z - mean) * rstd, (x.w - mean) * rstd);
         g[k] = make_float4(dy.x * w[k].x, dy.y * w[k].y, dy.z * w[k].z, dy.w * w[k].w);
         dw[k].x = fmaf(dy.x, xh[k].x, dw[k].x); dw[k].y = fmaf(dy.y, xh[k].y, dw[k].y);
@@ -184,7 +270,8 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_kernel(LnArgs p) {
           dx.x += r.x; dx.y += r.y; dx.z += r.z; dx.w += r.w;
         }
         if (p.dresidual) *reinterpret_cast<float4*>(p.dresidual + base + 4 * c) = dx;
-        if (dhg) st4<TH>(dhg + base + 4 * c, make_float4(dx.x * scale, dx.y * scale, dx.z * scale, dx.w * scale));
+        if (dhg && has_h)
+          st4<TH>(dhg + hbase + 4 * c, make_float4(dx.x * scale, dx.y * scale, dx.z * scale, dx.w * scale));
       }
     }
   }
@@ -263,23 +350,61 @@ extern "C" int simamba_add_layer_norm_grid(int batch, int rows_per_batch) {
   return ln_grid(rows > 2000000000ll ? 2000000000 : static_cast<int>(rows));
 }
 
-extern "C" int simamba_add_layer_norm_fwd_ex(const void* hidden, const float* residual, const float* rowscale,
-                                             const float* weight, const float* bias, float* residual_out, void* normed,
-                                             float* mean, float* rstd, int batch, int rows_per_batch, int dim,
-                                             float eps, int hidden_dtype, int out_dtype, int flags, void* stream) {
+// A slot map and its compact batch: null map <=> the tensor holds the whole batch.
+static int check_slots(const int* map, int compact_batch, int batch) {
+  if (compact_batch < 0 || compact_batch > batch) return SIMAMBA_E_SHAPE;
+  if (!map && compact_batch != batch) return SIMAMBA_E_NULLPTR;
+  return SIMAMBA_OK;
+}
+
+extern "C" int simamba_add_layer_norm_check_slots(const int* slots_host, int batch, int compact_batch) {
+  if (batch < 0 || compact_batch < 0 || compact_batch > batch) return SIMAMBA_E_SHAPE;
+  if (batch == 0) return SIMAMBA_OK;
+  if (!slots_host) return SIMAMBA_E_NULLPTR;
+  for (int b = 0; b < batch; ++b) {
+    const int s = slots_host[b];
+    if (s < -1 || s >= compact_batch) return SIMAMBA_E_SHAPE;
+    if (s < 0) continue;
+    for (int c = 0; c < b; ++c)
+      if (slots_host[c] == s) return SIMAMBA_E_SHAPE;      // two samples in one slot
+  }
+  return SIMAMBA_OK;
+}
+
+extern "C" int simamba_add_layer_norm_fwd_slots(const void* hidden, const float* residual, const float* rowscale,
+                                                const float* weight, const float* bias, float* residual_out,
+                                                void* normed, float* mean, float* rstd, const int* hidden_slot,
+                                                int hidden_batch, const int* normed_slot, int normed_batch, int batch,
+                                                int rows_per_batch, int dim, float eps, int hidden_dtype,
+                                                int out_dtype, int flags, void* stream) {
   if (flags & ~SIMAMBA_NORM_RMS) return SIMAMBA_E_VARIANT;
   const bool rms = (flags & SIMAMBA_NORM_RMS) != 0;
   if (rms && bias) return SIMAMBA_E_BIAS;
   int rc = check_ln(batch, rows_per_batch, dim);
   if (rc) return rc;
   if (batch == 0 || rows_per_batch == 0) return SIMAMBA_OK;
-  if (!hidden || !weight || !normed || (!mean && !rms) || !rstd) return SIMAMBA_E_NULLPTR;
+  if ((rc = check_slots(hidden_slot, hidden_batch, batch))) return rc;
+  if ((rc = check_slots(normed_slot, normed_batch, batch))) return rc;
+  if ((!hidden && hidden_batch) || !weight || (!normed && normed_batch) || (!mean && !rms) || !rstd)
+    return SIMAMBA_E_NULLPTR;
+  // a sample without hidden rows takes the residual: there has to be one, and somewhere to put the sum
+  if (hidden_slot && (!residual || !residual_out)) return SIMAMBA_E_NULLPTR;
   LnArgs a{};
   a.hidden = hidden; a.residual = residual; a.rowscale = rowscale; a.weight = weight; a.bias = bias;
   a.residual_out = residual_out; a.normed = normed; a.mean = mean; a.rstd = rstd;
+  a.hidden_slot = hidden_slot; a.normed_slot = normed_slot; a.hidden_batch = hidden_batch; a.normed_batch = normed_batch;
   a.batch = batch; a.rows_per_batch = rows_per_batch; a.dim = dim; a.eps = eps;
   return dispatch_ln(a, false, rms, simamba_add_layer_norm_grid(batch, rows_per_batch), hidden_dtype, out_dtype,
                      static_cast<hipStream_t>(stream));
+}
+
+extern "C" int simamba_add_layer_norm_fwd_ex(const void* hidden, const float* residual, const float* rowscale,
+                                             const float* weight, const float* bias, float* residual_out, void* normed,
+                                             float* mean, float* rstd, int batch, int rows_per_batch, int dim,
+                                             float eps, int hidden_dtype, int out_dtype, int flags, void* stream) {
+  return simamba_add_layer_norm_fwd_slots(hidden, residual, rowscale, weight, bias, residual_out, normed, mean, rstd,
+                                          nullptr, batch, nullptr, batch, batch, rows_per_batch, dim, eps, hidden_dtype,
+                                          out_dtype, flags, stream);
 }
 
 extern "C" int simamba_add_layer_norm_fwd(const void* hidden, const float* residual, const float* rowscale,
@@ -290,25 +415,42 @@ extern "C" int simamba_add_layer_norm_fwd(const void* hidden, const float* resid
                                        batch, rows_per_batch, dim, eps, hidden_dtype, out_dtype, 0, stream);
 }
 
-extern "C" int simamba_add_layer_norm_bwd_ex(const void* dnormed, const float* dresidual_out,
-                                             const float* residual_out, const float* mean, const float* rstd,
-                                             const float* weight, const float* rowscale, float* dresidual,
-                                             void* dhidden, float* dwb_partial, int batch, int rows_per_batch, int dim,
-                                             int hidden_dtype, int out_dtype, int flags, void* stream) {
+extern "C" int simamba_add_layer_norm_bwd_slots(const void* dnormed, const float* dresidual_out,
+                                                const float* residual_out, const float* mean, const float* rstd,
+                                                const float* weight, const float* rowscale, float* dresidual,
+                                                void* dhidden, float* dwb_partial, const int* hidden_slot,
+                                                int hidden_batch, const int* normed_slot, int normed_batch, int batch,
+                                                int rows_per_batch, int dim, int hidden_dtype, int out_dtype,
+                                                int flags, void* stream) {
   if (flags & ~SIMAMBA_NORM_RMS) return SIMAMBA_E_VARIANT;
   const bool rms = (flags & SIMAMBA_NORM_RMS) != 0;
   int rc = check_ln(batch, rows_per_batch, dim);
   if (rc) return rc;
   if (batch == 0 || rows_per_batch == 0) return SIMAMBA_OK;
-  if (!dnormed || !residual_out || (!mean && !rms) || !rstd || !weight || !dwb_partial || (!dresidual && !dhidden))
-    return SIMAMBA_E_NULLPTR;
+  if ((rc = check_slots(hidden_slot, hidden_batch, batch))) return rc;
+  if ((rc = check_slots(normed_slot, normed_batch, batch))) return rc;
+  // an empty compact dhidden is as good as none; an empty dnormed leaves residual_out, mean and rstd unread
+  if (hidden_batch == 0) dhidden = nullptr;
+  if ((!dnormed || !residual_out || (!mean && !rms) || !rstd) && normed_batch) return SIMAMBA_E_NULLPTR;
+  if (!weight || !dwb_partial || (!dresidual && !dhidden)) return SIMAMBA_E_NULLPTR;
   LnArgs a{};
   a.dnormed = dnormed; a.dresidual_out = dresidual_out; a.residual_out = const_cast<float*>(residual_out);
   a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.weight = weight; a.rowscale = rowscale;
   a.dresidual = dresidual; a.dhidden = dhidden; a.dwb_partial = dwb_partial;
+  a.hidden_slot = hidden_slot; a.normed_slot = normed_slot; a.hidden_batch = hidden_batch; a.normed_batch = normed_batch;
   a.batch = batch; a.rows_per_batch = rows_per_batch; a.dim = dim;
   return dispatch_ln(a, true, rms, simamba_add_layer_norm_grid(batch, rows_per_batch), hidden_dtype, out_dtype,
                      static_cast<hipStream_t>(stream));
+}
+
+extern "C" int simamba_add_layer_norm_bwd_ex(const void* dnormed, const float* dresidual_out,
+                                             const float* residual_out, const float* mean, const float* rstd,
+                                             const float* weight, const float* rowscale, float* dresidual,
+                                             void* dhidden, float* dwb_partial, int batch, int rows_per_batch, int dim,
+                                             int hidden_dtype, int out_dtype, int flags, void* stream) {
+  return simamba_add_layer_norm_bwd_slots(dnormed, dresidual_out, residual_out, mean, rstd, weight, rowscale, dresidual,
+                                          dhidden, dwb_partial, nullptr, batch, nullptr, batch, batch, rows_per_batch,
+                                          dim, hidden_dtype, out_dtype, flags, stream);
 }
 
 extern "C" int simamba_add_layer_norm_bwd(const void* dnormed, const float* dresidual_out, const float* residual_out,

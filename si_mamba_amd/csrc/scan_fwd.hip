@@ -195,8 +195,15 @@ extern "C" int simamba_scan_fwd_auto_variant(int batch, int dim) {
 extern "C" int simamba_scan_ckpt_step(int batch, int dim, int seqlen, int dstate, int io_dtype) {
   if (batch <= 0 || dim <= 0 || seqlen <= 0) return SIMAMBA_SCAN_CKPT_ROW;
   const long long rows = static_cast<long long>(batch) * dim;
+  // Long sequences keep the sequential pair down to 36 864 rows: a mixer that runs on part of a batch of 64 (the
+  // samples DropPath keeps, 48 .. 60 of them) would otherwise fall back to the row-scan pair just below the line.
+  // Measured inside the fp32 mixer at (B, 768, 1024), forward + backward kernel, us: B = 60 row-scan pair 340 + 971,
+  // sequential pair (four lanes per channel forward) 279 + 702; B = 56 334 + 957 against 240 + 691; B = 52 305 + 961
+  // against 241 + 696; B = 48 289 + 942 against 230 + 685.  Short sequences and bf16 I/O were not measured and keep
+  // the line.
+  const bool long_rows = io_dtype == SIMAMBA_F32 && seqlen >= 1024 && rows >= 36 * 1024;
   if (dstate == kMaxState && dim % 64 == 0 && seqlen % io_pack(io_dtype) == 0 && rows * seqlen < (1ll << 30) &&
-      auto_variant(rows, batch, dim) != SIMAMBA_SCAN_ROWSCAN)
+      (auto_variant(rows, batch, dim) != SIMAMBA_SCAN_ROWSCAN || long_rows))
     return SIMAMBA_SCAN_CKPT_SEQ;
   return SIMAMBA_SCAN_CKPT_ROW;
 }

@@ -221,6 +221,7 @@ class MaskMamba_2(nn.Module):
         self.mask_type = tc.mask_type
         self.pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, self.trans_dim))
         self.blocks = MixerModel(d_model=self.trans_dim, n_layer=self.depth, rms_norm=config.rms_norm)
+        self.blocks.drop_path_compact = False           # the classifier's route (block.py); not measured here
         self.norm = nn.LayerNorm(self.trans_dim)
         self.apply(self._init_weights)
 
@@ -293,6 +294,7 @@ class MambaDecoder_SST(nn.Module):
         super().__init__()
         self.blocks = MixerModel(d_model=embed_dim, n_layer=depth, rms_norm=config.rms_norm,
                                  drop_path=config.drop_path)
+        self.blocks.drop_path_compact = False
         self.norm = norm_layer(embed_dim)
         self.head = nn.Identity()
         self.apply(self._init_weights)

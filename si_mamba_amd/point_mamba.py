@@ -232,6 +232,23 @@ class PointMamba(nn.Module):
         t, p, _, _ = spectral.hlt_assemble(tokens, pos, center, vecs, self.k_top_eigenvectors, rand=rand)
         return t, p
 
+    def _draw_drop_plan(self, pts):
+        """The stack's DropPath factors, drawn before the tokeniser (MixerModel.draw_drop_plan): their copy to the host,
+        which the stack waits for to plan its compact batches, then finishes underneath FPS, grouping and the
+        encoder.  Only on the route that hands the stack the distinct tokens (SAST / MAMBA, no input dropout): nothing
+        between here and the blocks draws from the generator there, so every draw keeps its place in the sequence.
+        Every other route returns None and leaves the draw to the stack's entry."""
+        if self.add_after_layer or self.method not in ("SAST", "MAMBA") or not pts.is_cuda or pts.dim() != 3 \
+                or (self.training and self.drop_out.p > 0):
+            return None
+        G = self.num_group
+        L = 3 * G if self.method == "MAMBA" else self.k_top_eigenvectors * G * (2 if self.reverse else 1)
+        # shape and device of the tokens the stack will be handed (no storage behind it)
+        like = torch.empty_strided((pts.shape[0], G, self.trans_dim), (0, 0, 0), device=pts.device)
+        if not self.blocks._compact_ok(like):
+            return None
+        return self.blocks.draw_drop_plan(like, lead=not self.blocks._first_block_applies(like, L))
+
     def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None, *, lengths=None):
         """Reference signature (models/point_mamba.py:843; the runner calls
         ``base_model(points, gt=None, tau=None, use_wavelets=True)``, tools/runner_finetune.py:201).  Built: the
@@ -252,6 +269,7 @@ class PointMamba(nn.Module):
         want_policy = gt is not None
         if want_policy and self.method != "SAST":
             raise NotImplementedError("PointMamba.forward(gt=...): the reference defines `policy` on the SAST route only")
+        drop_plan = self._draw_drop_plan(pts)
         neighborhood, center, _ = self.group_divider(pts, lengths=lengths)
         order = spec = None
         overlap = center.is_cuda and self.method == "SAST"
@@ -283,7 +301,8 @@ class PointMamba(nn.Module):
         elif idx is not None and not (self.training and self.drop_out.p > 0):
             # the sequence is a gather of the G patch tokens: the stack takes the distinct tokens plus the index map
             # and runs the first block's per-token head on G instead of L positions (seq_expand.py); same result
-            x = self.blocks(tokens, pos, token_index=idx, balanced_index=True)     # concatenated permutations
+            x = self.blocks(tokens, pos, token_index=idx, balanced_index=True,     # concatenated permutations
+                            drop_plan=drop_plan)
         else:
             x, pos = self.order_tokens(tokens, pos, center, order)
             x = self.drop_out(x)

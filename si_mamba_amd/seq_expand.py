@@ -67,6 +67,11 @@ def seq_gather_last(x, idx32, inv32):
 
 def expansion_ok(x, token_index):
     """Shapes the copy kernels take (include/simamba.h)."""
-    G, L = x.shape[1], token_index.shape[1]
+    return expansion_len_ok(x, token_index.shape[1])
+
+
+def expansion_len_ok(x, L):
+    """expansion_ok for an index map of L positions (answerable before the map exists)."""
+    G = x.shape[1]
     return (x.is_cuda and x.dim() == 3 and G % 4 == 0 and L % 4 == 0 and G <= 256 and L <= 2048 and L % G == 0
             and L // G <= 8)
