@@ -26,6 +26,8 @@
  *   simamba_spectral_topk            the two above fused: centres -> top-k eigenpairs + orders.
  *   simamba_argsort_rows             the torch.sort of models/point_mamba.py:820.
  *   simamba_farthest_point_sample    pytorch3d.ops.sample_farthest_points, models/point_mamba.py:93.
+ *   simamba_augment_points           tools/runner_finetune.py:191-194 (fps_idx[:, choice], gather_operation) and the
+ *                                    transforms of datasets/data_transforms.py, one launch per batch.
  *
  * Conventions
  *   - Plain pointers and sizes only.  All pointers are DEVICE pointers unless noted.
@@ -708,6 +710,80 @@ int simamba_part_seg_eval(const void* scores, const long long* target, const int
                           const long long* lengths, long long* pred, int* inter, int* uni, double* shape_iou,
                           int* correct, long long* seen_class, long long* correct_class, long long batch, int n, int c,
                           int io_dtype, void* stream);
+
+/*
+ * Sampling and augmentation of a batch of clouds in front of a step (csrc/augment.hip; the reference's
+ * tools/runner_finetune.py:191-194 and datasets/data_transforms.py): for every cloud b and output row i < K
+ *   out[b][i] = chain(points[b][ idx[b][ sel[i] ] ])
+ * in one launch, one workgroup per cloud, followed by a one-lane kernel that adds 1 to the step.
+ *   points   : (B, N, 3) fp32.                                        1 <= N, M, K <= 8192 ; 1 <= B < 2^31.
+ *   idx      : (B, M) int32 (idx_is_64 == 0) or int64 rows into the cloud, or NULL (= the identity; then M == N).
+ *   sel      : (K) int64 positions into idx's columns, shared by the batch, or NULL (= the identity; then K == M).
+ *              The kernel forces every sel entry into [0, M) and every idx entry into [0, N) before it is used.
+ *   lengths  : (B) int64, device, or NULL (= K everywhere): cloud b has lengths[b] output rows (clamped to [1, K] by
+ *              the kernel).  Rows at and behind the length are written as 0; nothing is looked up or read for them, and
+ *              flip's maximum and dropout pass them over.
+ *   out      : (B, K, 3) fp32.  It may be `points` itself only when idx and sel are both NULL (in place, row for row);
+ *              any other overlap of the two is refused (SIMAMBA_E_VARIANT).
+ *   ops, op_params : HOST arrays of n_ops opcodes and n_ops x 4 fp32 parameters, 0 <= n_ops <= 8; read during the call:
+ *     SIMAMBA_AUG_ROTATE           -                  theta = u0 * fp32(2 pi); x' = x cos - z sin, y' = y, z' = x sin + z cos
+ *     SIMAMBA_AUG_SCALE            lo, hi             s_a = lo + u_a * (hi - lo);                   p'_a = p_a * s_a
+ *     SIMAMBA_AUG_TRANSLATE        r                  t_a = -r + u_a * (2 r);                       p'_a = p_a + t_a
+ *     SIMAMBA_AUG_SCALE_TRANSLATE  lo, hi, r          s from block 0, t from block 1;               p'_a = p_a * s_a + t_a
+ *     SIMAMBA_AUG_JITTER           std, clip          p'_a = p_a + min(max(std * n_a, -clip), clip), n standard normal
+ *     SIMAMBA_AUG_DROPOUT          max_ratio          ratio = u0 * max_ratio; row i becomes the cloud's current row 0
+ *                                                     iff u_i <= ratio
+ *     SIMAMBA_AUG_FLIP             upright axis 0|1|2 gate = u0 < 0.95; the j-th horizontal axis a (ascending) is flipped
+ *                                                     iff gate and u_(1+j) < 0.5: p'_a = max_rows(p_a) - p_a (a NaN is
+ *                                                     passed over by the maximum)
+ *     An unknown opcode or another upright axis: SIMAMBA_E_VARIANT.
+ *   state    : (2) int64, device: [seed, step].  Read by the kernel; step + 1 is written behind it in stream order.
+ *              Nothing is read on the host, so the call can be captured and every replay draws anew.
+ * Random numbers: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *     c0 = the output row i for a per-point draw, the block number (0, 1) for a per-cloud draw
+ *     c1 = the cloud b
+ *     c2 = step & 0xffffffff
+ *     c3 = ((step >> 32) & 0x0fffffff) | position of the op in the chain << 28 | (per-point draw ? 1 : 0) << 31
+ *   so no two ops of a chain share a stream, and the result for (seed, step, b, i, chain) depends on nothing else: not
+ *   on B, the launch geometry or the other clouds.  (step counts modulo 2^60.)
+ *   u_k of a block = (word k >> 8) * 2^-24.  Per-cloud draws use block 0 (SCALE_TRANSLATE's t: block 1), words 0..2
+ *   for the axes x, y, z.  DROPOUT's u_i is word 0 of row i's block.  JITTER's normals are Box-Muller on row i's block:
+ *     n_x = R(w0) cos(2 pi u(w1)), n_y = R(w0) sin(2 pi u(w1)), n_z = R(w2) cos(2 pi u(w3)),
+ *     R(w) = sqrt(-2 ln(((w >> 8) + 1) * 2^-24)).
+ *   Every product and sum above is one correctly rounded fp32 operation (no contraction), so theta, s, t, ratio and the
+ *   keep / flip decisions can be reproduced bit for bit; cos, sin and ln are the device library's.
+ * Checks in the order shape (SIMAMBA_E_SHAPE: B, N, M, K, n_ops, M != N without idx, K != M without sel), null pointers
+ * (points, out, state; ops and op_params when n_ops > 0), chain (SIMAMBA_E_VARIANT), overlap; all before any launch.
+ *
+ * simamba_augment_params: what the call above draws for the same chain and state, and no points; step is not advanced.
+ *   cloud_params : (B, n_ops, 8) fp32; per op [theta, cos, sin] | [s_x, s_y, s_z] | [t_x, t_y, t_z] |
+ *                  [s_x, s_y, s_z, t_x, t_y, t_z] | [std, clip] | [ratio] | [gate, flip_x, flip_y, flip_z] (0 / 1, the
+ *                  gate already applied to the three), the rest 0.
+ *   noise        : (B, K, 3) fp32 or NULL: n of the chain's FIRST jitter op (before std and the clip); 0 behind a length
+ *                  or without a jitter op.
+ *   keep         : (B, K) uint8 or NULL: 0 where the chain's FIRST dropout op replaces the row (u_i <= ratio) and
+ *                  behind a length, else 1.
+ *
+ * simamba_philox4x32_10: HOST only, compiled from the header the kernels draw with: the four words of counter
+ * (c0, c1, c2, c3) under the key of `seed`, into the host array out[4].
+ * Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_AUG_ROTATE          1
+#define SIMAMBA_AUG_SCALE           2
+#define SIMAMBA_AUG_TRANSLATE       3
+#define SIMAMBA_AUG_SCALE_TRANSLATE 4
+#define SIMAMBA_AUG_JITTER          5
+#define SIMAMBA_AUG_DROPOUT         6
+#define SIMAMBA_AUG_FLIP            7
+#define SIMAMBA_AUG_MAX_OPS         8
+#define SIMAMBA_AUG_CLOUD_PARAMS    8
+int simamba_augment_points(const float* points, const void* idx, int idx_is_64, const long long* sel,
+                           const long long* lengths, float* out, const int* ops, const float* op_params, int n_ops,
+                           long long* state, long long B, int N, int M, int K, void* stream);
+int simamba_augment_params(const long long* lengths, const int* ops, const float* op_params, int n_ops,
+                           const long long* state, float* cloud_params, float* noise, unsigned char* keep, long long B,
+                           int K, void* stream);
+int simamba_philox4x32_10(long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
 
 /*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,

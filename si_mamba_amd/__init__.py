@@ -13,8 +13,16 @@ from .shim import install_shim
 from .emd import earth_movers_distance
 from .sinkhorn import sinkhorn_divergence
 from .seg_metrics import SHAPENETPART, PartSegMetrics, PartTable, part_seg_eval
+from . import transforms
+from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRandomInputDropout, PointcloudRotate,
+                         PointcloudScale, PointcloudScaleAndTranslate, PointcloudTranslate, RandomHorizontalFlip,
+                         sample_and_augment)
+from .vote import vote_logits
 from ._lib import deterministic, deterministic_enabled, set_deterministic
 
-__all__ = ["SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
+__all__ = ["transforms", "AugmentState", "Compose", "PointcloudJitter", "PointcloudRandomInputDropout",
+           "PointcloudRotate", "PointcloudScale", "PointcloudScaleAndTranslate", "PointcloudTranslate",
+           "RandomHorizontalFlip", "sample_and_augment", "vote_logits",
+"SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
            "set_deterministic", "earth_movers_distance", "sinkhorn_divergence"]

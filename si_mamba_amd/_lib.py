@@ -35,6 +35,12 @@ BWD_DETERMINISTIC = 1
 NORM_RMS = 1
 # flags of simamba_sinkhorn_fwd / _bwd: subtract the two self-transport terms
 SINKHORN_DEBIAS = 1
+# opcodes of simamba_augment_points / _params (transforms.py); at most AUG_MAX_OPS per launch, AUG_CLOUD_PARAMS floats
+# per (cloud, op) from simamba_augment_params
+AUG_ROTATE, AUG_SCALE, AUG_TRANSLATE, AUG_SCALE_TRANSLATE, AUG_JITTER, AUG_DROPOUT, AUG_FLIP = 1, 2, 3, 4, 5, 6, 7
+AUG_MAX_OPS = 8
+AUG_CLOUD_PARAMS = 8
+AUG_MAX_POINTS = 8192
 
 # name -> (restype, argtypes); mirrors include/simamba.h one to one
 _P = c_void_p
@@ -135,6 +141,9 @@ SIGNATURES = {
     "simamba_sinkhorn_fwd": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P]),
     "simamba_sinkhorn_bwd": (c_int, [_P] * 11 + [_LL, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
     "simamba_part_seg_eval": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_int, _P]),
+    "simamba_augment_points": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _LL, c_int, c_int, c_int, _P]),
+    "simamba_augment_params": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _LL, c_int, _P]),
+    "simamba_philox4x32_10": (c_int, [_LL, c_uint, c_uint, c_uint, c_uint, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),

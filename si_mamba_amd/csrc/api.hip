@@ -16,7 +16,7 @@ extern "C" const char* simamba_strerror(int rc) {
     case SIMAMBA_E_WORKSPACE: return "simamba: workspace missing or too small";
     case SIMAMBA_E_GROUPS: return "simamba: need 2 <= G <= 128 (512 for the graph, _ex and fused calls), knn + 1 <= min(G, 32), k (+1) <= G (<= 8 above 128), 1 <= F <= 64";
     case SIMAMBA_E_ALIGN: return "simamba: pointer not aligned";
-    case SIMAMBA_E_VARIANT: return "simamba: scan variant unknown or not applicable to this shape, or unknown flag bits";
+    case SIMAMBA_E_VARIANT: return "simamba: scan variant unknown or not applicable to this shape, unknown flag bits, or an augmentation chain / buffer overlap the call cannot take";
     case SIMAMBA_E_BIAS: return "simamba: SIMAMBA_NORM_RMS takes no bias / beta (pass NULL)";
     default: break;
   }

@@ -55,6 +55,16 @@ class GraphedTrainStep:
     ``capturable=True``, no host synchronisation inside ``loss_fn`` (no ``.item()``, no shape that depends on data).
     Random ops (DropPath, Dropout, the HLT tie-break) draw from the graph-safe Philox stream.
 
+    Sampling and augmentation belong inside ``loss_fn`` (transforms.sample_and_augment: one launch, its random numbers
+    keyed by a device-side ``AugmentState`` that every replay reads and advances, so each step draws anew); the subset
+    of the sampled points is a static input like any other, drawn on the device before the call:
+
+        state = AugmentState(seed, device)                       # before the capture: it copies from the host
+        def loss_fn(raw, fps_idx, sel, gt):
+            return criterion(model(sample_and_augment(raw, train_transforms, idx=fps_idx, sel=sel, state=state)), gt)
+        step = GraphedTrainStep(loss_fn, optimizer, (raw, fps_idx, sel, gt), clip=10.0)
+        loss = step(raw, fps_idx, torch.randperm(point_all, device=device)[:npoints], gt)
+
     Data-parallel (``process_group=``, keyword-only; ``dist.group.WORLD`` for the default group):
 
         init_dist()

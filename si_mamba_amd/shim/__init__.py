@@ -15,6 +15,12 @@ on the HIP kernels, with the call forms and return shapes the reference uses, pl
 ``random_start_point`` arguments of the first two for ragged batches (clouds padded to a common point count), and
 everything but the normals of the third (``x_lengths`` / ``y_lengths``, ``weights``, ``norm``, ``point_reduction``,
 ``single_directional``).
+
+``install_shim(pointnet2=True)`` registers ``pointnet2_ops.pointnet2_utils`` with the two calls the reference's runners
+make (tools/runner_finetune.py:15, :191-194; tools/runner_pretrain.py:17; utils/misc.py:10;
+part_segmentation/models/pt_mamba.py:11): ``furthest_point_sample(xyz, K) -> (B, K) int32`` on the FPS kernel and
+``gather_operation(features (B, C, N), idx (B, K)) -> (B, C, K)``, differentiable in ``features``.  (The sampling and
+the gather fused with the augmentation chain is ``si_mamba_amd.transforms.sample_and_augment``.)
 """
 from __future__ import annotations
 
@@ -22,15 +28,16 @@ import sys
 import types
 
 
-def install_shim(force: bool = False, pytorch3d: bool = False):
-    """Register ``mamba_ssm`` and ``causal_conv1d`` (and, on request, ``pytorch3d``) stand-ins.  Refuses to shadow
-    real packages."""
+def install_shim(force: bool = False, pytorch3d: bool = False, pointnet2: bool = False):
+    """Register ``mamba_ssm`` and ``causal_conv1d`` (and, on request, ``pytorch3d`` and ``pointnet2_ops``) stand-ins.
+    Refuses to shadow real packages."""
     from .. import causal_conv1d as _cc
     from .. import mamba_simple as _ms
     from .. import selective_scan as _ss
 
     if not force:
-        for name in ("mamba_ssm", "causal_conv1d") + (("pytorch3d",) if pytorch3d else ()):
+        for name in ("mamba_ssm", "causal_conv1d") + (("pytorch3d",) if pytorch3d else ()) \
+                + (("pointnet2_ops",) if pointnet2 else ()):
             mod = sys.modules.get(name)
             if mod is not None and not getattr(mod, "__simamba_shim__", False):
                 raise RuntimeError(f"a real '{name}' package is already imported; pass force=True to shadow it")
@@ -61,7 +68,35 @@ def install_shim(force: bool = False, pytorch3d: bool = False):
     _mod("causal_conv1d", causal_conv1d_fn=_cc.causal_conv1d_fn)
     if pytorch3d:
         _install_pytorch3d(_mod)
+    if pointnet2:
+        _install_pointnet2(_mod)
     return root
+
+
+def _install_pointnet2(_mod):
+    """The two pointnet2_ops calls of the reference's runners, with their argument forms:
+         fps_idx = pointnet2_utils.furthest_point_sample(points, point_all)                    (runner_finetune.py:191)
+         pointnet2_utils.gather_operation(points.transpose(1, 2).contiguous(), fps_idx)        (:193)."""
+    import torch
+
+    from .. import _lib, grouping
+
+    def furthest_point_sample(xyz, npoint):
+        """(B, N, 3), K -> (B, K) int32: farthest-point sampling from point 0, ties to the lower index."""
+        return grouping.sample_farthest_points(xyz, int(npoint))[1].to(torch.int32)
+
+    def gather_operation(features, idx):
+        """features (B, C, N), idx (B, K) integers -> (B, C, K) = features[b, :, idx[b, k]]; differentiable in
+        ``features`` (the gradient is scattered back and summed over repeated indices)."""
+        _lib.require_gpu(features, "gather_operation")
+        if features.dim() != 3 or idx.dim() != 2 or idx.shape[0] != features.shape[0]:
+            raise ValueError(f"gather_operation: features (B, C, N) and idx (B, K), got {tuple(features.shape)} and "
+                             f"{tuple(idx.shape)}")
+        return torch.gather(features, 2, idx.long().unsqueeze(1).expand(-1, features.shape[1], -1))
+
+    root = _mod("pointnet2_ops")
+    root.pointnet2_utils = _mod("pointnet2_ops.pointnet2_utils", furthest_point_sample=furthest_point_sample,
+                                gather_operation=gather_operation)
 
 
 def _install_pytorch3d(_mod):
