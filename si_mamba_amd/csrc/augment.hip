@@ -19,6 +19,7 @@
 // drawn parameters and the keep / flip decisions bit for bit.  cos / sin / log are the device library's.
 #include "host_common.h"
 #include "philox.h"
+#include "pointset.h"
 
 namespace simamba {
 
@@ -145,18 +146,6 @@ __device__ __forceinline__ AugDraw aug_draw_cloud(const AugRng& r, int pos, int 
   return d;
 }
 
-__device__ __forceinline__ int aug_length(const long long* __restrict__ lengths, long long b, int K) {
-  if (!lengths) return K;
-  const long long l = lengths[b];
-  return l < 1 ? 1 : (l > K ? K : static_cast<int>(l));
-}
-
-__device__ __forceinline__ float aug_wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 template <typename IdxT>
 __global__ __launch_bounds__(kAugMaxThreads) void augment_points_kernel(
     const float* points, const IdxT* __restrict__ idx, const long long* __restrict__ sel,
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(kAugMaxThreads) void augment_points_kernel(
   __shared__ float sFirst[3];
   const long long b = blockIdx.x;
   const int T = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = T >> 6;
-  const int len = aug_length(lengths, b, K);
+  const int len = clamped_length(lengths, b, K);
   const AugRng rng = aug_rng(state, blockIdx.x);
 
   // rows >= len stay 0 and are never looked up; every index is forced into its range before it is used
@@ -276,9 +265,9 @@ __global__ __launch_bounds__(kAugMaxThreads) void augment_points_kernel(
             mz = fmaxf(mz, z[j]);
           }
         }
-        mx = aug_wave_max(mx);
-        my = aug_wave_max(my);
-        mz = aug_wave_max(mz);
+        mx = wave_xor_max(mx);
+        my = wave_xor_max(my);
+        mz = wave_xor_max(mz);
         if (lane == 0) {
           sMax[0][wave] = mx;
           sMax[1][wave] = my;
@@ -329,7 +318,7 @@ __global__ __launch_bounds__(kAugMaxThreads) void augment_params_kernel(
     float* __restrict__ cloud_params, float* __restrict__ noise, unsigned char* __restrict__ keep, int K) {
   const long long b = blockIdx.x;
   const int T = blockDim.x, tid = threadIdx.x;
-  const int len = aug_length(lengths, b, K);
+  const int len = clamped_length(lengths, b, K);
   const AugRng rng = aug_rng(state, blockIdx.x);
   int jitter_at = -1, dropout_at = -1;                               // the chain's first of each
   float ratio = 0.f;

@@ -13,12 +13,6 @@ namespace simamba {
 
 constexpr int kChWaves = 4;     // pairs per workgroup
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * kChWaves) void chamfer_fwd_kernel(const float* __restrict__ pred,
                                                                      const float* __restrict__ gt,
                                                                      float* __restrict__ dist,
@@ -58,7 +52,7 @@ __global__ __launch_bounds__(64 * kChWaves) void chamfer_fwd_kernel(const float*
     s2 = best;
     idx2[pr * m + lane] = static_cast<unsigned char>(bi);
   }
-  const float t1 = wave_sum(s1), t2 = wave_sum(s2);
+  const float t1 = wave_xor_sum(s1), t2 = wave_xor_sum(s2);
   if (lane == 0) dist[pr] = t1 / static_cast<float>(n) + t2 / static_cast<float>(m);
 }
 

@@ -36,30 +36,13 @@
 #include <type_traits>
 
 #include "host_common.h"
+#include "pointset.h"
 
 namespace simamba {
 
 constexpr int kChThreads = 256;
 constexpr int kChTile = 1024;        // targets per LDS tile: 16 KB
 constexpr int kChMaxPoints = 8192;
-
-// Stage targets [t0, t0 + cnt) of `set` (cnt <= kChTile) as float4; .w carries tag[t] (an int, bit-cast) or 0.
-__device__ __forceinline__ void stage_tile(float4* sT, const float* __restrict__ set, const int* __restrict__ tag,
-                                           int t0, int cnt) {
-  float* s = reinterpret_cast<float*>(sT);
-  const float* g = set + static_cast<long long>(t0) * 3;
-  for (int e = threadIdx.x; e < cnt * 3; e += kChThreads) {      // coalesced: consecutive lanes, consecutive floats
-    const int t = e / 3;
-    s[4 * t + (e - 3 * t)] = g[e];
-  }
-  if (tag)
-    for (int t = threadIdx.x; t < cnt; t += kChThreads) s[4 * t + 3] = __builtin_bit_cast(float, tag[t0 + t]);
-}
-
-// The length of pair `pr`'s set: len[pr] clamped to [1, padded], or `padded` without lengths.  Workgroup-uniform.
-__device__ __forceinline__ int pair_length(const int* __restrict__ len, long long pr, int padded) {
-  return len ? min(max(len[pr], 1), padded) : padded;
-}
 
 // rho(a, b) of one coordinate triple, from the differences
 template <int NORM>
@@ -89,7 +72,7 @@ __global__ __launch_bounds__(kChThreads) void chamfer_large_nn_kernel(const floa
   const int r = static_cast<int>(blockIdx.x - pr * (bx + by));
   const bool fwd = r < bx;                                       // workgroup-uniform
   const int nqp = fwd ? n : m, ntp = fwd ? m : n;                // padded sizes: the strides
-  const int nq = pair_length(fwd ? xlen : ylen, pr, nqp), nt = pair_length(fwd ? ylen : xlen, pr, ntp);
+  const int nq = clamped_length(fwd ? xlen : ylen, pr, nqp), nt = clamped_length(fwd ? ylen : xlen, pr, ntp);
   const float* qs = (fwd ? x : y) + pr * nqp * 3;
   const float* ts = (fwd ? y : x) + pr * ntp * 3;
   int* oi = (fwd ? idx1 : idx2) + pr * nqp;
@@ -116,7 +99,7 @@ __global__ __launch_bounds__(kChThreads) void chamfer_large_nn_kernel(const floa
   for (int t0 = 0; t0 < nt; t0 += kChTile) {
     const int cnt = min(kChTile, nt - t0);
     __syncthreads();
-    stage_tile(sT, ts, nullptr, t0, cnt);
+    stage_points<kChThreads>(sT, ts, t0, cnt);
     __syncthreads();
     if (!wave_live) continue;
 #pragma unroll 4
@@ -144,23 +127,19 @@ __global__ __launch_bounds__(kChThreads) void chamfer_large_reduce_kernel(const 
                                                                           const int* __restrict__ ylen,
                                                                           float* __restrict__ dist, int n, int m,
                                                                           int mean) {
-  __shared__ double s1[kChThreads], s2[kChThreads];
+  __shared__ double sS[2][kChThreads];
   const long long pr = blockIdx.x;
-  const int nx = pair_length(xlen, pr, n), ny = pair_length(ylen, pr, m);
+  const int nx = clamped_length(xlen, pr, n), ny = clamped_length(ylen, pr, m);
   const float* a = d1 + pr * n;
   const float* b = d2 ? d2 + pr * m : nullptr;                   // one-way: no second term
   double t1 = 0.0, t2 = 0.0;
   for (int i = threadIdx.x; i < nx; i += kChThreads) t1 += static_cast<double>(a[i]);
   if (b)
     for (int j = threadIdx.x; j < ny; j += kChThreads) t2 += static_cast<double>(b[j]);
-  s1[threadIdx.x] = t1; s2[threadIdx.x] = t2;
-  __syncthreads();
-  for (int w = kChThreads / 2; w >= 1; w >>= 1) {
-    if (threadIdx.x < w) { s1[threadIdx.x] += s1[threadIdx.x + w]; s2[threadIdx.x] += s2[threadIdx.x + w]; }
-    __syncthreads();
-  }
+  sS[0][threadIdx.x] = t1; sS[1][threadIdx.x] = t2;
+  block_tree_sum(sS);
   if (threadIdx.x == 0) {
-    const double a1 = mean ? s1[0] / nx : s1[0], a2 = mean ? s2[0] / ny : s2[0];
+    const double a1 = mean ? sS[0][0] / nx : sS[0][0], a2 = mean ? sS[1][0] / ny : sS[1][0];
     dist[pr] = static_cast<float>(b ? a1 + a2 : a1);
   }
 }
@@ -189,7 +168,7 @@ __global__ __launch_bounds__(kChThreads) void chamfer_large_bwd_kernel(const flo
   const int r = static_cast<int>(blockIdx.x - pr * (bx + by));
   const bool forx = r < bx;
   const int nsp = forx ? n : m, nop = forx ? m : n;              // own set, other set: padded sizes (the strides)
-  const int ns = pair_length(forx ? xlen : ylen, pr, nsp), no = pair_length(forx ? ylen : xlen, pr, nop);
+  const int ns = clamped_length(forx ? xlen : ylen, pr, nsp), no = clamped_length(forx ? ylen : xlen, pr, nop);
   const float* self = (forx ? x : y) + pr * nsp * 3;
   const float* other = (forx ? y : x) + pr * nop * 3;
   const int* near_other = (forx ? idx1 : idx2) + pr * nsp;       // nearest of the other set, per own point
@@ -234,7 +213,8 @@ __global__ __launch_bounds__(kChThreads) void chamfer_large_bwd_kernel(const flo
   for (int t0 = 0; reverse && t0 < no; t0 += kChTile) {
     const int cnt = min(kChTile, no - t0);
     __syncthreads();
-    stage_tile(sT, other, near_self, t0, cnt);
+    stage_points<kChThreads>(sT, other, t0, cnt);
+    stage_w<kChThreads>(sT, near_self, t0, cnt);    // (y_j, b(j)) in one float4
     if constexpr (POINTWISE)
       for (int t = threadIdx.x; t < cnt; t += kChThreads) sC[t] = kScale * c_other[t0 + t];
     __syncthreads();

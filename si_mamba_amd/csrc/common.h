@@ -97,6 +97,23 @@ __device__ __forceinline__ float wave_allreduce_sum(float v) {
   return v;
 }
 
+// The same reductions as a plain xor butterfly, offsets 32 -> 1, result in every lane.  Both sums stay: the butterfly
+// pairs lane l with l ^ 32 first, wave_allreduce_sum with l ^ 1 first, so float sums differ in their last bits, and the
+// callers of each are pinned to their order by bitwise tests.  Neither replaces the other.
+template <typename T>                               // float, int or double
+__device__ __forceinline__ T wave_xor_sum(T v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ float wave_xor_max(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+// The (value, index) butterflies of fps.hip, knn_group.hip and spectral_device.h stay spelled out where they are: through
+// a shared helper with the rule as a callable the compiler schedules those kernels differently.
+
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }

@@ -27,12 +27,6 @@ constexpr int kEmdWaves = 4;          // pairs per workgroup of the one-wave ker
 constexpr int kEmdMaxN = 1024;
 constexpr float kEmdEpsFloor = 1e-30f;  // eps_final when cmax == 0 (every point the same): any positive number does
 
-// 0: every wave scans lane per bidder whatever the number of its bidders (an alternative build, for the comparison of
-// tools/bench_emd.py --alt-lib; the results are the same bits)
-#ifndef SIMAMBA_EMD_SHARED_SCAN
-#define SIMAMBA_EMD_SHARED_SCAN 1
-#endif
-
 typedef unsigned long long emd_slot_t;
 
 struct EmdLds {          // one pair's state; N entries each
@@ -61,20 +55,9 @@ template <bool kWave> __device__ __forceinline__ int emd_count(bool p) {
   return __syncthreads_count(p);
 }
 
-__device__ __forceinline__ float emd_wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float emd_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // max (kMax) or sum over the pair's lanes, the same value in every lane, the same bits every time
 template <bool kWave, bool kMax> __device__ __forceinline__ float emd_reduce(float v, float* red) {
-  v = kMax ? emd_wave_max(v) : emd_wave_sum(v);
+  v = kMax ? wave_xor_max(v) : wave_xor_sum(v);
   if (kWave) return v;
   const int wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
   __syncthreads();                                  // red may still be read from the previous reduction
@@ -111,7 +94,7 @@ __device__ __forceinline__ void emd_pair(const float* __restrict__ X, const floa
   const int lane = threadIdx.x & 63;
   // bidders per wave up to which the shared scan is the shorter one: n steps of about 14 instructions against
   // ceil(n / 64) of them plus about 70 for the six-step merge, per bidder (5 at n = 32, 10 at 64, 48 at 1024)
-  const int coop_max = SIMAMBA_EMD_SHARED_SCAN ? (14 * n) / (14 * ((n + 63) / 64) + 70) : 0;
+  const int coop_max = (14 * n) / (14 * ((n + 63) / 64) + 70);
   float x = 0.f, y = 0.f, z = 0.f;
   if (active) {
     x = X[3 * i]; y = X[3 * i + 1]; z = X[3 * i + 2];

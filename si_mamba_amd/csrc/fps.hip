@@ -17,7 +17,7 @@
 // holds -- NaN, Inf -- enters no arithmetic), the first pick is start[b] instead of point 0 when given, min(K, len)
 // picks are made and the remaining idx / centers slots are written as -1 / 0, pytorch3d's padding.  The picks are
 // those of the unpadded cloud run alone.  The kRagged = false instantiations are the fixed-length kernels unchanged.
-#include "common.h"
+#include "pointset.h"
 
 namespace simamba {
 
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(const float* __restric
   const int tid = threadIdx.x;
   int len = N, cur = 0;
   if constexpr (kRagged) {
-    if (lengths) len = static_cast<int>(min(max(lengths[blockIdx.x], 1LL), static_cast<long long>(N)));
+    len = clamped_length(lengths, blockIdx.x, N);
     if (start) cur = static_cast<int>(min(max(start[blockIdx.x], 0LL), static_cast<long long>(len - 1)));
   }
   const int picks = kRagged ? min(K, len) : K;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(kFpsWideThreads) void fps_wide_kernel(const float* 
   const int tid = threadIdx.x;
   int len = N, cur = 0;
   if constexpr (kRagged) {
-    if (lengths) len = static_cast<int>(min(max(lengths[blockIdx.x], 1LL), static_cast<long long>(N)));
+    len = clamped_length(lengths, blockIdx.x, N);
     if (start) cur = static_cast<int>(min(max(start[blockIdx.x], 0LL), static_cast<long long>(len - 1)));
   }
   const int picks = kRagged ? min(K, len) : K;

@@ -12,6 +12,7 @@
 // The argmax is np.argmax's: the first maximum, a NaN greater than every number, the first NaN wins; +-inf order as
 // numbers.  No index is derived from a score, and a target label indexes LDS only after the check 0 <= t < C.
 #include "host_common.h"
+#include "pointset.h"
 
 namespace simamba {
 
@@ -20,12 +21,6 @@ constexpr int kPartMaxLabels = 256;     // C
 constexpr int kPartThreads = 256;
 constexpr int kPartWaves = kPartThreads / 64;
 constexpr int kPartSums = 2 * kPartMaxParts + 1;   // inter[16], uni[16], correct
-
-__device__ __forceinline__ int part_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(kPartThreads) void part_seg_eval_kernel(
@@ -44,11 +39,7 @@ __global__ __launch_bounds__(kPartThreads) void part_seg_eval_kernel(
   count = count < 1 ? 1 : (count > cmax ? cmax : count);
   int first = part_first[b];
   first = first < 0 ? 0 : (first > c - count ? c - count : first);
-  int len = n;
-  if (lengths) {
-    const long long l = lengths[b];
-    len = l < 1 ? 1 : (l > n ? n : static_cast<int>(l));
-  }
+  const int len = clamped_length(lengths, b, n);
 
   if (tid < c) sSeen[tid] = 0u;                    // c <= 256 = the workgroup
   __syncthreads();
@@ -94,10 +85,10 @@ __global__ __launch_bounds__(kPartThreads) void part_seg_eval_kernel(
 
 #pragma unroll
   for (int k = 0; k < kPartMaxParts; ++k) {
-    inter[k] = part_wave_sum(inter[k]);
-    uni[k] = part_wave_sum(uni[k]);
+    inter[k] = wave_xor_sum(inter[k]);
+    uni[k] = wave_xor_sum(uni[k]);
   }
-  correct = part_wave_sum(correct);
+  correct = wave_xor_sum(correct);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < kPartMaxParts; ++k) {

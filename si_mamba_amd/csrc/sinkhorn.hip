@@ -21,7 +21,7 @@
 //     same kernel in its `mrow` form leaves |1 - exp((f_i - f_i+) / eps)| per row of (x, y), f+ one further update that
 //     is not stored: the row-marginal error of the plan.
 //   * sinkhorn_final_kernel: one workgroup per pair: the six potential sums and the marginal error, fp64 partial sums in
-//     a fixed order (thread t takes elements t, t + 256, ...; then a tree) as in chamfer_large_reduce_kernel.
+//     a fixed order (thread t takes elements t, t + 256, ...; then block_tree_sum) as in chamfer_large_reduce_kernel.
 //   * sinkhorn_grad_kernel: the same walk with the potentials held fixed, accumulating sum w and sum w (x_i - y_j):
 //       dx_i = ddiv a_i 2 ( sum_j pi_xy(j|i) (x_i - y_j) - sum_k pi_xx(k|i) (x_i - x_k) ),
 //     pi_xy(j|i) = softmax_j((g_xy_j - C_ij) / eps_fin), pi_xx from g_xx; dy_j from f_xy and f_yy.  The two sums are the
@@ -34,6 +34,7 @@
 #include <cmath>
 
 #include "host_common.h"
+#include "pointset.h"
 
 namespace simamba {
 
@@ -64,22 +65,13 @@ struct SkLds {
   float part[5][kSkWaves][kSkWave];   // M, s, ax, ay, az of every wave's share of a row
 };
 
-__device__ __forceinline__ int sk_len(const int* __restrict__ len, long long pr, int padded) {
-  return len ? min(max(len[pr], 1), padded) : padded;
-}
-
 __device__ __forceinline__ float sk_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
 
 // Stage columns [t0, t0 + cnt) of `set` with .w = pot[t] (0 without pot), and pad to a multiple of kSkChunk
 __device__ __forceinline__ void sk_stage(float4* sT, const float* __restrict__ set, const float* __restrict__ pot,
                                          int t0, int cnt) {
-  float* s = reinterpret_cast<float*>(sT);
-  const float* g = set + static_cast<long long>(t0) * 3;
-  for (int e = threadIdx.x; e < cnt * 3; e += kSkThreads) {
-    const int t = e / 3;
-    s[4 * t + (e - 3 * t)] = g[e];
-  }
-  for (int t = threadIdx.x; t < cnt; t += kSkThreads) s[4 * t + 3] = pot ? pot[t0 + t] : 0.f;
+  stage_points<kSkThreads>(sT, set, t0, cnt);
+  for (int t = threadIdx.x; t < cnt; t += kSkThreads) sT[t].w = pot ? pot[t0 + t] : 0.f;
   const int padded = (cnt + kSkChunk - 1) / kSkChunk * kSkChunk;
   for (int t = cnt + threadIdx.x; t < padded; t += kSkThreads) sT[t] = make_float4(0.f, 0.f, 0.f, -INFINITY);
 }
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(kSkThreads) void sinkhorn_diam2_kernel(const float*
                                                                     float* __restrict__ diam2, int n, int m) {
   __shared__ float sLo[3][kSkThreads], sHi[3][kSkThreads];
   const long long pr = blockIdx.x;
-  const int nx = sk_len(xlen, pr, n), ny = sk_len(ylen, pr, m);
+  const int nx = clamped_length(xlen, pr, n), ny = clamped_length(ylen, pr, m);
   const float* xs = x + pr * n * 3;
   const float* ys = y + pr * m * 3;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -207,7 +199,7 @@ __global__ __launch_bounds__(kSkThreads) void sinkhorn_softmin_kernel(SkArgs a, 
   int r = static_cast<int>(blockIdx.x - pr * per);
   const int job = r < job0 ? 0 : (r < job0 + a.bx ? 1 : 2);      // workgroup-uniform
   r -= job == 0 ? 0 : (job == 1 ? job0 : job0 + a.bx);
-  const int nx = sk_len(a.xlen, pr, a.n), ny = sk_len(a.ylen, pr, a.m);
+  const int nx = clamped_length(a.xlen, pr, a.n), ny = clamped_length(a.ylen, pr, a.m);
   const bool rows_x = job == 1 || (job == 0 && half == 0);
   const bool cols_x = job == 1 || (job == 0 && half == 1);
   const int nrp = rows_x ? a.n : a.m, ncp = cols_x ? a.n : a.m;   // padded sizes: the strides
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(kSkThreads) void sinkhorn_final_kernel(SkArgs a, co
                                                                     float* __restrict__ merr) {
   __shared__ double sS[7][kSkThreads];
   const long long pr = blockIdx.x;
-  const int nx = sk_len(a.xlen, pr, a.n), ny = sk_len(a.ylen, pr, a.m);
+  const int nx = clamped_length(a.xlen, pr, a.n), ny = clamped_length(a.ylen, pr, a.m);
   const float* vx[4] = {a.f_xy + pr * a.n, a.debias ? a.f_xx + pr * a.n : nullptr,
                         a.debias ? a.g_xx + pr * a.n : nullptr, mrow ? mrow + pr * a.n : nullptr};
   const float* vy[3] = {a.g_xy + pr * a.m, a.debias ? a.f_yy + pr * a.m : nullptr,
@@ -258,14 +250,7 @@ __global__ __launch_bounds__(kSkThreads) void sinkhorn_final_kernel(SkArgs a, co
       for (int j = threadIdx.x; j < ny; j += kSkThreads) t[4 + v] += static_cast<double>(vy[v][j]);
 #pragma unroll
   for (int v = 0; v < 7; ++v) sS[v][threadIdx.x] = t[v];
-  __syncthreads();
-  for (int w = kSkThreads / 2; w >= 1; w >>= 1) {
-    if (threadIdx.x < w) {
-#pragma unroll
-      for (int v = 0; v < 7; ++v) sS[v][threadIdx.x] += sS[v][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+  block_tree_sum(sS);
   if (threadIdx.x == 0) {
     // x sums: 0 f_xy, 1 f_xx, 2 g_xx, 3 mrow ; y sums: 4 g_xy, 5 f_yy, 6 g_yy
     const double xy = sS[0][0] / nx + sS[4][0] / ny;
@@ -288,7 +273,7 @@ __global__ __launch_bounds__(kSkThreads) void sinkhorn_grad_kernel(SkArgs a, con
   const long long pr = blockIdx.x / (a.bx + a.by);
   const int r = static_cast<int>(blockIdx.x - pr * (a.bx + a.by));
   const bool forx = r < a.bx;
-  const int nx = sk_len(a.xlen, pr, a.n), ny = sk_len(a.ylen, pr, a.m);
+  const int nx = clamped_length(a.xlen, pr, a.n), ny = clamped_length(a.ylen, pr, a.m);
   const int nsp = forx ? a.n : a.m, nop = forx ? a.m : a.n;
   const int ns = forx ? nx : ny, no = forx ? ny : nx;
   const float* self = (forx ? a.x : a.y) + pr * nsp * 3;

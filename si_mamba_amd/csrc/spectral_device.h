@@ -80,12 +80,6 @@ __device__ __forceinline__ void householder_params(float nrm2, float x0, float* 
 }
 
 // ---- fp64 stages on the tridiagonal T = (d, e) --------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // 1/x to ~1 ulp: hardware v_rcp_f64 seed + one Newton step (the IEEE division sequence is ~30 dependent
 // instructions; the recurrences below are pure latency chains of divisions)
 __device__ __forceinline__ double rcp_f64(double x) {
@@ -234,12 +228,12 @@ __device__ __forceinline__ void gram_schmidt_wave0(double* sZ, int ntot, int G, 
       const double* zt = sZ + t * kPitch;
       double dot = 0.0;
       for (int i = tid; i < G; i += 64) dot += zs[i] * zt[i];
-      dot = wave_sum_f64(dot);
+      dot = wave_xor_sum(dot);
       for (int i = tid; i < G; i += 64) zs[i] -= dot * zt[i];
     }
     double nr = 0.0;
     for (int i = tid; i < G; i += 64) nr += zs[i] * zs[i];
-    nr = 1.0 / sqrt(wave_sum_f64(nr));
+    nr = 1.0 / sqrt(wave_xor_sum(nr));
     for (int i = tid; i < G; i += 64) zs[i] *= nr;
   }
 }

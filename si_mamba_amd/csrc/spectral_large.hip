@@ -117,12 +117,6 @@ constexpr int kLgBtPer = kSpecMaxGLarge / 64;      // reflector entries per lane
 constexpr size_t kLgDynLds = sizeof(double) * (kTdMaxSel + 4 * kLgVecBatch) * kSpecMaxGLarge +
                              kLgVecBatch * kSpecMaxGLarge;
 
-__device__ __forceinline__ float lg_wave_sum_f32(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) double dsm[];
   constexpr int NG = kSpecMaxGLarge;
@@ -191,7 +185,7 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
       }
       if (t >= 1) sq = s * s;
     }
-    sq = lg_wave_sum_f32(sq);
+    sq = wave_xor_sum(sq);
     if (lane == 0) sPart[wave] = sq;
     if (tid == 0) sD[k] = s;
     if (tid == 1) sX0 = s;
@@ -317,7 +311,7 @@ __global__ __launch_bounds__(kLgThreads) void laplacian_large_kernel(EigArgs p, 
         const int i = lane + 64 * q;
         if (i < m) dot += static_cast<double>(vk[q]) * z[k + 1 + i];
       }
-      dot = wave_sum_f64(dot) * tau;
+      dot = wave_xor_sum(dot) * tau;
 #pragma unroll
       for (int q = 0; q < kLgBtPer; ++q) {
         const int i = lane + 64 * q;

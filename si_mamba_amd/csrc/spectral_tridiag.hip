@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kTdThreads) void laplacian_tridiag_kernel(EigArgs p
         const double vi = (i == 0) ? 1.0 : static_cast<double>(S[(k + 1 + i) * LD + k]);
         dot += vi * z[k + 1 + i];
       }
-      dot = wave_sum_f64(dot) * tau;
+      dot = wave_xor_sum(dot) * tau;
       for (int i = lane; i < m; i += 64) {
         const double vi = (i == 0) ? 1.0 : static_cast<double>(S[(k + 1 + i) * LD + k]);
         z[k + 1 + i] -= dot * vi;

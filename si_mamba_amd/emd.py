@@ -9,6 +9,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._pointsets import as_pairs
 
 EMD_MAX_POINTS = 1024
 
@@ -76,9 +77,7 @@ def earth_movers_distance(x, y, *, eps=None, max_rounds=None, return_assignment=
     if x.shape != y.shape or x.dim() not in (2, 3) or x.shape[-1] != 3:
         raise ValueError(f"earth_movers_distance: x and y must both be (P, n, 3) or (n, 3) with the same n, got "
                          f"{tuple(x.shape)} and {tuple(y.shape)}")
-    single = x.dim() == 2
-    if single:
-        x, y = x.unsqueeze(0), y.unsqueeze(0)
+    x, y, single = as_pairs(x, y)
     pairs, n, _ = x.shape
     if not 1 <= n <= EMD_MAX_POINTS or pairs < 1:
         raise ValueError(f"earth_movers_distance: 1 <= n <= {EMD_MAX_POINTS} points per set and at least one pair, "

@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._pointsets import as_pairs, lengths_i32
 
 SINKHORN_MAX_POINTS = 8192
 SINKHORN_MAX_STEPS = 4096
@@ -23,7 +24,7 @@ def scaling_steps(eps_rel: float) -> int:
 
 
 def _lengths(lengths, device):
-    return None if lengths is None else lengths.to(device=device, dtype=torch.int32).contiguous()
+    return lengths_i32(None if lengths is None else lengths.to(device))
 
 
 class SinkhornFn(torch.autograd.Function):
@@ -100,9 +101,7 @@ def sinkhorn_divergence(x, y, *, x_lengths=None, y_lengths=None, eps_rel=2.0 ** 
             (x.dim() == 3 and x.shape[0] != y.shape[0]):
         raise ValueError(f"sinkhorn_divergence: x and y must be (P, n, 3) and (P, m, 3), or (n, 3) and (m, 3), got "
                          f"{tuple(x.shape)} and {tuple(y.shape)}")
-    single = x.dim() == 2
-    if single:
-        x, y = x.unsqueeze(0), y.unsqueeze(0)
+    x, y, single = as_pairs(x, y)
     pairs, n, m = x.shape[0], x.shape[1], y.shape[1]
     if not (1 <= n <= SINKHORN_MAX_POINTS and 1 <= m <= SINKHORN_MAX_POINTS) or pairs < 1:
         raise ValueError(f"sinkhorn_divergence: 1 <= n, m <= {SINKHORN_MAX_POINTS} points per set and at least one "

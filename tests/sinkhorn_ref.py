@@ -128,8 +128,10 @@ def gaussian_sets(pairs, n, m, seed):
 
 
 # ---- the cases the GPU tests walk (pairs, n, m): one lane, less than one wave, one off the wave multiple, one off the
-# row block and tile, several tiles with a remainder in both roles, and the reconstruct() shape
-SIZES = ((5, 1, 1), (3, 2, 3), (4, 63, 65), (2, 256, 257), (2, 300, 1000), (1, 1000, 300), (1, 2048, 1024))
+# row block and tile, several tiles with a remainder in both roles, the reconstruct() shape, and one full tile plus one
+# column (1025: the second tile is one point and seven columns of padding, on the first step without a potential)
+SIZES = ((5, 1, 1), (3, 2, 3), (4, 63, 65), (2, 256, 257), (2, 300, 1000), (1, 1000, 300), (1, 2048, 1024),
+         (2, 9, 1025))
 SETTINGS = ((2.0 ** -6, 16), (2.0 ** -9, 4))
 LIMIT_CASE = (1, 8192, 8192, 2.0 ** -3, 2)
 

@@ -27,12 +27,13 @@ SHAPES = [(3, 65, 64),        # one point over the small kernels' limit, on one 
           (2, 1000, 1300),    # neither size a multiple of any tile
           (1, 8192, 4099),    # the cap, and an odd size
           (300, 96, 80),      # many pairs, for the grid mapping
-          (2, 1, 257)]        # a single-point set
+          (2, 1, 257),        # a single-point set
+          (2, 9, 1025)]       # one full tile of targets plus one point, staged by workgroups with 9 queries
 # (2, 1, 257) has one query whose reverse-match gradient sums 257 displacements (cancellation); its transpose keeps the
 # single-point case with at most one reverse match per query
-GRAD_SHAPES = SHAPES[:4] + [(2, 257, 1)]
+GRAD_SHAPES = SHAPES[:4] + [(2, 257, 1), (2, 9, 1025)]
 SEED = {(3, 65, 64): 1, (2, 1000, 1300): 2, (1, 8192, 4099): 3, (300, 96, 80): 4, (2, 1, 257): 5, (2, 257, 1): 6,
-        (5, 32, 32): 7, (5, 64, 64): 8, (2, 65, 32): 9}
+        (5, 32, 32): 7, (5, 64, 64): 8, (2, 65, 32): 9, (2, 9, 1025): 10}
 BIG = 1 << 30
 
 

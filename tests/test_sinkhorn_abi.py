@@ -118,3 +118,18 @@ def test_python_route_checks_its_arguments_first():
         with pytest.raises(ValueError):
             sinkhorn_divergence(x, y, **kw)
     assert [scaling_steps(e) for e in (1.0, 0.5, 0.3, 2.0 ** -6, 2.0 ** -9, 1e-45)] == [0, 1, 2, 6, 9, 149]
+
+
+def test_lengths_reach_the_kernels_as_int32_without_wrapping():
+    """2^32 + 5 must not become 5, a length the kernel would take as valid: it stays at least every padded size."""
+    from si_mamba_amd import sinkhorn
+    from si_mamba_amd._pointsets import lengths_i32
+    t = torch.tensor([2 ** 32 + 5, -7, 3], dtype=torch.int64)
+    want = torch.tensor([1 << 20, -1, 3], dtype=torch.int32)
+    for got in (lengths_i32(t), sinkhorn._lengths(t, torch.device("cpu"))):
+        assert got.dtype == torch.int32 and got.is_contiguous() and torch.equal(got, want)
+    assert lengths_i32(None) is None and sinkhorn._lengths(None, torch.device("cpu")) is None
+    # every integer dtype is taken, as before the clamp: its bounds must not be converted to the narrow type
+    for dtype in (torch.int8, torch.uint8, torch.int16, torch.int32):
+        got = sinkhorn._lengths(torch.tensor([3, 100, 1], dtype=dtype), torch.device("cpu"))
+        assert got.dtype == torch.int32 and torch.equal(got, torch.tensor([3, 100, 1], dtype=torch.int32))

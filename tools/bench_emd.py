@@ -8,10 +8,7 @@ those of fresh tools/bench_mae.py processes, ``--runs`` per variant, the variant
 machine in the same minutes.  ``--parent DIR`` (a built checkout of the parent commit) adds that tree's cdl2 step to the
 alternation: no code on the cdl2 path changes, so the two must agree within their own spread.
 
-``--alt-lib PATH`` (tools/build_alt.sh noshared emd.hip "-DSIMAMBA_EMD_SHARED_SCAN=0") adds the forward of a library
-built without the shared object scan, same inputs, same windows: what spreading one bidder's scan over the wave buys.
-
-    python tools/bench_emd.py [--parent DIR] [--alt-lib PATH] [--runs 3] [--out profiles/emd.json]
+    python tools/bench_emd.py [--parent DIR] [--runs 3] [--out profiles/emd.json]
 """
 import argparse
 import json
@@ -52,25 +49,7 @@ def alternate(ops, target_ms=200.0, windows=5):
     return {name: [round(sorted(v)[len(v) // 2], 4), round(min(v), 4), round(max(v), 4)] for name, v in ts.items()}
 
 
-def raw_forward(lib_path, x, y, max_rounds):
-    """The bare C call of another build of the library, outputs allocated once -> (call, outputs)."""
-    import ctypes
-    from si_mamba_amd import _lib
-    fn = ctypes.CDLL(lib_path).simamba_emd_fwd
-    fn.restype, fn.argtypes = _lib.SIGNATURES["simamba_emd_fwd"]
-    pairs, n, _ = x.shape
-    out = [torch.empty(pairs, n, device=x.device, dtype=torch.int32), torch.empty(pairs, device=x.device),
-           torch.empty(pairs, device=x.device, dtype=torch.int32),
-           torch.empty(pairs, device=x.device, dtype=torch.uint8)]
-
-    def call():
-        rc = fn(x.data_ptr(), y.data_ptr(), *[t.data_ptr() for t in out], pairs, n, 0.0, max_rounds,
-                _lib.stream_ptr(x.device))
-        assert rc == 0, rc
-    return call, out
-
-
-def kernels(alt_lib=None):
+def kernels():
     from si_mamba_amd import earth_movers_distance
     from si_mamba_amd.emd import default_max_rounds
     from si_mamba_amd.mae import chamfer_distance
@@ -89,13 +68,8 @@ def kernels(alt_lib=None):
         if n <= 64:
             ops["chamfer_patch_fwd"] = lambda: chamfer_distance(x, y)
             ops["chamfer_patch_fwd_bwd"] = lambda: fwd_bwd(chamfer_distance)
-        if alt_lib:
-            ops["emd_fwd_no_shared_scan"], alt_out = raw_forward(alt_lib, x, y, default_max_rounds(n))
         row = dict(shape=[pairs, n], ms_median_min_max=alternate(ops))
         dist, assign, rounds, conv = earth_movers_distance(x, y, return_assignment=True)
-        if alt_lib:
-            row["no_shared_scan_same_bits"] = all(torch.equal(a, b) for a, b in
-                                                  zip(alt_out, (assign, dist, rounds, conv)))
         row.update(rounds_mean=round(float(rounds.float().mean()), 1), rounds_max=int(rounds.max()),
                    max_rounds=default_max_rounds(n), converged_share=float(conv.float().mean()))
         rows.append(row)
@@ -123,7 +97,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
-    ap.add_argument("--alt-lib", default=None, help="a library built with -DSIMAMBA_EMD_SHARED_SCAN=0")
     ap.add_argument("--runs", type=int, default=3, help="bench_mae.py processes per variant")
     ap.add_argument("--no-steps", action="store_true", help="kernel times only")
     args = ap.parse_args()
@@ -135,7 +108,7 @@ def main():
                                 "MI355X; call times (events around back-to-back calls, 5 windows of ~0.2 s per "
                                 "operation, the operations alternating): [median, min, max] ms; MAE step (B = 64, bf16, "
                                 "fwd + bwd + AdamW) per fresh process, variants alternating",
-                           device=torch.cuda.get_device_name(0), kernels=kernels(args.alt_lib), mae_step_ms=step_ms))
+                           device=torch.cuda.get_device_name(0), kernels=kernels(), mae_step_ms=step_ms))
     print(line)
     if args.out:
         with open(args.out, "w") as fh:
