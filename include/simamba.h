@@ -28,6 +28,8 @@
  *   simamba_farthest_point_sample    pytorch3d.ops.sample_farthest_points, models/point_mamba.py:93.
  *   simamba_augment_points           tools/runner_finetune.py:191-194 (fps_idx[:, choice], gather_operation) and the
  *                                    transforms of datasets/data_transforms.py, one launch per batch.
+ *   simamba_svm_ovo_fit/_vote        sklearn.svm.SVC(C=0.01, kernel='linear') (libsvm) of
+ *                                    tools/runner_pretrain.py:66-77.
  *
  * Conventions
  *   - Plain pointers and sizes only.  All pointers are DEVICE pointers unless noted.
@@ -42,7 +44,8 @@
  *     (batch, state, time) strides (e.g. straight out of the (batch, seqlen, R+2N) x_proj output).
  *     A stride of 0 means "contiguous default".
  *   - io_dtype: SIMAMBA_F32 or SIMAMBA_BF16 for activation-sized tensors; all state,
- *     accumulation and parameter gradients are fp32.
+ *     accumulation and parameter gradients are fp32.  The one exception is the simamba_svm_ovo_* family, which is
+ *     float64 throughout (stated there).
  */
 #ifndef SIMAMBA_H_
 #define SIMAMBA_H_
@@ -710,6 +713,55 @@ int simamba_part_seg_eval(const void* scores, const long long* target, const int
                           const long long* lengths, long long* pred, int* inter, int* uni, double* shape_iou,
                           int* correct, long long* seen_class, long long* correct_class, long long batch, int n, int c,
                           int io_dtype, void* stream);
+
+/*
+ * Linear one-vs-one C-SVC (csrc/svm.hip): the reference's per-epoch pre-training score, tools/runner_pretrain.py:66-77,
+ * scikit-learn's SVC(C=0.01, kernel='linear'), i.e. libsvm.  THIS FAMILY IS FLOAT64 -- the one exception to "all state
+ * fp32" above: the solver's gradient sums are of size n_SV * C * |K| against a tolerance of 1e-3.
+ *
+ * simamba_svm_ovo_fit: one workgroup per class pair (a, b), a < b, pairs in libsvm's order (0,1), (0,2), ...
+ * (nc-2, nc-1), P = nc (nc - 1) / 2 of them.  A pair's problem is class a's samples (y = +1) followed by class b's
+ * (y = -1); it solves  min 1/2 a'Qa - e'a,  0 <= a <= C,  y'a = 0,  Q = yy' o gram  by SMO with libsvm's second-order
+ * working-set rule (curvature floor 1e-12), libsvm's clipped update, libsvm's stopping rule m(a) - M(a) < tol and
+ * libsvm's rho (the mean of yG over the free a; with none free, the midpoint of the two bounds).
+ *   gram        : (n, n) fp64, row-major, the training Gram matrix x x'.      2 <= n <= 16384.
+ *   x           : (n, d) fp32 feature rows (read once per pair, for w).       1 <= d <= 4096.
+ *   order       : (n) int32, device: the sample indices grouped by class, input order kept inside a class.  Entries are
+ *                 clamped into [0, n) by the kernel.
+ *   class_start : (nc + 1) int32, a HOST array read during the call: class k is order[class_start[k] ..
+ *                 class_start[k + 1]).  class_start[0] == 0, class_start[nc] == n, no class empty, and no two classes
+ *                 together above 4096 samples (a pair lives in LDS); 2 <= nc <= 64.
+ *   alpha       : (nc - 1) * n fp64: the pairs' alpha back to back in pair order, each in the pair's sample order.  The
+ *                 kernel derives every pair's offset from class_start itself; 0 <= alpha <= C holds exactly.
+ *   w           : (P, d) fp64 = sum_k alpha_k y_k x_k, accumulated in fp64 in sample order.
+ *   rho         : (P) fp64; the pair's decision value of a row z is w . z - rho, positive for class a.
+ *   n_iter      : (P) int32, updates made.
+ *   converged   : (P) uint8, 1 when the stopping rule was met; 0: the cap was reached first (alpha is still feasible),
+ *                 or gram holds a NaN.
+ *   c_tol       : a HOST array of two fp64 read during the call, {C, tol}, both > 0 (the ABI passes no double by
+ *                 value).
+ *   max_iter >= 1, max_iter_per_sample >= 0: a pair of n_p samples makes at most
+ *                 max_iter + max_iter_per_sample * n_p updates (capped at 2^31 - 1); every loop of the kernel is bounded
+ *                 by it, whatever the input, and all waves leave in the same iteration.
+ * No atomics, ties to the lower position, every reduction in a fixed order: the same bits every call.
+ * Checks in the order shape (SIMAMBA_E_SHAPE: nc, n, d, the iteration caps, then -- each when its host array is not
+ * NULL -- C or tol <= 0 or NaN, and class_start's ends, an empty class, a pair above 4096), null pointers (all
+ * required); all before any launch.
+ *
+ * simamba_svm_ovo_vote: libsvm's svm_predict_values on decision values, one wave per row.
+ *   dec     : (m, P) fp64.  dec > 0 is a vote for a, anything else (exactly 0 and NaN too) for b; the class with the
+ *             most votes wins, the lowest class index on a tie.                 1 <= m < 2^31 ; 2 <= nc <= 64.
+ *   pred    : (m) int32, the winning class index.
+ *   labels  : (m) int64 class indices, or NULL; with labels, the rows with pred == labels are ADDED to
+ *   matches : (1) int64 (the caller zeroes it; one 64-bit integer atomic per matching row).  Required with labels.
+ * Checks: SIMAMBA_E_SHAPE (nc, m), then null pointers.  Still ABI version 9: symbols added, none changed.
+ */
+int simamba_svm_ovo_fit(const double* gram, const float* x, const int* order, const int* class_start,
+                        const double* c_tol, double* alpha, double* w, double* rho, int* n_iter,
+                        unsigned char* converged, int n, int d, int nc, int max_iter, int max_iter_per_sample,
+                        void* stream);
+int simamba_svm_ovo_vote(const double* dec, const long long* labels, int* pred, long long* matches, long long m, int nc,
+                         void* stream);
 
 /*
  * Sampling and augmentation of a batch of clouds in front of a step (csrc/augment.hip; the reference's

@@ -13,6 +13,7 @@ from .shim import install_shim
 from .emd import earth_movers_distance
 from .sinkhorn import sinkhorn_divergence
 from .seg_metrics import SHAPENETPART, PartSegMetrics, PartTable, part_seg_eval
+from .svm import OvOLinearSVC, evaluate_svm
 from . import transforms
 from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRandomInputDropout, PointcloudRotate,
                          PointcloudScale, PointcloudScaleAndTranslate, PointcloudTranslate, RandomHorizontalFlip,
@@ -25,4 +26,4 @@ __all__ = ["transforms", "AugmentState", "Compose", "PointcloudJitter", "Pointcl
            "RandomHorizontalFlip", "sample_and_augment", "vote_logits",
 "SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
-           "set_deterministic", "earth_movers_distance", "sinkhorn_divergence"]
+           "set_deterministic", "earth_movers_distance", "sinkhorn_divergence", "OvOLinearSVC", "evaluate_svm"]

@@ -141,6 +141,8 @@ SIGNATURES = {
     "simamba_sinkhorn_fwd": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P]),
     "simamba_sinkhorn_bwd": (c_int, [_P] * 11 + [_LL, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
     "simamba_part_seg_eval": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_int, _P]),
+    "simamba_svm_ovo_fit": (c_int, [_P] * 10 + [c_int, c_int, c_int, c_int, c_int, _P]),
+    "simamba_svm_ovo_vote": (c_int, [_P, _P, _P, _P, _LL, c_int, _P]),
     "simamba_augment_points": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_augment_params": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _LL, c_int, _P]),
     "simamba_philox4x32_10": (c_int, [_LL, c_uint, c_uint, c_uint, c_uint, _P]),
