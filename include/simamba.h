@@ -28,6 +28,8 @@
  *   simamba_farthest_point_sample    pytorch3d.ops.sample_farthest_points, models/point_mamba.py:93.
  *   simamba_augment_points           tools/runner_finetune.py:191-194 (fps_idx[:, choice], gather_operation) and the
  *                                    transforms of datasets/data_transforms.py, one launch per batch.
+ *   simamba_dataset_fetch            the torch DataLoader of tools/builder.py over the datasets/ classes and
+ *                                    part_segmentation/dataset.py: shuffle, per-item sampling, pc_norm, collate.
  *   simamba_svm_ovo_fit/_vote        sklearn.svm.SVC(C=0.01, kernel='linear') (libsvm) of
  *                                    tools/runner_pretrain.py:66-77.
  *
@@ -836,6 +838,68 @@ int simamba_augment_params(const long long* lengths, const int* ops, const float
                            const long long* state, float* cloud_params, float* noise, unsigned char* keep, long long B,
                            int K, void* stream);
 int simamba_philox4x32_10(long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned* out);
+
+/*
+ * A batch out of a dataset resident on the device (csrc/dataset.hip; the reference's torch DataLoader over
+ * datasets/ShapeNet55Dataset.py, ScanObjectNNDataset.py, ModelNetDataset.py and part_segmentation/dataset.py): one
+ * launch, one workgroup per slot of the batch, followed by a one-lane kernel that adds 1 to the step.
+ * The store:
+ *   points       : (T, 3) fp32, the clouds back to back; `total` = T.
+ *   offsets      : (S + 1) int64, cloud s is rows [offsets[s], offsets[s + 1]); or NULL: cloud s is rows
+ *                  [s stride, (s + 1) stride), S stride <= T.  The kernel forces every range inside [0, T).
+ *   labels       : (S) int64 or NULL.            point_labels : (T) int32 or NULL.
+ *   state        : (2) int64 [seed, step], the layout of simamba_augment_points.  Read by the kernel; step + 1 is written
+ *                  behind it in stream order.  Nothing is read on the host, so the call can be captured.
+ * Which cloud goes into slot b < B:
+ *   epoch = step / steps_per_epoch, pos = step % steps_per_epoch (both unsigned), p = (pos B + b) world + rank.
+ *   p >= S: an empty slot (the last partial batch): index -1, label -1, length 0, rows 0; nothing is looked up.
+ *   SIMAMBA_DS_SEQUENTIAL: s = p.     SIMAMBA_DS_SHUFFLE: s = perm(S, seed, stream(SHUFFLE, epoch, 0), p).
+ * Which rows: the candidates are the cloud's first c = min(n_s, first) rows (first == 0: c = n_s).
+ *   SIMAMBA_DS_FIRST   : row i = i, i < len = min(K, c).
+ *   SIMAMBA_DS_PERMUTE : row i = perm(c, seed, stream(ROWS, epoch, p), i), i < len = min(K, c): without replacement.
+ *   SIMAMBA_DS_CHOICE  : row i = (uint64(w_i) c) >> 32, i < len = K: with replacement;
+ *                        w_i = word 0 of philox4x32_10(key, c0 = i, c1 = 0x80000000, c2, c3 of stream(CHOICE, epoch, p)).
+ *   An empty cloud (c == 0) gives len = 0 in every mode.  Rows at and behind len are written as 0, point labels as -1.
+ * Normalisation of the selected rows (datasets/ShapeNet55Dataset.py:47-53, pc_norm):
+ *   SIMAMBA_DS_NONE, or SIMAMBA_DS_UNIT_SPHERE: d = row - row 0; mean_a = (sum of the len d) / len; r = d - mean;
+ *   m = sqrt(max_i((r_x r_x + r_y r_y) + r_z r_z)); out = r / m.  fp32, one rounding per operation; the sum runs per lane
+ *   over its rows in ascending order, over the wave by the butterfly 32 .. 1, over the waves in ascending order.  A NaN
+ *   is passed over by the maximum.  Taking row 0 off first changes nothing in exact arithmetic; in fp32 it makes rows
+ *   that all coincide exact zeros: then m == 0 (the reference divides by zero) and the slot is written as 0.
+ * Keyed choices: perm is the bijection of csrc/keyed_perm.h (a four-round balanced Feistel network over Philox4x32-10
+ * with cycle walking, stated there in full), key = (seed & 0xffffffff, seed >> 32), and
+ *   stream(purpose, epoch, p) = purpose << 60 | (epoch mod 2^29) << 31 | p        (c2 = its low, c3 = its high word)
+ *   purpose: SIMAMBA_DS_STREAM_SHUFFLE 1, _ROWS 2, _CHOICE 3.  Every Philox block drawn here has bit 31 of c1 set, which
+ *   no block of simamba_augment_points has.
+ *   So a slot's content depends only on (seed, epoch, p), the store and the modes: not on B, not on the other slots.
+ * Outputs, every element written on every call:
+ *   out (B, K, 3) fp32 ; index_out (B) int64 ; lengths_out (B) int32 ; label_out (B) int64 or NULL (-1 without labels) ;
+ *   point_label_out (B, K) int32 or NULL (-1 without point_labels).
+ * Checks in the order shape (SIMAMBA_E_SHAPE: 1 <= S < 2^31, 1 <= B < 2^31, 1 <= K <= 8192, 0 <= rank < world,
+ * steps_per_epoch >= 1, first >= 0, total >= 0, without offsets 1 <= stride and S stride <= total,
+ * steps_per_epoch B world <= 2^62), null pointers (points, state, out, index_out, lengths_out), modes
+ * (SIMAMBA_E_VARIANT); all before any launch.
+ *
+ * simamba_keyed_perm: HOST only, compiled from the header the kernel uses: out[j] = perm(n, seed, stream = tweak,
+ * first + j) for j < count into the host array out; 1 <= n < 2^31, first + count <= n.
+ * Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_DS_SEQUENTIAL     0
+#define SIMAMBA_DS_SHUFFLE        1
+#define SIMAMBA_DS_FIRST          0
+#define SIMAMBA_DS_PERMUTE        1
+#define SIMAMBA_DS_CHOICE         2
+#define SIMAMBA_DS_NONE           0
+#define SIMAMBA_DS_UNIT_SPHERE    1
+#define SIMAMBA_DS_STREAM_SHUFFLE 1
+#define SIMAMBA_DS_STREAM_ROWS    2
+#define SIMAMBA_DS_STREAM_CHOICE  3
+int simamba_dataset_fetch(const float* points, const long long* offsets, const long long* labels,
+                          const int* point_labels, long long* state, float* out, long long* label_out,
+                          int* point_label_out, long long* index_out, int* lengths_out, long long total, long long S,
+                          long long stride, long long B, int K, int first, long long steps_per_epoch, int rank,
+                          int world, int order, int rows, int norm, void* stream);
+int simamba_keyed_perm(long long seed, long long tweak, long long n, long long first, long long count, long long* out);
 
 /*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,

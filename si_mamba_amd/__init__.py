@@ -19,9 +19,11 @@ from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRand
                          PointcloudScale, PointcloudScaleAndTranslate, PointcloudTranslate, RandomHorizontalFlip,
                          sample_and_augment)
 from .vote import vote_logits
+from . import data
+from .data import Batch, DeviceDataset, DeviceLoader
 from ._lib import deterministic, deterministic_enabled, set_deterministic
 
-__all__ = ["transforms", "AugmentState", "Compose", "PointcloudJitter", "PointcloudRandomInputDropout",
+__all__ = ["data", "Batch", "DeviceDataset", "DeviceLoader", "transforms", "AugmentState", "Compose", "PointcloudJitter", "PointcloudRandomInputDropout",
            "PointcloudRotate", "PointcloudScale", "PointcloudScaleAndTranslate", "PointcloudTranslate",
            "RandomHorizontalFlip", "sample_and_augment", "vote_logits",
 "SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",

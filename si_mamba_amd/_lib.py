@@ -41,6 +41,12 @@ AUG_ROTATE, AUG_SCALE, AUG_TRANSLATE, AUG_SCALE_TRANSLATE, AUG_JITTER, AUG_DROPO
 AUG_MAX_OPS = 8
 AUG_CLOUD_PARAMS = 8
 AUG_MAX_POINTS = 8192
+# modes of simamba_dataset_fetch (data.py) and the purposes of its keyed streams
+DS_SEQUENTIAL, DS_SHUFFLE = 0, 1
+DS_FIRST, DS_PERMUTE, DS_CHOICE = 0, 1, 2
+DS_NONE, DS_UNIT_SPHERE = 0, 1
+DS_STREAM_SHUFFLE, DS_STREAM_ROWS, DS_STREAM_CHOICE = 1, 2, 3
+DS_MAX_POINTS = 8192
 
 # name -> (restype, argtypes); mirrors include/simamba.h one to one
 _P = c_void_p
@@ -146,6 +152,9 @@ SIGNATURES = {
     "simamba_augment_points": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_augment_params": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _LL, c_int, _P]),
     "simamba_philox4x32_10": (c_int, [_LL, c_uint, c_uint, c_uint, c_uint, _P]),
+    "simamba_dataset_fetch": (c_int, [_P] * 10 + [_LL, _LL, _LL, _LL, c_int, c_int, _LL, c_int, c_int, c_int, c_int,
+                                      c_int, _P]),
+    "simamba_keyed_perm": (c_int, [_LL, _LL, _LL, _LL, _LL, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),
