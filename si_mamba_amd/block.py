@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import math
 from functools import partial
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -27,6 +27,7 @@ from .cross_merge import cross_merge, cross_merge_composed, cross_merge_maps
 from .mamba_simple import Mamba
 from .out_norm import out_proj_add_ln_fn, out_proj_add_ln_ok
 from .rms_norm import RMSNorm
+from .spectral import argsort_rows, take
 
 _KERNEL_NORMS = (nn.LayerNorm, RMSNorm)      # the norms the add + norm kernels compute
 
@@ -83,7 +84,7 @@ class Block(nn.Module):
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
 
     def forward(self, hidden_states: Tensor, residual: Optional[Tensor] = None, inference_params=None, A=None, *,
-                rowscale=None, compact=None):
+                rowscale=None, draw=True, compact=None):
         """hidden_states = Mixer(LN(residual)); returns (hidden_states, residual).  ``A`` (optional, specific to this
         implementation): the mixer's -exp(A_log) when the caller has already formed it (MixerModel does, for all
         layers in one launch); handed on as an argument, never parked on the module.
@@ -91,12 +92,14 @@ class Block(nn.Module):
         Add (+ DropPath) + LayerNorm (or RMSNorm) run as one HIP pass each way (add_norm.py) for such blocks on the
         GPU; the composed torch form below is the reference's own and serves any other norm / device.
 
-        ``rowscale`` (B,), ``compact`` (both specific to this implementation, MixerModel's): the DropPath factors when
-        the caller has already drawn them, and add_layer_norm_fn's slot-map arguments when ``hidden_states`` holds only
-        some samples of the batch (None: none) and / or the mixer is to run only on some; the hidden_states returned
-        are then compact too, None when the mixer has no sample to run on."""
-        if compact is not None:
-            hidden_states, residual = _fused_norm(hidden_states, residual, self.norm, rowscale=rowscale, **compact)
+        ``rowscale`` (B,), ``draw``, ``compact`` (specific to this implementation, MixerModel's): the DropPath factors
+        when the caller has already drawn them; ``draw=False`` when it drew the whole forward's ahead (a DropPlan): the
+        block then draws none even where ``rowscale`` is None (block 0), and ``compact`` may hold add_layer_norm_fn's
+        slot-map arguments for a ``hidden_states`` of only some samples and / or a mixer that is to run only on some;
+        the hidden_states returned are then compact too, None when the mixer has no sample to run on."""
+        if not draw:
+            hidden_states, residual = _fused_norm(hidden_states, residual, self.norm, rowscale=rowscale,
+                                                  **(compact or {}))
             if hidden_states.shape[0] == 0:
                 return None, residual
         elif hidden_states.is_cuda and type(self.norm) in _KERNEL_NORMS and hidden_states.dim() == 3:
@@ -185,6 +188,18 @@ class DropPlan:
     __slots__ = ("masks", "lead", "batch", "event", "host", "sizes", "maps", "sel")
 
 
+class StackRoute(NamedTuple):
+    """Which way one forward of a MixerModel goes (MixerModel.route)."""
+    first_on_tokens: bool       # block 0 runs on the G distinct tokens (_first_block_on_distinct_tokens)
+    stack: str                  # "chain" (fused bf16, _chain), "compact" (a DropPlan, _compact_stack) or "layers"
+
+    @property
+    def lead(self):
+        """Does a DropPlan of this route open with block 0's draw?  Where block 0 goes through Block.forward it draws
+        a rowscale it never applies; on the distinct tokens it draws none."""
+        return not self.first_on_tokens
+
+
 class MixerModel(nn.Module):
     def __init__(self, d_model: int, n_layer: int, ssm_cfg=None, norm_epsilon: float = 1e-5,
                  rms_norm: bool = False, initializer_cfg=None, fused_add_norm=False,
@@ -219,10 +234,22 @@ class MixerModel(nn.Module):
     # kept samples only: block j - 1's add + norm writes `normed` compacted, block j's reads `hidden` compacted
     # (add_norm.py's slot maps); the residual stream keeps the whole batch.
 
+    def route(self, like, seqlen=None, inference_params=None):
+        """The StackRoute of a forward, from shapes, dtypes (autocast's), modes and the configuration alone, so that it
+        can be asked before the tokens exist; the one place the three predicates below are asked, each once.
+        ``like``: what the stack is handed, or a stand-in of its shape and device; ``seqlen``: the length of the
+        balanced ``token_index`` that comes with (B, G, C) distinct tokens, None when ``like`` is the sequence."""
+        plain = inference_params is None and len(self.layers) > 0
+        first = plain and seqlen is not None and self._first_block_applies(like, seqlen)
+        if plain and self._chain_ok(like):
+            return StackRoute(first, "chain")
+        return StackRoute(first, "compact" if self._compact_ok(like, inference_params) else "layers")
+
     def _compact_ok(self, x, inference_params=None):
-        """Does a forward on ``x`` take the compact route?  Training with DropPath in every block, the layer-by-layer
-        route of plain blocks on the add + norm kernels, nothing between the blocks, no stream capture (the plan
-        needs the factors on the host), and not switched off (_lib.drop_path_compact, self.drop_path_compact)."""
+        """Does a forward on ``x`` take the compact route, the fused chain apart (route() asks _chain_ok first)?
+        Training with DropPath in every block, plain blocks on the add + norm kernels, nothing between the blocks, no
+        stream capture (the plan needs the factors on the host), and not switched off (_lib.drop_path_compact,
+        self.drop_path_compact)."""
         if not (self.drop_path_compact and _lib.drop_path_compact_enabled() and self.training
                 and type(self) is MixerModel and inference_params is None and len(self.layers) > 1
                 and x.is_cuda and x.dim() == 3 and isinstance(self.drop_out_in_block, nn.Identity)
@@ -233,7 +260,7 @@ class MixerModel(nn.Module):
             if not (type(layer) is Block and type(layer.norm) in _KERNEL_NORMS and type(layer.mixer) is Mamba
                     and isinstance(dp, DropPath) and dp.training and 0.0 < dp.drop_prob < 1.0):
                 return False
-        return not torch.cuda.is_current_stream_capturing() and not self._chain_ok(x)
+        return not torch.cuda.is_current_stream_capturing()
 
     def _first_block_applies(self, tokens, seqlen):
         """Will _first_block_on_distinct_tokens take (B, G, C) ``tokens`` expanded to ``seqlen`` positions?  Shapes and
@@ -244,12 +271,15 @@ class MixerModel(nn.Module):
         return (tokens.is_cuda and type(layer.norm) in _KERNEL_NORMS and isinstance(layer.mixer, Mamba)
                 and layer.mixer.use_fast_path and seq_expand.expansion_len_ok(tokens, seqlen))
 
-    def draw_drop_plan(self, like, lead=False, drop_masks=None):
+    def draw_drop_plan(self, like, lead=False, drop_masks=None, route=None):
         """Draw the DropPath factors of blocks 1 .. n - 1 for a batch like ``like``'s NOW -- the same bernoulli_ calls
         in the same order as the blocks would make (``lead``: block 0's unused draw first, see DropPlan) -- and start
         their copy to the host.  -> a DropPlan for forward(drop_plan=...), or None when a forward on ``like`` would not
-        take the compact route (then nothing is drawn).  ``drop_masks``: these factors instead of drawn ones."""
-        if not self._compact_ok(like):
+        take the compact route (then nothing is drawn).  ``drop_masks``: these factors instead of drawn ones.
+        ``route``: route()'s answer for this forward when the caller holds it (``lead`` is then ``route.lead``)."""
+        if route is None:
+            route = self.route(like)
+        if route.stack != "compact":
             return None
         n, B, dev = len(self.layers), like.shape[0], like.device
         plan = DropPlan()
@@ -342,17 +372,13 @@ class MixerModel(nn.Module):
         """Block 0 when the sequence is ``gather(tokens + pos, token_index)``: Add + LayerNorm + in_proj on the G
         distinct tokens, expanded to the L positions by a copy kernel (seq_expand.py).  -> (hidden, residual) of
         block 0 as the reference's Block.forward returns them (``emit_y``: the mixer's output before out_proj in
-        place of hidden, see _chain), or None when the route does not apply.  ``keep`` = (samples (n,) int32, n): the
-        mixer runs on these samples only and ``hidden`` holds them in this order (None when n == 0); the residual
-        keeps the whole batch."""
+        place of hidden, see _chain).  For routes with ``first_on_tokens`` (_first_block_applies, which holds L % G == 0
+        among its conditions).  ``keep`` = (samples (n,) int32, n): the mixer runs on these samples only and ``hidden``
+        holds them in this order (None when n == 0); the residual keeps the whole batch."""
         from . import seq_expand
         layer = self.layers[0]
         mixer = layer.mixer
-        if not self._first_block_applies(tokens, token_index.shape[1]):
-            return None
         inv32 = seq_expand.inverse_positions(token_index, tokens.shape[1])
-        if inv32 is None:
-            return None
         idx32 = token_index.to(torch.int32).contiguous()
         # residual_0 = tokens + pos and its LayerNorm in one pass over the G tokens.  (Low-precision operands: the
         # reference's `input_ids + pos` rounds the sum to that dtype first -- keep that rounding.)
@@ -369,8 +395,7 @@ class MixerModel(nn.Module):
         else:
             xz = seq_expand.seq_gather_last(mixer.in_proj_xz(normed), idx32, inv32)      # (B, 2D, L)
             hidden = mixer.forward_xz(xz, A=A, emit_y=emit_y)
-        residual = torch.gather(res0, 1, token_index.unsqueeze(-1).expand(-1, -1, res0.shape[-1]))
-        return hidden, residual
+        return hidden, take(res0, token_index)
 
     def _precompute_A(self):
         """A = -exp(A_log) of every layer in three launches (stack, exp, neg) instead of two per layer, and one
@@ -404,13 +429,21 @@ class MixerModel(nn.Module):
                 return False
         return True
 
-    def _chain(self, first, y, normed, residual, A_all):
-        """Blocks ``first``.. of the stack and its final norm on the fused route.  Enters either with ``normed`` (the
-        LayerNorm output block ``first`` feeds its mixer) or with ``y`` (block ``first - 1``'s mixer output before
-        out_proj); ``residual`` is the fp32 residual stream that goes with it.  What the reference computes across each
+    def _chain(self, first, hidden_states, residual, A_all):
+        """Blocks ``first``.. of the stack and its final norm on the fused route.  ``hidden_states``: the stack's input
+        when ``first == 0`` (block 0's add + norm opens the chain with ``normed``, the LayerNorm output a block feeds
+        its mixer), else ``y``, block ``first - 1``'s mixer output before out_proj (B, d_inner, L); ``residual`` is the
+        fp32 residual stream that goes with it.  What the reference computes across each
         block boundary -- out_proj (models/block.py:72), residual = drop_path(hidden) + residual and norm(residual) at
         the top of the next block (:56-58), or norm_f after the last (models/point_mamba.py:257-258) -- is one kernel;
         shapes it does not take run the same three ops through the library GEMM and the add + LayerNorm kernel."""
+        y = normed = None
+        if first == 0:
+            l0 = self.layers[0]
+            scale = l0.drop_path.rowscale(hidden_states) if isinstance(l0.drop_path, DropPath) else None
+            normed, residual = _fused_norm(hidden_states, None, l0.norm, rowscale=scale)
+        else:
+            y = hidden_states
         n = len(self.layers)
         i = first
         while True:
@@ -437,7 +470,7 @@ class MixerModel(nn.Module):
             i += 1
 
     def forward(self, input_ids, pos, inference_params=None, token_index=None, balanced_index=False, *,
-                drop_plan=None, drop_masks=None):
+                route=None, drop_plan=None, drop_masks=None):
         """Reference signature (models/point_mamba.py:247).  ``token_index`` (B, L) int64, optional and specific to
         this implementation: when given, ``input_ids`` / ``pos`` are the G DISTINCT tokens (B, G, C) and the sequence
         the reference would be handed is their gather by ``token_index``; the result is the same.
@@ -446,62 +479,55 @@ class MixerModel(nn.Module):
         does the first block's per-token head run on the G tokens (the adjoint of that expansion sums a fixed number
         of positions per token); any other index takes the reference's route on the gathered sequence.
 
-        ``drop_plan`` (keyword-only, specific to this implementation): what draw_drop_plan returned for this forward
-        when the caller drew the DropPath factors early (PointMamba does, ahead of its tokeniser, so that the copy to
-        the host is long done here); without one the factors are drawn on entry.  ``drop_masks``: a test hook, the
-        (B,) rowscales of blocks 1 .. n - 1 to use in place of drawn ones, on the compact and on the full route."""
-        first = 0
-        residual = None
-        first_on_tokens = (token_index is not None and balanced_index and inference_params is None
-                           and len(self.layers) > 0 and self._first_block_applies(input_ids, token_index.shape[1]))
+        ``route``, ``drop_plan`` (keyword-only, specific to this implementation): route()'s answer for this forward
+        and what draw_drop_plan returned for it, when the caller asked and drew early (PointMamba does, ahead of its
+        tokeniser, so that the copy to the host is long done here); without them the route is decided and the factors
+        are drawn on entry.  ``drop_masks``: a test hook, the (B,) rowscales of blocks 1 .. n - 1 to use in place of
+        drawn ones, on the compact and on the full route."""
+        if route is None:
+            route = self.route(input_ids, token_index.shape[1] if (token_index is not None and balanced_index) else None,
+                               inference_params)
         plan = drop_plan
         if plan is None:
-            plan = self.draw_drop_plan(input_ids, lead=not first_on_tokens, drop_masks=drop_masks)
-        elif plan.lead == first_on_tokens or plan.batch != input_ids.shape[0]:
+            plan = self.draw_drop_plan(input_ids, lead=route.lead, drop_masks=drop_masks, route=route)
+        elif route.stack != "compact" or plan.lead != route.lead or plan.batch != input_ids.shape[0]:
             raise ValueError("MixerModel.forward: drop_plan was drawn for another route or batch")
         if plan is not None:
             self._finish_plan(plan, input_ids.device)
             _lib.count("drop_path_compact")
         A_all = self._precompute_A()
-        chain = inference_params is None and len(self.layers) > 0 and self._chain_ok(input_ids)
-        if chain and drop_masks is not None:
+        if route.stack == "chain" and drop_masks is not None:
             raise NotImplementedError("MixerModel.forward(drop_masks=...): the fused bf16 chain draws its own factors")
-        if token_index is not None:
-            keep = None if plan is None else (plan.sel, plan.sizes[0])
-            done = (self._first_block_on_distinct_tokens(input_ids, pos, token_index, A=A_all[0], emit_y=chain,
-                                                         keep=keep)
-                    if (balanced_index and inference_params is None) else None)
-            if done is not None:
-                hidden_states, residual = done
-                if plan is not None:
-                    if hidden_states is None:               # block 0's mixer ran on no sample
-                        residual = _SkippedMixerFn.apply(residual, *self.layers[0].mixer.parameters())
-                    else:
-                        size = hidden_states.shape[0]
-                        _lib.compact_sizes[size] = _lib.compact_sizes.get(size, 0) + 1
-                if chain:                                   # hidden_states is block 0's y (B, d_inner, L)
-                    return self._chain(1, hidden_states, None, residual, A_all)
-                hidden_states = self.drop_out_in_block(hidden_states)
-                first = 1
-            else:                                       # the reference's route on the expanded sequence
-                ex = token_index.unsqueeze(-1)
-                input_ids = torch.gather(input_ids, 1, ex.expand(-1, -1, input_ids.shape[-1]))
-                pos = torch.gather(pos, 1, ex.expand(-1, -1, pos.shape[-1]))
-        if first == 0:
-            hidden_states = input_ids + pos
-        if chain:
-            l0 = self.layers[0]
-            scale = l0.drop_path.rowscale(hidden_states) if isinstance(l0.drop_path, DropPath) else None
-            normed, residual = _fused_norm(hidden_states, None, l0.norm, rowscale=scale)
-            return self._chain(0, None, normed, residual, A_all)
-        n = len(self.layers)
+        if route.first_on_tokens:
+            hidden_states, residual = self._first_block_on_distinct_tokens(
+                input_ids, pos, token_index, A=A_all[0], emit_y=route.stack == "chain",
+                keep=None if plan is None else (plan.sel, plan.sizes[0]))
+            if plan is not None:
+                residual = self._compact_ran(0, hidden_states, residual)
+            hidden_states = self.drop_out_in_block(hidden_states)
+            first = 1
+        else:
+            if token_index is not None:                     # the reference's route on the expanded sequence
+                input_ids, pos = take(input_ids, token_index), take(pos, token_index)
+            hidden_states, residual, first = input_ids + pos, None, 0
+        if route.stack == "chain":
+            return self._chain(first, hidden_states, residual, A_all)
         if plan is not None:
             return self._compact_stack(first, hidden_states, residual, A_all, plan)
-        for i in range(first, n):
+        return self._layer_stack(first, hidden_states, residual, A_all, inference_params, drop_masks)
+
+    def _layer_stack(self, first, hidden_states, residual, A_all, inference_params=None, drop_masks=None):
+        """Blocks ``first``.. and the final norm, every block drawing its own factors (``drop_masks``: those)."""
+        for i in range(first, len(self.layers)):
             scale = drop_masks[i - 1] if (drop_masks is not None and i > 0) else None
             hidden_states, residual = self.layers[i](hidden_states, residual, inference_params=inference_params,
                                                      A=A_all[i], rowscale=scale)
             hidden_states = self.drop_out_in_block(hidden_states)
+        return self._final_norm(hidden_states, residual)
+
+    def _final_norm(self, hidden_states, residual):
+        """norm_f(hidden_states + residual), the stack's output (and the segmentation stack's taps): the add + norm
+        kernel on the GPU, the reference's composed torch ops otherwise."""
         if hidden_states.is_cuda and type(self.norm_f) in _KERNEL_NORMS and hidden_states.dim() == 3:
             # the stack's output norm returns the parameter dtype (fp32) under autocast too, as F.layer_norm does
             # there; the block norms feed a GEMM and may hand over the autocast dtype directly
@@ -509,6 +535,13 @@ class MixerModel(nn.Module):
         residual = (hidden_states + residual) if residual is not None else hidden_states
         return self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))
 
+    def _compact_ran(self, i, hidden_states, residual):
+        """Mixer ``i``'s compact batch is counted; one that ran on no sample gets zero gradients.  -> residual"""
+        if hidden_states is None:
+            return _SkippedMixerFn.apply(residual, *self.layers[i].mixer.parameters())
+        size = hidden_states.shape[0]
+        _lib.compact_sizes[size] = _lib.compact_sizes.get(size, 0) + 1
+        return residual
 
     def _compact_stack(self, first, hidden_states, residual, A_all, plan):
         """Blocks ``first``.. and the final norm with every mixer on its boundary's compact batch (DropPlan).
@@ -517,24 +550,20 @@ class MixerModel(nn.Module):
         n, B = len(self.layers), plan.batch
         io = hidden_states.dtype if hidden_states is not None else self.layers[0].mixer.out_proj.weight.dtype
         for i in range(first, n):
-            # always a dict, empty where neither side is compact: with a plan no block draws, block 0 included (on
-            # its own route through Block.forward it would draw a rowscale it never applies; the plan's ``lead`` draw
-            # stands for that one)
             compact = {}
             if i > 0 and plan.sizes[i - 1] < B:            # hidden holds boundary i's samples
                 compact.update(hidden_slot=plan.maps[i - 1], hidden_dtype=io)
             if i < n - 1 and plan.sizes[i] < B:            # mixer i runs on boundary i + 1's
                 compact.update(normed_slot=plan.maps[i], normed_batch=plan.sizes[i])
-            size = plan.sizes[i] if i < n - 1 else B
+            # draw=False: with a plan no block draws, block 0 included (on its own route through Block.forward it
+            # would draw a rowscale it never applies; the plan's ``lead`` draw stands for that one)
             hidden_states, residual = self.layers[i](hidden_states, residual, A=A_all[i],
                                                      rowscale=plan.masks[i - 1] if i > 0 else None,
-                                                     compact=compact)
-            if size:
+                                                     draw=False, compact=compact)
+            residual = self._compact_ran(i, hidden_states, residual)
+            if hidden_states is not None:
                 io = hidden_states.dtype
-                _lib.compact_sizes[size] = _lib.compact_sizes.get(size, 0) + 1
-            else:
-                residual = _SkippedMixerFn.apply(residual, *self.layers[i].mixer.parameters())
-        return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
+        return self._final_norm(hidden_states, residual)
 
 
 class MixerModel_add(MixerModel):
@@ -560,10 +589,9 @@ class MixerModel_add(MixerModel):
                              "discards the merge)")
         k = int(N_k_top_eigenvectors)
         if order is None:
-            from . import spectral
             vecs = top_k_eigenvectors[:, :, :k]
             B, G = vecs.shape[:2]
-            order = spectral.argsort_rows(vecs.transpose(1, 2).reshape(B * k, G)).view(B, k, G)
+            order = argsort_rows(vecs.transpose(1, 2).reshape(B * k, G)).view(B, k, G)
         if order.shape[1] != k or 2 * k * order.shape[2] != input_ids.shape[1]:
             raise ValueError(f"MixerModel_add: a sequence of {input_ids.shape[1]} tokens is not 2 k G with orders "
                              f"{tuple(order.shape)} and k = {k}")
@@ -576,7 +604,4 @@ class MixerModel_add(MixerModel):
             hidden_states = self.drop_out_in_block(hidden_states)
             hidden_states = (cross_merge_composed(hidden_states, order) if self.composed
                              else cross_merge(hidden_states, maps))
-        if hidden_states.is_cuda and type(self.norm_f) in _KERNEL_NORMS and hidden_states.dim() == 3:
-            return _fused_norm(hidden_states, residual, self.norm_f, out_dtype=self.norm_f.weight.dtype)[0]
-        residual = (hidden_states + residual) if residual is not None else hidden_states
-        return self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))
+        return self._final_norm(hidden_states, residual)

@@ -27,6 +27,7 @@ from .chamfer import (CHAMFER_SMALL_MAX, ChamferFn, ChamferRaggedFn, _CHAMFER_RE
                       _pair_lengths, chamfer_distance)
 from .emd import earth_movers_distance
 from .point_mamba import Encoder, Group
+from .spectral import take
 
 
 def default_mae_config(**over):
@@ -141,9 +142,6 @@ class MaskMamba_2(nn.Module):
             msk_src = torch.cat([msk_src, msk_src.flip(1)], 1)
             full_src = torch.cat([full_src, full_src.flip(1)], 1)
 
-        def take(x, idx):
-            return torch.gather(x, 1, idx.unsqueeze(-1).expand(-1, -1, x.shape[-1]))
-
         x_vis = self.blocks(take(tokens, vis_src), take(pos, vis_src))
         x_vis = self.norm(x_vis)
         return dict(x_vis=x_vis, orders=orders, pos_mask=take(pos, msk_src), pos_full=take(pos, full_src), mask=mask,
@@ -256,12 +254,12 @@ class Point_MAE_Mamba(nn.Module):
         x_vis, C = enc["x_vis"], enc["C"]
         if noaug:
             return x_vis
-        T = k * G * (2 if self.reverse else 1)
+        T = spectral.sast_len(k, G, self.reverse)
         # mask tokens at the masked positions, visible tokens back at theirs (:3150-3190)
         x_full = self.mask_token.to(x_vis.dtype).expand(B, T, C).scatter(
             1, enc["vis_seq"].unsqueeze(-1).expand(-1, -1, C), x_vis)
         x_rec = self.MAE_decoder(x_full, enc["pos_full"], enc["pos_mask"].shape[1])
-        x_rec = torch.gather(x_rec, 1, enc["msk_seq"].unsqueeze(-1).expand(-1, -1, C))          # (B, Mtok, C)
+        x_rec = take(x_rec, enc["msk_seq"])                                                      # (B, Mtok, C)
         Mtok = x_rec.shape[1]
         w = self.increase_dim[0]
         rebuild = F.linear(x_rec.reshape(B * Mtok, C), w.weight.squeeze(-1), w.bias).reshape(B * Mtok, -1, 3)
@@ -296,7 +294,7 @@ class Point_MAE_Mamba(nn.Module):
         B, G, M, _ = neighborhood.shape
         rebuild, src = parts["rebuild"].float(), parts["msk_src"]                 # (B * Mtok, M, 3), (B, Mtok)
         Mtok = src.shape[1]
-        centre = torch.gather(center, 1, src.unsqueeze(-1).expand(-1, -1, 3))
+        centre = take(center, src)
         rebuilt = (rebuild.view(B, Mtok, M, 3) + centre.unsqueeze(2)).reshape(B, Mtok * M, 3)
         keep = ~parts["mask"]
         visible = (neighborhood[keep] + center[keep].unsqueeze(1)).reshape(B, -1, 3)

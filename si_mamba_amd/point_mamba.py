@@ -181,13 +181,6 @@ class PointMamba(nn.Module):
                                       "are built; the wavelet / RL research branches are out of scope")
         self.hlt_rand = True          # the reference's torch.rand tie-break of HLT (:1062); tests switch it off
 
-    def _side_stream(self, device):
-        st = getattr(self, "_spectral_stream", None)
-        if st is None or st.device != device:
-            st = torch.cuda.Stream(device=device)
-            self._spectral_stream = st
-        return st
-
     def get_loss_acc(self, ret, gt):
         loss = self.loss_ce(ret, gt.long())
         pred = ret.argmax(-1)
@@ -203,51 +196,40 @@ class PointMamba(nn.Module):
     def spectral_order(self, center):
         return self.spectral_eigs(center)[2]
 
+    def _on_tokens(self):
+        """Is the stack handed the G distinct tokens plus an index map (SAST / MAMBA: the sequence is a pure gather of
+        them), not the assembled sequence?  Not with input dropout, which acts on every position by itself, and not
+        with add_after_layer, whose stack merges whole sequences."""
+        return (not self.add_after_layer and self.method in ("SAST", "MAMBA")
+                and not (self.training and self.drop_out.p > 0))
+
+    def seq_len(self):
+        """Length of token_index()'s rows, known before the centres are."""
+        if self.method == "MAMBA":
+            return spectral.XYZ_ORDERS * self.num_group
+        return spectral.sast_len(self.k_top_eigenvectors, self.num_group, self.reverse)
+
     def token_index(self, center, order=None):
-        """(B, L) int64 patch index of every sequence position for the routes that are pure gathers (SAST :868-989,
-        MAMBA :850-866); None for HLT, whose assembly also writes zeros (:1075-1112)."""
+        """(B, seq_len()) int64 patch index of every sequence position for the routes that are pure gathers (SAST
+        :868-989, MAMBA :850-866); None for HLT, whose assembly also writes zeros (:1075-1112)."""
         if self.method == "SAST":
             if order is None:
                 order = self.spectral_order(center)
             return spectral.sast_index_map(order, self.reverse)
         if self.method == "MAMBA":
-            return torch.cat([center[:, :, a].argsort(dim=-1) for a in range(3)], dim=1)
+            return spectral.xyz_sorted_index(center)
         return None
 
     def order_tokens(self, tokens, pos, center, order=None):
         """Tokens and positions in sequence order for ``self.method`` (reference :850-1112)."""
-        if self.method == "SAST":                                               # :868-989
-            if order is None:
-                order = self.spectral_order(center)
-            return spectral.sast_gather(tokens, pos, order, reverse=self.reverse)
-        if self.method == "MAMBA":                                              # :850-866: x-, y-, z-sorted copies
-            idx = torch.cat([center[:, :, a].argsort(dim=-1) for a in range(3)], dim=1).unsqueeze(-1)
-            return (torch.gather(tokens, 1, idx.expand(-1, -1, tokens.shape[-1])),
-                    torch.gather(pos, 1, idx.expand(-1, -1, pos.shape[-1])))
-        # HLT :1054-1112
-        adj = spectral.create_graph_from_centers(center, self.knn_graph, self.alpha, self.symmetric, self.self_loop,
-                                                 self.binary)
-        vecs = spectral._eig(adj, self.k_top_eigenvectors, self.smallest, False, want_all=False)[1]     # :1057
-        rand = torch.rand(center.shape[0], center.shape[1], device=center.device) if self.hlt_rand else None
-        t, p, _, _ = spectral.hlt_assemble(tokens, pos, center, vecs, self.k_top_eigenvectors, rand=rand)
-        return t, p
-
-    def _draw_drop_plan(self, pts):
-        """The stack's DropPath factors, drawn before the tokeniser (MixerModel.draw_drop_plan): their copy to the host,
-        which the stack waits for to plan its compact batches, then finishes underneath FPS, grouping and the
-        encoder.  Only on the route that hands the stack the distinct tokens (SAST / MAMBA, no input dropout): nothing
-        between here and the blocks draws from the generator there, so every draw keeps its place in the sequence.
-        Every other route returns None and leaves the draw to the stack's entry."""
-        if self.add_after_layer or self.method not in ("SAST", "MAMBA") or not pts.is_cuda or pts.dim() != 3 \
-                or (self.training and self.drop_out.p > 0):
-            return None
-        G = self.num_group
-        L = 3 * G if self.method == "MAMBA" else self.k_top_eigenvectors * G * (2 if self.reverse else 1)
-        # shape and device of the tokens the stack will be handed (no storage behind it)
-        like = torch.empty_strided((pts.shape[0], G, self.trans_dim), (0, 0, 0), device=pts.device)
-        if not self.blocks._compact_ok(like):
-            return None
-        return self.blocks.draw_drop_plan(like, lead=not self.blocks._first_block_applies(like, L))
+        if self.method == "SAST" and order is None:
+            order = self.spectral_order(center)
+        elif self.method == "HLT":                                              # :1054-1057: the eigenvectors
+            adj = spectral.create_graph_from_centers(center, self.knn_graph, self.alpha, self.symmetric,
+                                                     self.self_loop, self.binary)
+            order = spectral._eig(adj, self.k_top_eigenvectors, self.smallest, False, want_all=False)[1]
+        return spectral.order_tokens(self.method, (tokens, pos), center, order, self.k_top_eigenvectors, self.reverse,
+                                     self.hlt_rand)
 
     def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None, *, lengths=None):
         """Reference signature (models/point_mamba.py:843; the runner calls
@@ -269,27 +251,27 @@ class PointMamba(nn.Module):
         want_policy = gt is not None
         if want_policy and self.method != "SAST":
             raise NotImplementedError("PointMamba.forward(gt=...): the reference defines `policy` on the SAST route only")
-        drop_plan = self._draw_drop_plan(pts)
+        on_tokens = self._on_tokens()
+        route = drop_plan = None
+        if on_tokens:
+            # The stack's route, asked before the tokeniser from the shape and device of the tokens it will be handed
+            # (no storage behind the stand-in), and on the compact route its DropPath factors, drawn here
+            # (MixerModel.draw_drop_plan): their copy to the host, which the stack waits for to plan its compact
+            # batches, then finishes underneath FPS, grouping and the encoder.  Nothing between here and the blocks
+            # draws from the generator on this route, so every draw keeps its place in the sequence; every other route
+            # leaves the draw to the stack's entry.
+            like = torch.empty_strided((pts.shape[0], self.num_group, self.trans_dim), (0, 0, 0), device=pts.device)
+            route = self.blocks.route(like, self.seq_len())
+            drop_plan = self.blocks.draw_drop_plan(like, lead=route.lead, route=route)
         neighborhood, center, _ = self.group_divider(pts, lengths=lengths)
-        order = spec = None
-        overlap = center.is_cuda and self.method == "SAST"
         # The eigen-ordering depends only on the centres and is latency-bound on B of the 256 CUs: run it
         # on a side HIP stream underneath the (MFMA-bound) patch encoder, join before the gather.
-        if overlap:
-            main = torch.cuda.current_stream(center.device)
-            side = self._side_stream(center.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                spec = self.spectral_eigs(center)
-                order = spec[2]
-            center.record_stream(side)
+        join = (spectral.run_on_side_stream(lambda: self.spectral_eigs(center), center)
+                if center.is_cuda and self.method == "SAST" else None)
         tokens = self.encoder(neighborhood)
         pos = self.pos_embed(center)
-        if overlap:
-            main.wait_stream(side)
-            for t in spec:
-                t.record_stream(main)
-        idx = None if self.add_after_layer else self.token_index(center, order)
+        spec = join() if join is not None else None
+        order = None if spec is None else spec[2]
         if self.add_after_layer:
             # :1118-1119: the stack merges the orderings after every block, so it takes the whole sequence (every
             # position through block 0, not the distinct tokens) plus the eigenvectors and their argsort
@@ -298,11 +280,12 @@ class PointMamba(nn.Module):
             x, pos = self.order_tokens(tokens, pos, center, spec[2])
             x = self.drop_out(x)
             x = self.blocks(x, pos, spec[1], self.k_top_eigenvectors, self.reverse, order=spec[2])
-        elif idx is not None and not (self.training and self.drop_out.p > 0):
+        elif on_tokens:
             # the sequence is a gather of the G patch tokens: the stack takes the distinct tokens plus the index map
             # and runs the first block's per-token head on G instead of L positions (seq_expand.py); same result
-            x = self.blocks(tokens, pos, token_index=idx, balanced_index=True,     # concatenated permutations
-                            drop_plan=drop_plan)
+            x = self.blocks(tokens, pos, token_index=self.token_index(center, order),
+                            balanced_index=True,                                    # concatenated permutations
+                            route=route, drop_plan=drop_plan)
         else:
             x, pos = self.order_tokens(tokens, pos, center, order)
             x = self.drop_out(x)

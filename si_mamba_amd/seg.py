@@ -18,7 +18,6 @@ unchanged.
 """
 from __future__ import annotations
 
-from functools import partial
 from types import SimpleNamespace
 
 import torch
@@ -26,11 +25,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import spectral
-from .block import DropPath, _fused_norm, _init_weights, create_block
+from .block import DropPath, MixerModel
 from .encoder_ops import bn_relu_fn, token_linear
 from .interp import three_interpolate, three_nn
 from .point_mamba import Encoder, Group
-from .rms_norm import RMSNorm
 
 
 def default_seg_config(**over):
@@ -42,25 +40,17 @@ def default_seg_config(**over):
     return SimpleNamespace(**cfg)
 
 
-class MixerModelForSegmentation(nn.Module):
+class MixerModelForSegmentation(MixerModel):
     """reference pt_mamba.py:320-416: the block stack, returning norm_f(hidden + residual) after each layer in
-    ``fetch_idx`` (no DropPath on the tap)."""
+    ``fetch_idx`` (no DropPath on the tap).  Constructor, parameter names and initialisation are MixerModel's."""
 
     def __init__(self, d_model, n_layer, ssm_cfg=None, norm_epsilon=1e-5, rms_norm=False, initializer_cfg=None,
                  fused_add_norm=False, residual_in_fp32=False, drop_path=0.1, fetch_idx=(3, 7, 11), device=None,
                  dtype=None):
-        super().__init__()
-        kw = {"device": device, "dtype": dtype}
-        self.residual_in_fp32 = residual_in_fp32
-        self.fused_add_norm = fused_add_norm
+        super().__init__(d_model, n_layer, ssm_cfg=ssm_cfg, norm_epsilon=norm_epsilon, rms_norm=rms_norm,
+                         initializer_cfg=initializer_cfg, fused_add_norm=fused_add_norm,
+                         residual_in_fp32=residual_in_fp32, drop_path=drop_path, device=device, dtype=dtype)
         self.fetch_idx = tuple(fetch_idx)
-        self.layers = nn.ModuleList([
-            create_block(d_model, ssm_cfg=ssm_cfg, norm_epsilon=norm_epsilon, rms_norm=rms_norm,
-                         residual_in_fp32=residual_in_fp32, fused_add_norm=fused_add_norm, layer_idx=i,
-                         drop_path=drop_path, **kw) for i in range(n_layer)])
-        self.norm_f = (nn.LayerNorm if not rms_norm else RMSNorm)(d_model, eps=norm_epsilon, **kw)
-        self.apply(partial(_init_weights, n_layer=n_layer, **(initializer_cfg if initializer_cfg is not None else {})))
-        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
 
     def forward(self, input_ids, pos, inference_params=None):
         hidden_states = input_ids + pos
@@ -69,11 +59,7 @@ class MixerModelForSegmentation(nn.Module):
         for i, layer in enumerate(self.layers):
             hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params)
             if i in self.fetch_idx:
-                if hidden_states.is_cuda:
-                    feats.append(_fused_norm(hidden_states, residual, self.norm_f,
-                                             out_dtype=self.norm_f.weight.dtype)[0])
-                else:
-                    feats.append(self.norm_f((hidden_states + residual).to(self.norm_f.weight.dtype)))
+                feats.append(self._final_norm(hidden_states, residual))
         return feats
 
 
@@ -174,25 +160,12 @@ class PartSegMamba(nn.Module):
         return spectral._eig(adj, self.k_top_eigenvectors, self.smallest, False, want_all=False, want_order=True)[4]
 
     def order_tokens(self, tokens, pos, center, spec=None):
-        """-> (tokens, pos, center) in sequence order: (B, L, C), (B, L, C), (B, L, 3)."""
-        if self.method == "Point_MAMBA":                                        # :640-663
-            idx = torch.cat([center[:, :, a].argsort(dim=-1) for a in range(3)], dim=1)
-            ex = idx.unsqueeze(-1)
-            return (torch.gather(tokens, 1, ex.expand(-1, -1, tokens.shape[-1])),
-                    torch.gather(pos, 1, ex.expand(-1, -1, pos.shape[-1])),
-                    torch.gather(center, 1, ex.expand(-1, -1, 3)))
+        """-> (tokens, pos, center) in sequence order: (B, L, C), (B, L, C), (B, L, 3).  Point_MAMBA :640-663, HLT
+        :665-723, SAST :725-759 (the graph is create_graph_from_centers here, not the feature-space variant)."""
         if spec is None:
             spec = self._spectral(center)
-        if self.method == "HLT":                                                # :665-723
-            rand = torch.rand(center.shape[0], center.shape[1], device=center.device) if self.hlt_rand else None
-            t, p, c, _ = spectral.hlt_assemble(tokens, pos, center, spec, self.k_top_eigenvectors, rand=rand)
-            return t, p, c
-        # SAST :725-759 (the graph is create_graph_from_centers here, not the feature-space variant)
-        idx = spectral.sast_index_map(spec, self.reverse)
-        ex = idx.unsqueeze(-1)
-        return (torch.gather(tokens, 1, ex.expand(-1, -1, tokens.shape[-1])),
-                torch.gather(pos, 1, ex.expand(-1, -1, pos.shape[-1])),
-                torch.gather(center, 1, ex.expand(-1, -1, 3)))
+        return spectral.order_tokens(self.method, (tokens, pos, center), center, spec, self.k_top_eigenvectors,
+                                     self.reverse, self.hlt_rand)
 
     # ---- forward -------------------------------------------------------------------------------------------------
     def forward(self, pts, cls_label, *, lengths=None):

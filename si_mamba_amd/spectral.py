@@ -109,10 +109,14 @@ def argsort_rows(vals):
     return idx
 
 
+def take(x, idx):
+    """Token gather: x (B, G, C), idx (B, L) int64 -> (B, L, C) with out[b, l] = x[b, idx[b, l]]."""
+    return torch.gather(x, 1, idx.unsqueeze(-1).expand(-1, -1, x.shape[-1]))
+
+
 def sort_points_by_fiedler(points, fiedler_vector):
     """reference :817-826 (384 generalised to points.shape[-1]); differentiable w.r.t. points."""
-    order = argsort_rows(fiedler_vector)
-    return torch.gather(points, 1, order.unsqueeze(-1).expand(-1, -1, points.shape[-1]))
+    return take(points, argsort_rows(fiedler_vector))
 
 
 def multilevel_travers(eigen_vectors, level):
@@ -150,8 +154,13 @@ def spectral_order(center, knn_graph, alpha, k_top_eigenvectors, smallest=True, 
     return vals, vecs, order
 
 
+def sast_len(k, G, reverse=True):
+    """Length of sast_index_map's rows for (B,k,G) orders."""
+    return k * G * (2 if reverse else 1)
+
+
 def sast_index_map(order, reverse=True):
-    """(B,k,G) orders -> (B, k*G*(1+reverse)) token indices: k orderings, then their flip (:982-989)."""
+    """(B,k,G) orders -> (B, sast_len(k, G, reverse)) token indices: k orderings, then their flip (:982-989)."""
     idx = order.flatten(1)
     if reverse:
         idx = torch.cat((idx, idx.flip(1)), 1)
@@ -161,9 +170,15 @@ def sast_index_map(order, reverse=True):
 def sast_gather(tokens, pos, order, reverse=True):
     """Token assembly of reference :889-898 + :982-989 as one gather per tensor."""
     idx = sast_index_map(order, reverse)
-    ex = idx.unsqueeze(-1)
-    return (torch.gather(tokens, 1, ex.expand(-1, -1, tokens.shape[-1])),
-            torch.gather(pos, 1, ex.expand(-1, -1, pos.shape[-1])))
+    return take(tokens, idx), take(pos, idx)
+
+
+XYZ_ORDERS = 3
+
+
+def xyz_sorted_index(center):
+    """(B,G,3) centres -> (B, XYZ_ORDERS * G) patch indices: the x-, y- and z-sorted orders in a row (:850-866)."""
+    return torch.cat([center[:, :, a].argsort(dim=-1) for a in range(XYZ_ORDERS)], dim=1)
 
 
 _hlt_maps = {}
@@ -196,26 +211,43 @@ def hlt_index_map(G, k, device=None):
     return idx
 
 
-def hlt_assemble(tokens, pos, center, top_k_eigenvectors, k, rand=None):
+def hlt_take(tensors, top_k_eigenvectors, k, rand=None):
     """HLT token order of reference :1059-1112: bit-code traversal (multilevel_travers) + random tie-break
     (``rand``: (B, G) in [0,1), the reference's torch.rand at :1062; None = no tie-break) -> argsort -> the
-    block assembly above.  Returns (tokens (B,2G,C), pos (B,2G,C), center (B,2G,3), order (B,G))."""
+    block assembly above.  -> (every (B,G,*) tensor of ``tensors`` as (B,2G,*), order (B,G))."""
     codes = multilevel_travers(top_k_eigenvectors, k).to(torch.float32)
     if codes.dim() == 1:
         codes = codes.unsqueeze(0)
     if rand is not None:
         codes = codes + rand
     order = argsort_rows(codes)
-    G = order.shape[1]
-    slot = hlt_index_map(G, k, order.device)
+    slot = hlt_index_map(order.shape[1], k, order.device)
     valid = (slot >= 0)
     src = torch.gather(order, 1, slot.clamp_min(0).unsqueeze(0).expand(order.shape[0], -1))     # (B, 2G)
+    return tuple(take(x, src) * valid.to(x.dtype)[None, :, None] for x in tensors), order
 
-    def pick(x):
-        out = torch.gather(x, 1, src.unsqueeze(-1).expand(-1, -1, x.shape[-1]))
-        return out * valid.to(x.dtype)[None, :, None]
 
-    return pick(tokens), pick(pos), pick(center), order
+def hlt_assemble(tokens, pos, center, top_k_eigenvectors, k, rand=None):
+    """hlt_take of the three -> (tokens (B,2G,C), pos (B,2G,C), center (B,2G,3), order (B,G))."""
+    out, order = hlt_take((tokens, pos, center), top_k_eigenvectors, k, rand)
+    return (*out, order)
+
+
+def order_tokens(method, tensors, center, spec, k, reverse=True, hlt_rand=True):
+    """Every (B,G,*) tensor of ``tensors`` in sequence order, for the three orderings the models share.  ``spec``: what
+    the eigen-solver gave for the method, from either spectral route -- the (B,k,G) argsorts for "SAST" (:868-989), the
+    (B,G,k) eigenvectors for "HLT" (:1054-1112, with the reference's torch.rand tie-break of :1062 drawn here unless
+    ``hlt_rand`` is off); the xyz-sorted copies ("MAMBA" / "Point_MAMBA", :850-866) need none."""
+    if method == "HLT":
+        rand = torch.rand(center.shape[0], center.shape[1], device=center.device) if hlt_rand else None
+        return hlt_take(tensors, spec, k, rand)[0]
+    if method == "SAST":
+        idx = sast_index_map(spec, reverse)
+    elif method in ("MAMBA", "Point_MAMBA"):
+        idx = xyz_sorted_index(center)
+    else:
+        raise NotImplementedError(f"ordering method {method!r}")
+    return tuple(take(x, idx) for x in tensors)
 
 
 _side_streams = {}

@@ -249,3 +249,73 @@ def test_bf16_layer_by_layer(model, device):
         assert (qa.grad is None) == (qb.grad is None), ka
         if qb.grad is not None:
             assert nerr(qa.grad, qb.grad) < 1e-2, ka
+
+
+# ---- the classifier: its early route decision and draw against what the stack then does ------------------------------
+# (config overrides, does the stack take the compact route).  SAST / MAMBA at 16 patches: block 0 on the distinct tokens,
+# a plan without a lead draw, drawn ahead of the tokeniser; 18 patches (G % 4 != 0): the gathered route, a lead draw;
+# input dropout, HLT, add_after_layer: nothing is drawn early -- the plain stack draws on entry, the merging stack of
+# add_after_layer has no compact route.
+POINT_MAMBA_CASES = {
+    "sast": (dict(method="SAST"), True),
+    "mamba": (dict(method="MAMBA"), True),
+    "sast_18_patches": (dict(method="SAST", num_group=18), True),
+    "input_dropout": (dict(method="SAST", drop_out=0.1), True),
+    "hlt": (dict(method="HLT"), True),
+    "add_after_layer": (dict(method="SAST", add_after_layer=True), False),
+}
+
+
+def _point_mamba(device, **over):
+    from si_mamba_amd.point_mamba import PointMamba, default_config
+    from si_mamba_amd.synthetic import make_clouds
+    cfg = dict(trans_dim=128, encoder_dims=128, depth=3, group_size=8, num_group=16, knn_graph=4, drop_path=0.3,
+               cls_dim=5)
+    cfg.update(over)
+    torch.manual_seed(0)
+    return PointMamba(default_config(**cfg)).to(device).train(), make_clouds(B, 128, seed=0, device=device)
+
+
+@pytest.mark.parametrize("case", sorted(POINT_MAMBA_CASES))
+def test_point_mamba_early_draw_agrees_with_the_stack(case, device):
+    """PointMamba decides the stack's route and draws the plan before its tokeniser; the stack must then take exactly
+    that route (no ValueError from its guard), make the full route's draws and give the full route's logits."""
+    over, compact = POINT_MAMBA_CASES[case]
+    m, pts = _point_mamba(device, **over)
+    c0 = _lib.counters.get("drop_path_compact", 0)
+    s0 = dict(_lib.compact_sizes)
+    for n, seed in enumerate((11, 12, 13), 1):
+        with torch.no_grad():
+            torch.manual_seed(seed)
+            a = m(pts)
+            ra = torch.rand(5, device=device)
+            assert _lib.counters.get("drop_path_compact", 0) == c0 + n * int(compact)
+            torch.manual_seed(seed)
+            with _lib.drop_path_compact(False):
+                b = m(pts)
+            rb = torch.rand(5, device=device)
+        assert _lib.counters.get("drop_path_compact", 0) == c0 + n * int(compact)
+        e = nerr(a, b)
+        print(f"{case} seed {seed}: logits {e:.2e}")
+        assert e < 1e-5
+        assert torch.equal(ra, rb)
+    sizes = {k: v - s0.get(k, 0) for k, v in _lib.compact_sizes.items() if v != s0.get(k, 0)}
+    print(f"{case}: mixer batches {sizes}")
+    # drop_path = 0.3 at B = 6: over three seeds some boundary keeps at most four samples (a compact batch of 4)
+    assert any(k < B for k in sizes) == compact
+
+
+def test_route_predicates_run_once_per_forward(device, monkeypatch):
+    m, pts = _point_mamba(device, method="SAST")
+    calls = {}
+    for name in ("_compact_ok", "_chain_ok", "_first_block_applies"):
+        def spy(self, *a, _real=getattr(MixerModel, name), _name=name, **k):
+            calls[_name] = calls.get(_name, 0) + 1
+            return _real(self, *a, **k)
+        monkeypatch.setattr(MixerModel, name, spy)
+    c0 = _lib.counters.get("drop_path_compact", 0)
+    with torch.no_grad():
+        m(pts)
+    assert _lib.counters.get("drop_path_compact", 0) == c0 + 1
+    print(calls)
+    assert calls and all(n <= 1 for n in calls.values()), calls

@@ -54,6 +54,22 @@ def test_mixer_model_norm_f_follows_rms_norm():
     assert type(MixerModel(d_model=64, n_layer=2, drop_path=0.).norm_f) is torch.nn.LayerNorm
 
 
+@pytest.mark.parametrize("rms_norm", [False, True])
+def test_segmentation_stack_is_the_mixer_models_construction(rms_norm):
+    """After the same seed the two stacks hold the same state dict: same keys in the same order, equal tensors (one
+    constructor, one order of draws from the generator)."""
+    from si_mamba_amd.block import MixerModel
+    from si_mamba_amd.seg import MixerModelForSegmentation
+    torch.manual_seed(0)
+    a = MixerModel(64, 3, drop_path=0.1, rms_norm=rms_norm).state_dict()
+    torch.manual_seed(0)
+    b = MixerModelForSegmentation(64, 3, drop_path=0.1, rms_norm=rms_norm).state_dict()
+    assert list(a) == list(b)
+    assert all(k.startswith(("layers.", "norm_f.")) for k in a)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+
+
 _NORM_BIAS = re.compile(r"(^|\.)blocks\.(layers\.\d+\.norm|norm_f)\.bias$")
 
 
