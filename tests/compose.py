@@ -10,34 +10,8 @@ when both operands arrive as bf16).
 """
 import torch
 
+from helpers import scaled_err
 from oracle import scan_ref
-
-
-def clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
-
-
-def nerr(got, want):
-    """max |got - want| / max(1, max |want|): the normalised error the north-star tolerances are stated on."""
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
-
-
-def scaled_err(got, want):
-    """(max |got - want| / max |want|, rms(got - want) / rms(want)) in float64: the error on the tensor's OWN scale, with
-    no floor of 1 -- what a gradient of order 1e-3 needs (``nerr`` lets an absolute 1e-3 through, i.e. all of it).
-    Explicit fallback for a reference that is exactly zero (no scale to divide by): the two ABSOLUTE errors
-    (max |got|, rms(got)); a bound stated on the ratio then demands |got| below that bound outright."""
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    diff = got - want
-    dmax, drms = diff.abs().max().item(), diff.square().mean().sqrt().item()
-    wmax, wrms = want.abs().max().item(), want.square().mean().sqrt().item()
-    if wmax == 0.0:
-        return dmax, drms
-    return dmax / wmax, drms / wrms
 
 
 def mixer_oracle_run(ref, h, dout, io_dtype=None, f64=False):

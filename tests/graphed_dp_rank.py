@@ -18,14 +18,9 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from helpers import clouds  # noqa: E402  (run as a script: its own directory, tests/, leads sys.path)
+
 CLIP, LR = 10.0, 0.002
-
-
-def clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
 
 
 def no_dropout(model):

@@ -202,9 +202,9 @@ def channel_err(got, want, dim):
 
 def errors(got, want):
     """name -> {'chan': the per-channel scaled error (tensors with a channel axis; for dD / ddelta_bias, dB / dC the max
-    error on the tensor's own scale), 'max', 'rms': compose.scaled_err on the whole tensor, 'elem': worst single-element
+    error on the tensor's own scale), 'max', 'rms': helpers.scaled_err on the whole tensor, 'elem': worst single-element
     relative error (dD and ddelta_bias only; reported, not bounded)}."""
-    from compose import scaled_err
+    from helpers import scaled_err
     res = {}
     for k, w in want.items():
         if k not in got or got[k] is None:

@@ -6,31 +6,18 @@ import re
 
 import pytest
 
+import abi_tables
+from abi_tables import OFF, P, check_rows, declared_params
 from conftest import ROOT
 from si_mamba_amd import _lib
 
 
 def _declared():
-    text = open(os.path.join(ROOT, "include", "simamba.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(simamba_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(simamba_[a-z0-9_]+)\s*\(", abi_tables.header_code())))
 
 
 def test_header_and_binding_agree():
     assert _declared() == sorted(_lib.SIGNATURES)
-
-
-def _declared_params():
-    """name -> the parameter declarations of every simamba_* prototype in the header, comments stripped."""
-    text = open(os.path.join(ROOT, "include", "simamba.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    out = {}
-    for name, params in re.findall(r"\b(simamba_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in out, name
-        params = [p.strip() for p in params.split(",")]
-        out[name] = [] if params == ["void"] else params
-    return out
 
 
 def _kind(ctype):
@@ -45,7 +32,7 @@ def _kind(ctype):
 def test_header_and_binding_agree_on_parameters():
     """ctypes accepts surplus arguments silently and converts whatever argtypes says, so a binding that disagrees
     with the header would first show on the device: count and kind (pointer / float / integer) of every parameter."""
-    declared = _declared_params()
+    declared = declared_params()
     assert sorted(declared) == sorted(_lib.SIGNATURES)
     for name, params in declared.items():
         argtypes = _lib.SIGNATURES[name][1]
@@ -114,6 +101,7 @@ def test_library_exports_every_declared_symbol():
 def test_version_strerror_and_chunks():
     lib = _lib.load()
     assert lib.simamba_abi_version() == 9
+    assert _lib.ABI_VERSION == 9
     assert lib.simamba_strerror(0) == b"ok"
     assert b"dstate" in lib.simamba_strerror(-4)
     assert lib.simamba_scan_num_chunks(64) == 1
@@ -140,22 +128,30 @@ def test_version_strerror_and_chunks():
     assert b"variant" in lib.simamba_strerror(-9)
 
 
+def test_error_code_literals_equal_the_header():
+    """tests/abi_tables.py spells the codes as numbers, which are an ABI promise: each equals its #define, and the
+    header defines no code the tables have no name for."""
+    defines = {k: int(v) for k, v in re.findall(r"#define\s+SIMAMBA_(OK|E_[A-Z]+)\s+(-?\d+)", abi_tables.header_code())}
+    assert defines == {k: getattr(abi_tables, k) for k in defines}
+    assert sorted(defines.values()) == list(range(-10, 1))
+
+
 # The *_ex scan backward, the dt pair and the workspace query.  Every row states what it changes in a call that would
 # otherwise be accepted, and the code the library answers; rows with two faults pin the order of the checks.  P is a
 # 16-byte aligned address that is never dereferenced: no row gets as far as a memset or a launch.  (An empty backward
 # problem that passes validation clears the caller's accumulators, a device call, so it has no row here; the rows with
 # batch == 0 show that the checks in front of that still run.)
-P, OFF = 1 << 20, (1 << 20) + 4
 _BWD_EX = dict(u=P, delta=P, A=P, B=P, C=P, D=None, z=None, delta_bias=None, dout=P, x_ckpt=P, du=P, ddelta=P, dA=P,
                dB=P, dC=P, dD=None, dz=None, ddelta_bias=None, batch=2, dim=64, seqlen=32, dstate=16, io_dtype=0,
-               softplus=1, z_bs=0, dz_bs=0, bc_bs=0, bc_ns=0, bc_ts=0, ckpt_step=16, flags=1, workspace=P,
-               workspace_floats=1 << 40, stream=None)
+               delta_softplus=1, z_bstride=0, dz_bstride=0, bc_bstride=0, bc_nstride=0, bc_tstride=0, ckpt_step=16,
+               flags=1, workspace=P, workspace_floats=1 << 40, stream=None)
 _DT_FWD = dict(u=P, xdbl=P, wdt=P, A=P, D=None, z=P, delta_bias=None, out=P, x_ckpt=None, last_state=None, batch=2,
-               dim=64, seqlen=32, dstate=16, dt_rank=8, io_dtype=0, z_bs=0, xdbl_bs=0, xdbl_ts=0, ckpt_step=0,
-               variant=0, stream=None)
+               dim=64, seqlen=32, dstate=16, dt_rank=8, io_dtype=0, z_bstride=0, xdbl_bstride=0, xdbl_tstride=0,
+               ckpt_step=0, variant=0, stream=None)
 _DT_BWD_EX = dict(u=P, xdbl=P, wdt=P, A=P, D=None, z=P, delta_bias=None, dout=P, x_ckpt=P, du=P, ddelta=P, dA=P, dB=P,
                   dC=P, dD=None, dz=P, ddelta_bias=None, batch=2, dim=64, seqlen=32, dstate=16, dt_rank=8, io_dtype=0,
-                  z_bs=0, dz_bs=0, xdbl_bs=0, xdbl_ts=0, flags=1, workspace=P, workspace_floats=1 << 40, stream=None)
+                  z_bstride=0, dz_bstride=0, xdbl_bstride=0, xdbl_tstride=0, flags=1, workspace=P,
+                  workspace_floats=1 << 40, stream=None)
 _WS = dict(batch=2, dim=64, seqlen=32, dstate=16, ckpt_step=16, flags=1)
 
 SCAN_ROWS = [
@@ -170,10 +166,12 @@ SCAN_ROWS = [
         (dict(workspace=None), -6), (dict(workspace_floats=64), -6), (dict(workspace=OFF), -8),
         (dict(batch=0, dA=None), -1), (dict(seqlen=0, workspace=OFF), -8),                    # empty, and still checked
         # what the sequential kernel cannot take (deterministic: nothing is cleared in front of this answer)
-        (dict(dim=32), -9), (dict(dstate=8), -9), (dict(softplus=0), -9), (dict(u=OFF), -9), (dict(ddelta=OFF), -9),
+        (dict(dim=32), -9), (dict(dstate=8), -9), (dict(delta_softplus=0), -9), (dict(u=OFF), -9),
+        (dict(ddelta=OFF), -9),
         (dict(seqlen=30), -9), (dict(io_dtype=1, seqlen=36), -9), (dict(A=OFF), -9), (dict(x_ckpt=OFF), -9),
-        (dict(B=OFF), -9), (dict(bc_bs=514, bc_ns=32, bc_ts=1), -9), (dict(bc_bs=512, bc_ns=2, bc_ts=32), -9),
-        (dict(z=P, dz=OFF), -9), (dict(z=P, dz=P, z_bs=2050), -9), (dict(z=P, dz=P, dz_bs=1 << 29), -9),
+        (dict(B=OFF), -9), (dict(bc_bstride=514, bc_nstride=32, bc_tstride=1), -9),
+        (dict(bc_bstride=512, bc_nstride=2, bc_tstride=32), -9),
+        (dict(z=P, dz=OFF), -9), (dict(z=P, dz=P, z_bstride=2050), -9), (dict(z=P, dz=P, dz_bstride=1 << 29), -9),
         (dict(batch=4096, dim=4096, seqlen=64), -9),                                          # rows * seqlen = 2^30
         # two faults: flags, shape, ckpt_step, dstate, dtype, pointers, workspace size, workspace alignment, kernel
         (dict(flags=2, dim=0), -9), (dict(dim=0, ckpt_step=32), -2), (dict(ckpt_step=32, dstate=17), -9),
@@ -188,7 +186,8 @@ SCAN_ROWS = [
         (dict(io_dtype=1, seqlen=64, dt_rank=4), -2), (dict(io_dtype=1, seqlen=64, dt_rank=12), -2),   # bf16: of 8
         (dict(u=None), -1), (dict(xdbl=None), -1), (dict(wdt=None), -1), (dict(z=None), -1), (dict(out=None), -1),
         (dict(xdbl=OFF), -9), (dict(wdt=OFF), -9), (dict(u=OFF), -9), (dict(A=OFF), -9), (dict(seqlen=30), -9),
-        (dict(xdbl_bs=1 << 29), -9), (dict(xdbl_ts=42), -9), (dict(z_bs=2050), -9), (dict(z_bs=1 << 29), -9),
+        (dict(xdbl_bstride=1 << 29), -9), (dict(xdbl_tstride=42), -9), (dict(z_bstride=2050), -9),
+        (dict(z_bstride=1 << 29), -9),
         (dict(batch=4096, dim=4096, seqlen=64), -9),
         (dict(batch=0), 0), (dict(seqlen=0, u=None, xdbl=None, out=None), 0),                 # empty problems
         # two faults: shape, dstate, dtype, ckpt_step, variant, dt_rank, empty, pointers, the kernel's conditions
@@ -202,11 +201,11 @@ SCAN_ROWS = [
         (dict(dt_rank=6), -2), (dict(dt_rank=28), -2),
         (dict(io_dtype=1, seqlen=64, dt_rank=4), -2), (dict(io_dtype=1, seqlen=64, dt_rank=12), -2),
         (dict(xdbl=None), -1), (dict(wdt=None), -1), (dict(z=None), -1),
-        (dict(xdbl=OFF), -9), (dict(wdt=OFF), -9), (dict(xdbl_bs=1 << 29), -9), (dict(xdbl_ts=42), -9),
+        (dict(xdbl=OFF), -9), (dict(wdt=OFF), -9), (dict(xdbl_bstride=1 << 29), -9), (dict(xdbl_tstride=42), -9),
         (dict(dim=0), -2), (dict(batch=65536), -2), (dict(u=None), -1), (dict(dA=None), -1), (dict(dz=None), -1),
         (dict(x_ckpt=None), -1), (dict(workspace=None), -6), (dict(workspace_floats=64), -6),
         (dict(workspace=OFF), -8), (dict(batch=0, dA=None), -1), (dict(seqlen=0, workspace=OFF), -8),
-        (dict(dim=32), -9), (dict(u=OFF), -9), (dict(seqlen=30), -9), (dict(A=OFF), -9), (dict(dz_bs=2050), -9),
+        (dict(dim=32), -9), (dict(u=OFF), -9), (dict(seqlen=30), -9), (dict(A=OFF), -9), (dict(dz_bstride=2050), -9),
         # two faults: flags, dstate, dtype, dt_rank, pointers, xdbl's layout -- all in front of the shape check
         (dict(flags=2, dstate=8), -9), (dict(dstate=8, dim=0), -4), (dict(io_dtype=7, dt_rank=6), -3),
         (dict(dt_rank=6, xdbl=None), -2), (dict(xdbl=None, wdt=OFF), -1), (dict(xdbl=OFF, dim=0), -9),
@@ -243,9 +242,7 @@ def test_argument_validation_precedes_any_launch():
     assert lib.simamba_spectral_topk(one, n, n, n, one, 8, 1, 16, 4, 1.0, 4, 0, n) == -6
     assert lib.simamba_argsort_rows(one, one, 1, 2048, n) == -2
     for name, base, rows in SCAN_ROWS:
-        for change, want in rows:
-            assert set(change) <= set(base), change
-            assert getattr(lib, name)(*{**base, **change}.values()) == want, (name, change)
+        check_rows(name, base, rows, lib)
 
 
 def test_product_path_refuses_cpu_tensors():

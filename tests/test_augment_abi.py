@@ -10,10 +10,8 @@ import pytest
 import torch
 
 import augment_ref as ar
+from abi_tables import E_NULLPTR, E_SHAPE, E_VARIANT, P, check_rows
 from si_mamba_amd import _lib
-
-P = 1 << 20   # a non-null address that is never dereferenced: every call with it ends in validation
-E_NULLPTR, E_SHAPE, E_VARIANT = -1, -2, -9
 
 
 def _philox_lib(key, ctr):
@@ -119,25 +117,14 @@ PARAM_ROWS = [
 
 
 def test_return_codes_without_a_device():
-    lib = _lib.load()
-    for name, base, rows in (("simamba_augment_points", POINTS, POINT_ROWS),
-                             ("simamba_augment_params", PARAMS, PARAM_ROWS)):
-        for change, want in rows:
-            assert set(change) <= set(base), change
-            assert getattr(lib, name)(*{**base, **change}.values()) == want, (name, change)
+    check_rows("simamba_augment_points", POINTS, POINT_ROWS)
+    check_rows("simamba_augment_params", PARAMS, PARAM_ROWS)
 
 
 def test_out_over_points_with_a_gather_is_refused():
     """A gather reads rows that other lanes, or other clouds' workgroups, write: with either index width."""
-    fn = _lib.load().simamba_augment_points
-    assert fn(*{**POINTS, **GATHER, "out": P}.values()) == E_VARIANT
-    assert fn(*{**POINTS, "idx": P, "idx_is_64": 1, "out": P}.values()) == E_VARIANT
-
-
-def test_abi_version_unchanged():
-    assert _lib.load().simamba_abi_version() == 9
-    assert _lib.ABI_VERSION == 9
-    assert b"variant" in _lib.load().simamba_strerror(E_VARIANT)
+    check_rows("simamba_augment_points", POINTS, [(dict(**GATHER, out=P), E_VARIANT),
+                                                  (dict(idx=P, idx_is_64=1, out=P), E_VARIANT)])
 
 
 def test_opcodes_agree_with_the_binding_and_the_header():

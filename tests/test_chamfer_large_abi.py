@@ -3,13 +3,10 @@ device, in the order shape, empty, null pointers, and the Python route did not g
 import pytest
 import torch
 
-from si_mamba_amd import _lib
-
-P = 1 << 20   # a non-null address that is never dereferenced: every call below ends in validation
+from abi_tables import E_NULLPTR, E_SHAPE, E_VARIANT, OK, P, check_rows
 
 FWD = dict(x=P, y=P, dist=P, idx1=P, idx2=P, d1=P, d2=P, pairs=2, n=100, m=100, stream=None)
 BWD = dict(x=P, y=P, ddist=P, idx1=P, idx2=P, dx=P, dy=P, pairs=2, n=100, m=100, stream=None)
-OK, E_NULLPTR, E_SHAPE = 0, -1, -2
 
 ROWS = [
     (dict(n=0), E_SHAPE), (dict(n=8193), E_SHAPE), (dict(m=8193), E_SHAPE), (dict(m=0), E_SHAPE),
@@ -24,41 +21,27 @@ ROWS = [
 
 @pytest.mark.parametrize("name,base", [("simamba_chamfer_large_fwd", FWD), ("simamba_chamfer_large_bwd", BWD)])
 def test_return_codes_without_a_device(name, base):
-    fn = getattr(_lib.load(), name)
-    for change, want in ROWS:
-        if not set(change) <= set(base):       # dist exists in the forward only
-            change = {k: v for k, v in change.items() if k in base}
-        assert fn(*{**base, **change}.values()) == want, (name, change)
+    # dist exists in the forward only
+    check_rows(name, base, [({k: v for k, v in change.items() if k in base}, want) for change, want in ROWS])
 
 
 def test_forward_needs_every_output_and_backward_none():
-    lib = _lib.load()
-    for k in ("dist", "idx1", "d1", "d2"):
-        assert lib.simamba_chamfer_large_fwd(*{**FWD, k: None}.values()) == E_NULLPTR, k
-    assert lib.simamba_chamfer_large_bwd(*{**BWD, "ddist": None}.values()) == E_NULLPTR
+    check_rows("simamba_chamfer_large_fwd", FWD, [({k: None}, E_NULLPTR) for k in ("dist", "idx1", "d1", "d2")])
     # neither gradient wanted: nothing to launch
-    assert lib.simamba_chamfer_large_bwd(*{**BWD, "dx": None, "dy": None}.values()) == OK
+    check_rows("simamba_chamfer_large_bwd", BWD, [(dict(ddist=None), E_NULLPTR), (dict(dx=None, dy=None), OK)])
 
 
 def test_forced_queries_per_thread_is_checked_first():
-    lib = _lib.load()
-    E_VARIANT = -9
     fwd = {**FWD, "queries": 0}
     fwd = {k: fwd[k] for k in list(FWD)[:-1] + ["queries", "stream"]}
     bwd = {**BWD, "queries": 0}
     bwd = {k: bwd[k] for k in list(BWD)[:-1] + ["queries", "stream"]}
-    for fn, base in ((lib.simamba_chamfer_large_fwd_ex, fwd), (lib.simamba_chamfer_large_bwd_ex, bwd)):
-        for q in (3, 8, -1):
-            assert fn(*{**base, "queries": q}.values()) == E_VARIANT, q
-        assert fn(*{**base, "queries": 3, "n": 0}.values()) == E_VARIANT
-        for q in (0, 1, 2, 4):
-            assert fn(*{**base, "queries": q, "n": 0}.values()) == E_SHAPE
-            assert fn(*{**base, "queries": q, "pairs": 0, "x": None}.values()) == OK
-            assert fn(*{**base, "queries": q, "x": None}.values()) == E_NULLPTR
-
-
-def test_abi_version_unchanged():
-    assert _lib.load().simamba_abi_version() == 9
+    rows = [(dict(queries=q), E_VARIANT) for q in (3, 8, -1)] + [(dict(queries=3, n=0), E_VARIANT)]
+    for q in (0, 1, 2, 4):
+        rows += [(dict(queries=q, n=0), E_SHAPE), (dict(queries=q, pairs=0, x=None), OK),
+                 (dict(queries=q, x=None), E_NULLPTR)]
+    check_rows("simamba_chamfer_large_fwd_ex", fwd, rows)
+    check_rows("simamba_chamfer_large_bwd_ex", bwd, rows)
 
 
 def test_python_route_refuses_cpu_tensors():

@@ -6,9 +6,8 @@ import ctypes
 import pytest
 import torch
 
+from abi_tables import E_DTYPE, E_NULLPTR, E_SHAPE
 from si_mamba_amd import _lib
-
-E_NULLPTR, E_SHAPE, E_DTYPE = -1, -2, -3
 
 
 def restated_merge_expand(hidden, eigvecs, k):

@@ -9,11 +9,9 @@ import pytest
 import torch
 
 import dataset_ref as dr
+from abi_tables import E_NULLPTR, E_SHAPE, E_VARIANT, P, check_rows, declared_params, header_code
 from conftest import ROOT
 from si_mamba_amd import _lib
-
-P = 1 << 20   # a non-null address that is never dereferenced: every call with it ends in validation
-E_NULLPTR, E_SHAPE, E_VARIANT = -1, -2, -9
 
 SIZES = [1, 2, 3, 4, 5, 63, 64, 65, 1000, 9843, 52470, (1 << 20) + 1]
 SEEDS = [0, 0xa4093822299f31d0, 20240607]                                   # the second: both key words in use
@@ -137,21 +135,14 @@ FETCH_ROWS = [
 
 
 def test_fetch_return_codes_without_a_device():
-    fn = _lib.load().simamba_dataset_fetch
-    for change, want in FETCH_ROWS:
-        assert set(change) <= set(FETCH), change
-        assert fn(*{**FETCH, **change}.values()) == want, change
+    check_rows("simamba_dataset_fetch", FETCH, FETCH_ROWS)
 
 
-def test_abi_version_unchanged_and_symbols_bound():
-    lib = _lib.load()
-    assert lib.simamba_abi_version() == 9 and _lib.ABI_VERSION == 9
-    text = open(os.path.join(ROOT, "include", "simamba.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(simamba_[a-z0-9_]+)\s*\(", code))
+def test_symbols_and_modes_bound():
+    declared = set(declared_params())
     assert declared == set(_lib.SIGNATURES)
     assert {"simamba_dataset_fetch", "simamba_keyed_perm"} <= declared
-    header = {k: int(v) for k, v in re.findall(r"#define SIMAMBA_DS_([A-Z_]+)\s+(\d+)", text)}
+    header = {k: int(v) for k, v in re.findall(r"#define SIMAMBA_DS_([A-Z_]+)\s+(\d+)", header_code())}
     assert header == dict(SEQUENTIAL=0, SHUFFLE=1, FIRST=0, PERMUTE=1, CHOICE=2, NONE=0, UNIT_SPHERE=1,
                           STREAM_SHUFFLE=1, STREAM_ROWS=2, STREAM_CHOICE=3)
     for k, v in header.items():

@@ -8,12 +8,9 @@ import pytest
 import torch
 
 import assignment_ref as ar
-from si_mamba_amd import _lib
-
-P = 1 << 20   # a non-null address that is never dereferenced: every call below ends in validation
+from abi_tables import E_NULLPTR, E_SHAPE, P, check_rows
 
 FWD = dict(x=P, y=P, assign=P, dist=P, rounds=P, converged=P, pairs=2, n=100, eps=0.0, max_rounds=1000, stream=None)
-E_NULLPTR, E_SHAPE = -1, -2
 
 ROWS = [
     (dict(n=0), E_SHAPE), (dict(n=-1), E_SHAPE), (dict(n=1025), E_SHAPE), (dict(pairs=0), E_SHAPE),
@@ -32,15 +29,7 @@ ROWS = [
 
 
 def test_return_codes_without_a_device():
-    fn = _lib.load().simamba_emd_fwd
-    for change, want in ROWS:
-        assert set(change) <= set(FWD), change
-        assert fn(*{**FWD, **change}.values()) == want, change
-
-
-def test_abi_version_unchanged():
-    assert _lib.load().simamba_abi_version() == 9
-    assert _lib.ABI_VERSION == 9
+    check_rows("simamba_emd_fwd", FWD, ROWS)
 
 
 def test_python_route_refuses_cpu_tensors():

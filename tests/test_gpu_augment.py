@@ -17,6 +17,7 @@ import torch
 
 import augment_ref as ar
 from augment_ref import DIST_B, DIST_N, DIST_SEED
+from helpers import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,8 @@ def ref_chain(transforms):
     return [t.op() for t in transforms]
 
 
-def clouds(B, N, seed, device):
+def uniform_clouds(B, N, seed, device):
+    """Points uniform in the cube [-1, 1)^3."""
     g = torch.Generator().manual_seed(seed)
     return (torch.rand(B, N, 3, generator=g) * 2 - 1).to(device)
 
@@ -69,14 +71,6 @@ def state_at(device, seed=SEED, step=STEP):
 
 def run(points, transforms, step=STEP, seed=SEED, **kw):
     return T().sample_and_augment(points, transforms, state=state_at(points.device, seed, step), **kw)
-
-
-def bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 # ---- the drawn parameters --------------------------------------------------------------------------------------------
@@ -125,7 +119,7 @@ def test_parameters_do_not_advance_the_step_and_skip_the_padding(device):
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("N", SIZES)
 def test_points_against_the_float64_chain(device, N, B):
-    pts = clouds(B, N, N, device)
+    pts = uniform_clouds(B, N, N, device)
     host = pts.cpu().numpy()
     worst = 0.0
     for name, tr in chains().items():
@@ -153,7 +147,7 @@ def test_points_agree_with_the_restatements_own_draws(device):
     """End to end with nothing taken from the library: the restatement draws, the kernel draws, the clouds agree within
     the chain's bound plus what the 1e-5 of the normals and the 1e-6 of cos / sin can move a point."""
     tr, B, N = five(), 2, 200
-    pts = clouds(B, N, 3, device)
+    pts = uniform_clouds(B, N, 3, device)
     got = run(pts, tr).cpu().numpy()
     for b in range(B):
         want, big = ar.reference_cloud(pts[b].cpu().numpy(), ref_chain(tr), SEED, STEP, b)
@@ -165,7 +159,7 @@ def test_points_agree_with_the_restatements_own_draws(device):
 @pytest.mark.parametrize("N", [65, 1025])
 def test_a_cloud_does_not_depend_on_the_batch(device, N):
     tr = five()
-    pts = clouds(3, N, 5, device)
+    pts = uniform_clouds(3, N, 5, device)
     whole = run(pts, tr)
     for b in range(3):
         assert same_bits(run(pts[:b + 1].contiguous(), tr)[b], whole[b])
@@ -179,7 +173,7 @@ def test_a_cloud_does_not_depend_on_the_batch(device, N):
 def test_lengths(device, fill):
     tr, N = five(), 1025
     lens = [1, 700, 1025]
-    pts = clouds(3, N, 6, device)
+    pts = uniform_clouds(3, N, 6, device)
     padded = pts.clone()
     for b, n in enumerate(lens):
         padded[b, n:] = fill                                 # flip's maximum must not see it
@@ -201,7 +195,7 @@ def test_lengths(device, fill):
 @pytest.mark.parametrize("N,M,K", [(2048, 1200, 1024), (65, 65, 65), (300, 65, 65)])
 def test_fused_gather_and_subset(device, N, M, K):
     tr, B = five(), 3
-    pts = clouds(B, N, 7, device)
+    pts = uniform_clouds(B, N, 7, device)
     g = torch.Generator().manual_seed(N + M)
     idx = torch.stack([torch.randperm(N, generator=g)[:M] for _ in range(B)]).to(device)
     sel = torch.randperm(M, generator=g)[:K].to(device)
@@ -223,7 +217,7 @@ def test_fused_gather_and_subset(device, N, M, K):
 @pytest.mark.parametrize("N", [65, 8192])
 def test_in_place_equals_out_of_place(device, N):
     tr = five()
-    pts = clouds(2, N, 8, device)
+    pts = uniform_clouds(2, N, 8, device)
     want = run(pts, tr)
     work = pts.clone()
     assert run(work, tr, out=work) is work and same_bits(work, want)
@@ -244,7 +238,7 @@ def test_in_place_equals_out_of_place(device, N):
 
 def test_compose_runs_foreign_callables_between_launches(device):
     t = T()
-    pts = clouds(2, 100, 9, device)
+    pts = uniform_clouds(2, 100, 9, device)
     calls = []
 
     def foreign(pc):
@@ -270,7 +264,7 @@ def test_compose_runs_foreign_callables_between_launches(device):
 def test_state(device):
     t = T()
     tr = five()
-    pts = clouds(2, 130, 10, device)
+    pts = uniform_clouds(2, 130, 10, device)
     st = t.AugmentState(1234, device)
     assert (st.seed, st.step) == (1234, 0)
     a = t.sample_and_augment(pts, tr, state=st)
@@ -310,7 +304,7 @@ def test_captured_graph_draws_anew_at_every_replay(device):
     t = T()
     tr = five()
     model = small_model(device)
-    pts = clouds(2, 128, 11, device)
+    pts = uniform_clouds(2, 128, 11, device)
     st = t.AugmentState(77, device)
     aug = torch.empty_like(pts)
 
@@ -368,7 +362,7 @@ def test_vote_logits_equals_the_loop_written_out(device):
     from si_mamba_amd import grouping, vote_logits
     t = T()
     model = small_model(device)
-    raw = clouds(2, 300, 12, device)
+    raw = uniform_clouds(2, 300, 12, device)
     npoints, point_all, times = 128, 160, 3
     st = t.AugmentState(5, device)
     torch.manual_seed(21)
@@ -405,7 +399,7 @@ def test_pointnet2_stand_in(device):
     try:
         install_shim(pointnet2=True)
         from pointnet2_ops import pointnet2_utils
-        pts = clouds(2, 300, 13, device)
+        pts = uniform_clouds(2, 300, 13, device)
         fps = pointnet2_utils.furthest_point_sample(pts, 40)
         assert fps.dtype == torch.int32 and fps.shape == (2, 40)
         assert torch.equal(fps.long(), grouping.sample_farthest_points(pts, 40)[1])

@@ -19,6 +19,7 @@ import sys
 import pytest
 import torch
 
+from helpers import clouds_from, max_scaled, relerr
 from si_mamba_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -37,20 +38,11 @@ SEED = {(3, 65, 64): 1, (2, 1000, 1300): 2, (1, 8192, 4099): 3, (300, 96, 80): 4
 BIG = 1 << 30
 
 
-def clouds(B, N, gen):
-    """N(0,1) points, centred and scaled into the unit ball per cloud like tests/compose.py::clouds (a single point
-    cannot be centred: it is scaled only)."""
-    p = torch.randn(B, N, 3, generator=gen)
-    if N > 1:
-        p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
-
-
 @functools.lru_cache(maxsize=None)
 def random_pair(shape):
     pairs, n, m = shape
     gen = torch.Generator().manual_seed(SEED[shape])
-    return clouds(pairs, n, gen), clouds(pairs, m, gen)
+    return clouds_from(pairs, n, gen), clouds_from(pairs, m, gen)
 
 
 def nearest64(q, t, chunk=512):
@@ -111,10 +103,6 @@ def run_fwd(x, y, device, queries=0):
 @functools.lru_cache(maxsize=None)
 def random_result(shape, device, queries=0):
     return run_fwd(*random_pair(shape), device, queries)
-
-
-def relerr(got, want):
-    return float(((got.double() - want).abs() / want.abs().clamp_min(1e-300)).max())
 
 
 # ---- 1, 2: random clouds ---------------------------------------------------------------------------------------------
@@ -184,10 +172,6 @@ def grad_case(shape, device):
     assert not undecided(ref, 1).any() and not undecided(ref, 2).any(), "seed has a near-tie: pick another"
     w = torch.rand(shape[0], generator=torch.Generator().manual_seed(100 + SEED[shape])) + 0.5
     return x, y, w, autograd64(x, y, w, device)
-
-
-def max_scaled(got, want):
-    return float((got.double().cpu() - want).abs().max() / want.abs().max())
 
 
 @pytest.mark.parametrize("which", ["x", "y", "both"])
@@ -362,7 +346,7 @@ def test_shim_takes_whole_clouds(device):
         from pytorch3d.loss import chamfer_distance
         gen = torch.Generator().manual_seed(21)
         for n, m in ((1024, 1024), (2048, 1024)):
-            a, b = clouds(4, n, gen), clouds(4, m, gen)
+            a, b = clouds_from(4, n, gen), clouds_from(4, m, gen)
             want = reference(a, b)["dist"]
             ad, bd = a.to(device), b.to(device)
             loss, normals = chamfer_distance(ad, bd)
@@ -390,7 +374,7 @@ def small_mae(device, **over):
 
 def test_mae_trains_with_patches_of_96_points(device):
     m = small_mae(device, group_size=96).train()
-    pts = clouds(2, 512, torch.Generator().manual_seed(31)).to(device)
+    pts = clouds_from(2, 512, torch.Generator().manual_seed(31)).to(device)
     _lib.counters.clear()
     loss = m(pts)
     assert _lib.counters.get("chamfer_large") == 1 and "chamfer_small" not in _lib.counters
@@ -406,7 +390,7 @@ def test_mae_reconstruct(device):
     from si_mamba_amd.mae import chamfer_distance
     m = small_mae(device).eval()
     B, N, G, M = 2, 512, 16, 32
-    pts = clouds(B, N, torch.Generator().manual_seed(32)).to(device)
+    pts = clouds_from(B, N, torch.Generator().manual_seed(32)).to(device)
     with torch.no_grad():
         _, center, _ = m.group_divider(pts)
         mask = m.MAE_encoder._mask_center_rand(center, generator=torch.Generator().manual_seed(33))

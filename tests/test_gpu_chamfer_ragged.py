@@ -30,6 +30,7 @@ import sys
 import pytest
 import torch
 
+from helpers import clouds_from, max_scaled, relerr
 from si_mamba_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -57,20 +58,12 @@ BIG = 1 << 30
 REDUCTIONS = {"mean": 0, "sum": 1, None: 2}
 
 
-def clouds(B, N, gen):
-    """N(0,1) points, centred and scaled into the unit ball per cloud (a single point is scaled only)."""
-    p = torch.randn(B, N, 3, generator=gen)
-    if N > 1:
-        p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
-
-
 @functools.lru_cache(maxsize=None)
 def case(k):
     """(x (P,n,3), y (P,m,3), nx (P,), ny (P,)) of CASES[k]: generator seeds 11 .. 15."""
     P, n, m = CASES[k]
     gen = torch.Generator().manual_seed(11 + k)
-    x, y = clouds(P, n, gen), clouds(P, m, gen)
+    x, y = clouds_from(P, n, gen), clouds_from(P, m, gen)
     nx, ny = torch.tensor(LENGTHS[k][0]), torch.tensor(LENGTHS[k][1])
     assert nx.shape == ny.shape == (P,) and 1 <= int(nx.min()) and int(nx.max()) <= n and int(ny.max()) <= m
     return x, y, nx, ny
@@ -135,14 +128,6 @@ def undecided(ref, k):
     """Real queries whose best and second-best float64 distances are within relative 1e-5 (one target: inf)."""
     best, second = ref[f"d{k}"], ref[f"second{k}"]
     return torch.isfinite(second) & ~((second - best) > 1e-5 * second)
-
-
-def relerr(got, want):
-    return float(((got.double() - want).abs() / want.abs().clamp_min(1e-300)).max())
-
-
-def max_scaled(got, want):
-    return float((got.double().cpu() - want).abs().max() / want.abs().max())
 
 
 # ---- the entry points ----------------------------------------------------------------------------------------------
@@ -270,7 +255,7 @@ def test_full_and_absent_lengths_equal_the_plain_entry_points(k, device):
 def test_default_python_call_keeps_its_routes(device):
     from si_mamba_amd.mae import chamfer_distance
     gen = torch.Generator().manual_seed(7)
-    x, y = clouds(5, 32, gen).to(device), clouds(5, 32, gen).to(device)
+    x, y = clouds_from(5, 32, gen).to(device), clouds_from(5, 32, gen).to(device)
     _lib.counters.clear()
     small = chamfer_distance(x.clone().requires_grad_(), y)
     assert _lib.counters == {"chamfer_small": 1}
@@ -356,7 +341,7 @@ def grad_case(k):
     """Clouds of a seed without near-ties, GRAD_SHAPES[k] at GRAD_LENGTHS[k]."""
     P, n, m = GRAD_SHAPES[k]
     gen = torch.Generator().manual_seed(GRAD_SEED[k])
-    x, y = clouds(P, n, gen), clouds(P, m, gen)
+    x, y = clouds_from(P, n, gen), clouds_from(P, m, gen)
     nx, ny = torch.tensor(GRAD_LENGTHS[k][0]), torch.tensor(GRAD_LENGTHS[k][1])
     for norm in (1, 2):
         ref = reference(x, y, nx, ny, norm)

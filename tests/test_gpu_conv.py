@@ -3,14 +3,10 @@ import pytest
 import torch
 
 from conftest import load_golden
+from helpers import nerr
 from oracle import scan_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 @pytest.mark.parametrize("name", ["conv_cfg1", "conv_odd"])

@@ -4,16 +4,11 @@ and PointMamba with the option on against a CPU composition, against the compose
 import pytest
 import torch
 
+from helpers import clouds, nerr
 from oracle import scan_ref
 from test_cross_merge_abi import eigvecs_and_order, restated_merge_expand
 
 pytestmark = pytest.mark.gpu
-
-
-def nerr(a, b):
-    """The project's metric: max |got - want| / max(1, max |want|)."""
-    a, b = a.detach().float().cpu(), b.detach().float().cpu()
-    return float((a - b).abs().max() / max(1.0, float(b.abs().max())))
 
 
 def _raw(x, gather_idx, scatter_idx):
@@ -98,18 +93,11 @@ def _config(**over):
                           k_top_eigenvectors=K, knn_graph=6, drop_path=0., drop_out=0., drop_out_in_block=0., **over)
 
 
-def _clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
-
-
 @pytest.fixture(scope="module")
 def small(device):
     from si_mamba_amd.point_mamba import PointMamba
     torch.manual_seed(0)
-    return PointMamba(_config(add_after_layer=True)).to(device), _clouds(2, 128, 3).to(device)
+    return PointMamba(_config(add_after_layer=True)).to(device), clouds(2, 128, 3).to(device)
 
 
 def test_model_matches_cpu_composition(small, device):
@@ -188,7 +176,7 @@ def test_no_effect_when_off(device):
     from si_mamba_amd.block import MixerModel
     from si_mamba_amd.point_mamba import PointMamba
     torch.manual_seed(0)
-    pts = _clouds(2, 128, 3).to(device)
+    pts = clouds(2, 128, 3).to(device)
     m = PointMamba(_config(add_after_layer=False)).to(device).eval()
     assert type(m.blocks) is MixerModel
     before = _lib.counters.get("cross_merge", 0)
@@ -202,7 +190,7 @@ def test_graphed_forward_replays_the_eager_result(small, device):
     from si_mamba_amd.graphed import GraphedForward
     m, pts = small
     m.eval()
-    other = _clouds(2, 128, 4).to(device)
+    other = clouds(2, 128, 4).to(device)
     with torch.no_grad():
         before = _lib.counters.get("cross_merge", 0)
         ea, eb = m(pts).clone(), m(other).clone()

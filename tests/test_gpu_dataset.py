@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import dataset_ref as dr
+from helpers import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -26,14 +27,6 @@ RULES = {"first": dr.FIRST, "permute": dr.PERMUTE, "choice": dr.CHOICE}
 def D():
     from si_mamba_amd import data
     return data
-
-
-def bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def cloud_lengths(S, K, ragged):

@@ -3,7 +3,8 @@ csrc/fps.hip) and the models at 256 / 512 patches (the large-G spectral kernels)
 import pytest
 import torch
 
-from compose import clouds, sast_gather_by_order
+from compose import sast_gather_by_order
+from helpers import clouds
 from oracle import fps_ref, scan_ref, spectral_ref as sr
 
 pytestmark = pytest.mark.gpu

@@ -7,6 +7,7 @@ import copy
 import pytest
 import torch
 
+from helpers import clouds, nerr
 from oracle import scan_ref
 from si_mamba_amd import _lib
 
@@ -14,11 +15,6 @@ pytestmark = pytest.mark.gpu
 
 TOL = {torch.float32: 1e-3, torch.bfloat16: 1e-2}
 GRADS = ("u", "delta", "A", "B", "C", "D", "z", "delta_bias")
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 @pytest.fixture
@@ -236,13 +232,6 @@ def test_default_route_unchanged(device):
 
 
 # ---- end to end: one seeded training step, twice from the same state ---------------------------------------------
-def _clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
-
-
 def _state(m, opt):
     return copy.deepcopy(m.state_dict()), copy.deepcopy(opt.state_dict())
 
@@ -282,7 +271,7 @@ def test_pointmamba_finetune_step_bitwise(amp, torch_deterministic, device):
     torch.manual_seed(0)
     m = PointMamba(default_config()).to(device).train()
     opt = torch.optim.AdamW(m.parameters(), lr=5e-4, weight_decay=0.05)
-    pts = _clouds(64, 1024, 1).to(device)
+    pts = clouds(64, 1024, 1).to(device)
     gt = torch.randint(0, 15, (64,), generator=torch.Generator().manual_seed(2)).to(device)
     c0 = dict(_lib.counters)
     res = _twice(m, opt, lambda: m.get_loss_acc(m(pts), gt)[0], amp)
@@ -296,7 +285,7 @@ def test_mae_step_bitwise(torch_deterministic, device):
     torch.manual_seed(0)
     m = Point_MAE_Mamba(default_mae_config(trans_dim=96, encoder_dims=96, depth=2, decoder_depth=1)).to(device).train()
     opt = torch.optim.AdamW(m.parameters(), lr=1e-3, weight_decay=0.05)
-    pts = _clouds(4, 1024, 2).to(device)
+    pts = clouds(4, 1024, 2).to(device)
     _assert_same_step(_twice(m, opt, lambda: m(pts), True))
 
 
@@ -305,7 +294,7 @@ def test_partseg_step_bitwise(torch_deterministic, device):
     torch.manual_seed(0)
     m = PartSegMamba(50).to(device).train()
     B, N = 2, 2048
-    pts = _clouds(B, N, 5).transpose(1, 2).contiguous().to(device)
+    pts = clouds(B, N, 5).transpose(1, 2).contiguous().to(device)
     label = torch.nn.functional.one_hot(torch.tensor([0, 3]), 16).float().to(device)
     target = torch.randint(0, 50, (B, N), generator=torch.Generator().manual_seed(3)).to(device)
     opt = torch.optim.AdamW(m.parameters(), lr=1e-3, weight_decay=0.05)
@@ -326,7 +315,7 @@ def test_graphed_train_step_deterministic(torch_deterministic, device):
         if isinstance(mod, torch.nn.Dropout):
             mod.p = 0.0
     opt = torch.optim.AdamW(m.parameters(), lr=1e-3, capturable=True)
-    pts = _clouds(8, 256, 20).to(device)
+    pts = clouds(8, 256, 20).to(device)
     gt = torch.randint(0, 5, (8,), generator=torch.Generator().manual_seed(0)).to(device)
     c0 = dict(_lib.counters)
     step = GraphedTrainStep(lambda p, y: m.get_loss_acc(m(p), y)[0], opt, (pts, gt), clip=10.0, warmup=3)

@@ -10,7 +10,7 @@ import copy
 import pytest
 import torch
 
-from compose import nerr
+from helpers import nerr
 from si_mamba_amd import _lib
 from si_mamba_amd.block import MixerModel
 

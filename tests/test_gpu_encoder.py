@@ -5,12 +5,9 @@ import pytest
 import torch
 import torch.nn as nn
 
+from helpers import peak_err
+
 pytestmark = pytest.mark.gpu
-
-
-def nerr(a, b):
-    a, b = a.detach().float().cpu(), b.detach().float().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
 @pytest.mark.parametrize("rows,C,group,dtype", [(4096, 128, 0, torch.float32), (2048, 512, 32, torch.float32),
@@ -37,22 +34,22 @@ def test_bn_relu_matches_torch(rows, C, group, dtype, device):
     yb = torch.relu(bn_b(xe))
     yb.backward(dy.float())
     tol = 1e-4 if dtype == torch.float32 else 2e-2
-    assert nerr(ya, yb) < tol
-    assert nerr(xa.grad, xb.grad) < tol * 5
-    assert nerr(bn_a.weight.grad, bn_b.weight.grad) < tol * 5
-    assert nerr(bn_a.bias.grad, bn_b.bias.grad) < tol * 5
+    assert peak_err(ya, yb) < tol
+    assert peak_err(xa.grad, xb.grad) < tol * 5
+    assert peak_err(bn_a.weight.grad, bn_b.weight.grad) < tol * 5
+    assert peak_err(bn_a.bias.grad, bn_b.bias.grad) < tol * 5
     if gt is not None:
-        assert nerr(ga.grad, gb.grad) < tol * 5
+        assert peak_err(ga.grad, gb.grad) < tol * 5
     # buffers follow nn.BatchNorm1d
-    assert nerr(bn_a.running_mean, bn_b.running_mean) < tol
-    assert nerr(bn_a.running_var, bn_b.running_var) < tol
+    assert peak_err(bn_a.running_mean, bn_b.running_mean) < tol
+    assert peak_err(bn_a.running_var, bn_b.running_var) < tol
     assert int(bn_a.num_batches_tracked) == int(bn_b.num_batches_tracked) == 1
     # eval mode uses them
     bn_a.eval(); bn_b.eval()
     with torch.no_grad():
         ye = bn_relu_fn(x, bn_a, gterm=gt, group=group)
         yr = torch.relu(bn_b(x.float() if gt is None else x.float() + gt.repeat_interleave(group, dim=0)))
-    assert nerr(ye, yr) < tol
+    assert peak_err(ye, yr) < tol
 
 
 def test_bn_relu_large_mean_is_stable(device):
@@ -63,7 +60,7 @@ def test_bn_relu_large_mean_is_stable(device):
     bn = nn.BatchNorm1d(64).to(device)
     y = bn_relu_fn(x, bn)
     ref = torch.relu(torch.nn.functional.batch_norm(x.double(), None, None, bn.weight.double(), bn.bias.double(), True))
-    assert nerr(y, ref) < 2e-3
+    assert peak_err(y, ref) < 2e-3
 
 
 @pytest.mark.parametrize("groups,n,C,dtype", [(512, 32, 256, torch.float32), (100, 17, 384, torch.float32),
@@ -97,19 +94,19 @@ def test_encoder_fused_matches_composed(train, device):
     dy = torch.randn(4, 16, 384, device=device)
     pa, pb = pts.clone().requires_grad_(True), pts.clone().requires_grad_(True)
     ya, yb = enc_a(pa), enc_b(pb)
-    assert nerr(ya, yb) < 1e-4
+    assert peak_err(ya, yb) < 1e-4
     if train:
         ya.backward(dy); yb.backward(dy)
-        assert nerr(pa.grad, pb.grad) < 2e-3
+        assert peak_err(pa.grad, pb.grad) < 2e-3
         for (k, a), (_, b) in zip(enc_a.named_parameters(), enc_b.named_parameters()):
             if k in ("first_conv.0.bias", "first_conv.3.bias", "second_conv.0.bias"):
                 # biases in front of a BatchNorm (first_conv.3.bias reaches BN2 through both concat halves): the
                 # gradient is exactly 0, both sides hold rounding noise
                 assert float(a.grad.abs().max()) < 1e-4 and float(b.grad.abs().max()) < 1e-4, k
             else:
-                assert nerr(a.grad, b.grad) < 2e-3, k
+                assert peak_err(a.grad, b.grad) < 2e-3, k
         for (k, a), (_, b) in zip(enc_a.named_buffers(), enc_b.named_buffers()):
-            assert nerr(a, b) < 1e-4, k
+            assert peak_err(a, b) < 1e-4, k
 
 
 def test_bn_relu_argument_errors(device):
@@ -158,7 +155,7 @@ def test_token_linear_matches_linear(rows, cin, cout, bias, dtype, device):
     assert torch.equal(grads["ours"][0], grads["torch"][0])                    # the forward IS F.linear
     for got, want in zip(grads["ours"][1:], grads["torch"][1:]):
         if want is not None:
-            assert got.dtype == want.dtype and nerr(got, want) < tol
+            assert got.dtype == want.dtype and peak_err(got, want) < tol
     if dtype == torch.float32:                                                 # and against float64 for the weight gradient
         want = dy.double().t() @ x.double()
-        assert nerr(grads["ours"][2], want) < 1e-5
+        assert peak_err(grads["ours"][2], want) < 1e-5

@@ -5,17 +5,14 @@ the reference is built from the bf16-rounded operands."""
 import pytest
 import torch
 
+from helpers import peak_err
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 32, 64, 8),          # one column block, one patch
           (3, 32, 128, 384),       # two column blocks, G no multiple of any slab
           (70, 17, 64, 12),        # several slabs with a remainder, n no power of two
           (64, 32, 512, 384)]      # the workload's channel counts
-
-
-def nerr(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
 def _operands(G, n, cin, cout, dtype, seed=0):
@@ -71,12 +68,12 @@ def test_parity_with_float64(G, n, cin, cout, dtype, device):
         yr.gather(1, first).squeeze(1).backward(dy.double())
         rdx, rdw, rdb = xr.grad, wr.grad, br.grad
     tol = 5e-4 if dtype == torch.float32 else 1e-1
-    print(f"nerr out {nerr(out, ro):.3e} dx {nerr(dx, rdx):.3e} dw {nerr(dw, rdw):.3e} db {nerr(db, rdb):.3e}")
-    assert nerr(out, ro) < (1e-4 if dtype == torch.float32 else 2e-2)
+    print(f"nerr out {peak_err(out, ro):.3e} dx {peak_err(dx, rdx):.3e} dw {peak_err(dw, rdw):.3e} db {peak_err(db, rdb):.3e}")
+    assert peak_err(out, ro) < (1e-4 if dtype == torch.float32 else 2e-2)
     assert dx.dtype == dtype and dw.dtype == dtype and db.dtype == dtype
-    assert nerr(dx, rdx) < tol
-    assert nerr(dw, rdw) < tol
-    assert nerr(db, rdb) < tol
+    assert peak_err(dx, rdx) < tol
+    assert peak_err(dw, rdw) < tol
+    assert peak_err(db, rdb) < tol
 
 
 def _planted(G, n, cin, cout, rows):
@@ -112,12 +109,12 @@ def test_edge_cases_ties_and_empty_rows(device):
     for r in range(G * n):
         if r not in (3, n, n + 1):
             assert torch.equal(dx[r], torch.zeros(cin)), r      # exact zeros, the tied row 5 included
-    assert nerr(dx, want) < 5e-4
+    assert peak_err(dx, want) < 5e-4
     wantw = torch.zeros(cout, cin, dtype=torch.float64)
     for c in range(cout):
         wantw[c] = dy[0, c].double() * x[3].double() + dy[1, c].double() * x[n + c % 2].double()
-    assert nerr(dw, wantw) < 5e-4
-    assert nerr(db, dy.double().sum(0)) < 5e-4
+    assert peak_err(dw, wantw) < 5e-4
+    assert peak_err(db, dy.double().sum(0)) < 5e-4
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -148,7 +145,7 @@ def test_autocast_rounds_like_the_dense_route(dtype, device):
     tol = 5e-4 if dtype == torch.float32 else 1e-1
     for got, want in zip(res[0][1:], res[1][1:]):
         assert got.dtype == want.dtype == torch.float32
-        assert nerr(got, want) < tol
+        assert peak_err(got, want) < tol
 
 
 def test_fallback_outside_the_shape_limits(device):

@@ -16,8 +16,9 @@ import pytest
 import torch
 import torch.nn as nn
 
-from graphed_dp_rank import (CLIP, LR, cls_batches, cls_loss, clouds, eager_step, graphed_against_eager, no_dropout,
+from graphed_dp_rank import (CLIP, LR, cls_batches, cls_loss, eager_step, graphed_against_eager, no_dropout,
                              small_pointmamba, worst_difference)
+from helpers import clouds, max_scaled
 
 pytestmark = pytest.mark.gpu
 
@@ -170,8 +171,6 @@ def test_recapture_takes_the_new_momentum(device, one_rank_group):
         torch.cuda.synchronize()
         return bn.running_mean.clone(), bn.running_var.clone()
 
-    def nerr(a, b):
-        return float((a - b).abs().max() / b.abs().max())
     eager_old = stats_after(lambda: cls_loss(m)(pts, gt))
     bn.momentum = 0.5
     eager_new = stats_after(lambda: cls_loss(m)(pts, gt))
@@ -180,10 +179,11 @@ def test_recapture_takes_the_new_momentum(device, one_rank_group):
     fresh = stats_after(lambda: step(pts, gt))
     # 1e-4: the bar tests/test_gpu_sync_bn.py holds running statistics to
     for i in range(2):
-        print(nerr(stale[i], eager_old[i]), nerr(fresh[i], eager_new[i]), nerr(eager_old[i], eager_new[i]))
-        assert nerr(eager_old[i], eager_new[i]) > 1e-2
-        assert nerr(stale[i], eager_old[i]) < 1e-4
-        assert nerr(fresh[i], eager_new[i]) < 1e-4
+        print(max_scaled(stale[i], eager_old[i]), max_scaled(fresh[i], eager_new[i]),
+              max_scaled(eager_old[i], eager_new[i]))
+        assert max_scaled(eager_old[i], eager_new[i]) > 1e-2
+        assert max_scaled(stale[i], eager_old[i]) < 1e-4
+        assert max_scaled(fresh[i], eager_new[i]) < 1e-4
 
 
 def test_released_gradients_are_refused(device, one_rank_group):

@@ -4,12 +4,9 @@ GEMM route it replaces."""
 import pytest
 import torch
 
+from helpers import nerr
+
 pytestmark = pytest.mark.gpu
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 def _call(x, w, device, dtype=torch.bfloat16):

@@ -5,21 +5,10 @@ boolean-mask / loop code on the same weights, mask and orders."""
 import pytest
 import torch
 
+from helpers import clouds, nerr, peak_err
 from oracle import mae_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def nerr(a, b):
-    a, b = a.detach().float().cpu(), b.detach().float().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
-
-
-def _clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
 
 
 @pytest.mark.parametrize("pairs,n,m", [(1000, 32, 32), (7, 64, 17), (33, 5, 64), (1, 1, 1)])
@@ -35,8 +24,8 @@ def test_chamfer_matches_oracle(pairs, n, m, device):
     xb = x.clone().requires_grad_(True)
     db = mae_ref.chamfer_distance(xb, y)
     (db * w).sum().backward()
-    assert nerr(da, db) < 1e-5
-    assert nerr(xa.grad, xb.grad) < 1e-5
+    assert peak_err(da, db) < 1e-5
+    assert peak_err(xa.grad, xb.grad) < 1e-5
 
 
 def test_chamfer_golden_fixture(device):
@@ -47,8 +36,8 @@ def test_chamfer_golden_fixture(device):
     x = torch.from_numpy(z["pred"]).to(device).requires_grad_(True)
     d = chamfer_distance(x, torch.from_numpy(z["gt"]).to(device))
     (d * torch.from_numpy(z["wsum"]).to(device)).sum().backward()
-    assert nerr(d, torch.from_numpy(z["dist"])) < 1e-5
-    assert nerr(x.grad, torch.from_numpy(z["grad_pred"])) < 1e-5
+    assert peak_err(d, torch.from_numpy(z["dist"])) < 1e-5
+    assert peak_err(x.grad, torch.from_numpy(z["grad_pred"])) < 1e-5
 
 
 @pytest.mark.parametrize("full,dtype", [(False, torch.float32), (True, torch.float32), (True, torch.bfloat16)])
@@ -57,7 +46,7 @@ def test_mae_forward_matches_oracle_flow(full, dtype, device):
     L = 208, decoder L = 512) in fp32 and under bf16 autocast as tools/runner_pretrain.py:243 runs it.  Tolerances on
     the normalised error: 2e-3 fp32 (two stacked models), 1e-2 bf16 against the oracle restated with the autocast
     roundings (tests/compose.py)."""
-    from compose import nerr as nerr1, oracle_stack
+    from compose import oracle_stack
     from si_mamba_amd.mae import Point_MAE_Mamba, default_mae_config
     torch.manual_seed(0)
     if full:
@@ -73,7 +62,7 @@ def test_mae_forward_matches_oracle_flow(full, dtype, device):
     m = Point_MAE_Mamba(cfg).to(device).eval()
     with torch.no_grad():
         m.mask_token.normal_(std=0.5)
-    pts = _clouds(B, N, 7)
+    pts = clouds(B, N, 7)
     gen = torch.Generator().manual_seed(11)
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
         nb, center, _ = m.group_divider(pts.to(device))
@@ -101,7 +90,7 @@ def test_mae_forward_matches_oracle_flow(full, dtype, device):
         want_loss, rebuild, gt, x_full = mae_ref.decoder_flow(
             x_vis, cpu.mask_token, masks, mask_tensor, pos_full, snb, cfg.transformer_config.mask_ratio, G,
             lambda x, p: cpu.MAE_decoder.norm(dec_blocks(x, p.to(pos.dtype))), inc)
-    scale = lambda a, b: nerr1(a.float(), b.float())
+    scale = lambda a, b: nerr(a.float(), b.float())
     assert scale(parts["x_vis"], x_vis) < tol
     assert torch.equal(parts["pos_full"].float().cpu(), pos_full) and torch.equal(parts["pos_mask"].float().cpu(), pos_mask)
     assert scale(parts["x_full"], x_full) < tol
@@ -116,7 +105,7 @@ def test_mae_train_step_reference_sizes(device):
     from si_mamba_amd.mae import Point_MAE_Mamba, default_mae_config
     torch.manual_seed(0)
     m = Point_MAE_Mamba(default_mae_config()).to(device).train()
-    pts = _clouds(8, 1024, 2).to(device)
+    pts = clouds(8, 1024, 2).to(device)
     with torch.autocast("cuda", dtype=torch.bfloat16):
         loss, parts = m(pts, return_parts=True)
     assert parts["x_vis"].shape == (8, 208, 384) and parts["x_full"].shape == (8, 512, 384)
@@ -144,13 +133,12 @@ def test_config4_full_batch_step(device):
     Tolerances: 1e-3 in fp32.  Under autocast the two sides of each comparison run DIFFERENT library GEMM kernels (the
     batch size selects them) and every block rounds its activations to bf16, so they are held to 3e-2 -- the bf16
     arithmetic itself is held to the oracle at 1e-2 by test_mae_forward_matches_oracle_flow."""
-    from compose import nerr as nerr1
     from si_mamba_amd.mae import Point_MAE_Mamba, default_mae_config
     torch.manual_seed(0)
     cfg = default_mae_config()                      # DropPath / dropout at the config's rates: off in eval mode
     m = Point_MAE_Mamba(cfg).to(device).eval()
     B, G = 64, cfg.num_group
-    pts = _clouds(B, 1024, 41).to(device)
+    pts = clouds(B, 1024, 41).to(device)
     nm = int(cfg.transformer_config.mask_ratio * G)
     gen = torch.Generator().manual_seed(6)
     mask = (torch.rand(B, G, generator=gen).argsort(dim=1).argsort(dim=1) < nm).to(device)      # nm True per row
@@ -161,7 +149,7 @@ def test_config4_full_batch_step(device):
             _, two = m(pts[:2], mask=mask[:2], return_parts=True)
         assert full["x_vis"].shape == (B, 208, 384) and full["x_full"].shape == (B, 512, 384)
         per = full["rebuild"].shape[0] // B
-        assert nerr1(full["rebuild"][:2 * per].float(), two["rebuild"].float()) < tol, on
+        assert nerr(full["rebuild"][:2 * per].float(), two["rebuild"].float()) < tol, on
 
         def grads(sl):
             m.zero_grad(set_to_none=True)
@@ -173,7 +161,7 @@ def test_config4_full_batch_step(device):
         g_all, g_a, g_b = grads(slice(0, 64)), grads(slice(0, 32)), grads(slice(32, 64))
         assert set(g_all) == set(g_a) == set(g_b) and len(g_all) > 100
         for k in g_all:
-            assert nerr1(g_all[k], g_a[k] + g_b[k]) < tol, (on, k)
+            assert nerr(g_all[k], g_a[k] + g_b[k]) < tol, (on, k)
     m.train()
     m.zero_grad(set_to_none=True)
     with torch.autocast("cuda", dtype=torch.bfloat16):

@@ -4,6 +4,7 @@ import torch
 
 from compose import mixer_scaled_bound_violations
 from conftest import load_golden
+from helpers import nerr
 from oracle import scan_ref
 
 pytestmark = pytest.mark.gpu
@@ -11,11 +12,6 @@ pytestmark = pytest.mark.gpu
 # the three mixer gradients of order 1e-3 .. 1e-2, where ``nerr`` (floor of 1) passes anything: also held to the
 # scale-aware bound of tests/test_gpu_mixer_routes.py
 SMALL_GRADS = ("dt_proj.weight", "dt_proj.bias", "A_log")
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 def test_mamba_block_cfg1_golden(device):

@@ -25,9 +25,9 @@ import os
 import pytest
 import torch
 
-from compose import nerr
 import guarded_alloc
 from guarded_alloc import LARGE, SENTINEL, ZERO, guarded, place, same_bits
+from helpers import nerr
 from si_mamba_amd import _lib
 
 pytestmark = pytest.mark.gpu

@@ -8,7 +8,7 @@ backward on the whole batch, asserts -- through _lib.counters -- that the run to
 passing row cannot be one that silently fell back), and compares the output, the input gradient and every parameter
 gradient with oracle.scan_ref.MambaRef computed in float64 from the same weights and inputs.
 
-Metric and bounds (tests/compose.scaled_err: max and RMS error on the tensor's OWN scale, no floor of 1 -- three of
+Metric and bounds (tests/helpers.scaled_err: max and RMS error on the tensor's OWN scale, no floor of 1 -- three of
 the gradients are of order 1e-3 .. 1e-2, where the suite's ``nerr`` passes anything).  The bounds come from the
 reference side only, never from what the device returned:
 
@@ -32,7 +32,8 @@ import os
 import pytest
 import torch
 
-from compose import mixer_oracle_run as _oracle, nerr, scaled_err
+from compose import mixer_oracle_run as _oracle
+from helpers import nerr, scaled_err
 from oracle import scan_ref
 from si_mamba_amd import _lib
 

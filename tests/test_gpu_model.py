@@ -2,16 +2,10 @@
 import pytest
 import torch
 
+from helpers import clouds, nerr
 from oracle import fps_ref, scan_ref, spectral_ref as sr
 
 pytestmark = pytest.mark.gpu
-
-
-def _clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
 
 
 def test_pointmamba_small_forward_matches_oracle_composition(device):
@@ -21,7 +15,7 @@ def test_pointmamba_small_forward_matches_oracle_composition(device):
     cfg = default_config(trans_dim=64, encoder_dims=64, depth=2, num_group=32, group_size=16, drop_path=0.,
                          knn_graph=8)
     m = PointMamba(cfg).to(device).eval()
-    pts = _clouds(3, 256, 0)
+    pts = clouds(3, 256, 0)
     with torch.no_grad():
         got = m(pts.to(device)).cpu()
         nb, center, _ = m.group_divider(pts.to(device))
@@ -51,7 +45,7 @@ def test_pointmamba_full_config_train_step(device):
     torch.manual_seed(0)
     m = PointMamba(default_config()).to(device).train()
     opt = torch.optim.AdamW(m.parameters(), lr=5e-4, weight_decay=0.05)
-    pts = _clouds(8, 1024, 1).to(device)
+    pts = clouds(8, 1024, 1).to(device)
     gt = torch.randint(0, 15, (8,), device=device)
     logits = m(pts)
     assert logits.shape == (8, 15)
@@ -68,7 +62,7 @@ def test_farthest_point_sampling_matches_oracle(shape, device):
     accumulated without FMA, first maximum on ties)."""
     from si_mamba_amd import grouping
     B, N, K = shape
-    pts = _clouds(B, N, seed=N + K)
+    pts = clouds(B, N, seed=N + K)
     centers, idx = grouping.sample_farthest_points(pts.to(device), K)
     wc, widx = fps_ref.sample_farthest_points(pts, K)
     assert torch.equal(idx.cpu(), widx)
@@ -82,7 +76,7 @@ def test_graphed_inference_matches_eager(device):
     from si_mamba_amd.point_mamba import PointMamba, default_config
     torch.manual_seed(0)
     m = PointMamba(default_config(depth=4, drop_path=0.)).to(device).eval()
-    a, b = _clouds(4, 1024, 2).to(device), _clouds(4, 1024, 3).to(device)
+    a, b = clouds(4, 1024, 2).to(device), clouds(4, 1024, 3).to(device)
     with torch.no_grad():
         ea, eb = m(a).clone(), m(b).clone()
     g = GraphedForward(m, a)
@@ -137,7 +131,7 @@ def test_knn_group_matches_exact_neighbours(B, N, G, K, device):
     """Neighbour sets of csrc/knn_group.hip against a float64 brute force (the reference's pytorch3d knn_points,
     return_sorted=False, leaves the order open); output order ascending, ties to the lower index."""
     from si_mamba_amd.grouping import knn_group
-    pts = _clouds(B, N, N + K)
+    pts = clouds(B, N, N + K)
     centers = pts[:, :G].clone()
     idx = knn_group(centers.to(device), pts.to(device), K).cpu()
     d64 = ((centers.double().unsqueeze(2) - pts.double().unsqueeze(1)) ** 2).sum(-1)          # (B,G,N)
@@ -165,7 +159,7 @@ def test_pointmamba_other_orderings_match_oracle_composition(method, device):
                          knn_graph=8, method=method, k_top_eigenvectors=3)
     m = PointMamba(cfg).to(device).eval()
     m.hlt_rand = False
-    pts = _clouds(3, 256, 4)
+    pts = clouds(3, 256, 4)
     with torch.no_grad():
         got = m(pts.to(device)).cpu()
         nb, center, _ = m.group_divider(pts.to(device))
@@ -199,7 +193,7 @@ def test_pytorch3d_shim_call_forms(device):
     si_mamba_amd.install_shim(pytorch3d=True)
     from pytorch3d.loss import chamfer_distance
     from pytorch3d.ops import knn_points, sample_farthest_points
-    xyz = _clouds(2, 512, 9).to(device)
+    xyz = clouds(2, 512, 9).to(device)
     center = sample_farthest_points(points=xyz, K=32)[0]                       # models/point_mamba.py:93-94
     idx = knn_points(center, xyz, K=16, return_sorted=False).idx               # :96-97
     assert center.shape == (2, 32, 3) and idx.shape == (2, 32, 16) and idx.dtype == torch.int64
@@ -229,7 +223,7 @@ def test_graphed_train_step_matches_eager(device):
     # +-lr steps on near-zero gradients, which makes two correct runs drift apart by themselves
     oa = torch.optim.SGD(ma.parameters(), lr=0.002)
     ob = torch.optim.SGD(mb.parameters(), lr=0.002)
-    data = [(_clouds(8, 256, 20 + i).to(device), torch.randint(0, 5, (8,), generator=torch.Generator().manual_seed(i)).to(device))
+    data = [(clouds(8, 256, 20 + i).to(device), torch.randint(0, 5, (8,), generator=torch.Generator().manual_seed(i)).to(device))
             for i in range(7)]
     step = GraphedTrainStep(lambda p, y: ma.get_loss_acc(ma(p), y)[0], oa, data[0], clip=10.0, warmup=3)
     la, lb = [], []
@@ -266,12 +260,12 @@ def test_pointmamba_full_depth_forward_matches_oracle(npoints, device):
     """Configs 2 (1024 points) and 3 (2048 points) architecture at B = 2: FPS + k-NN grouping and the patch encoder on
     the device (covered on their own), then the oracle's graph / eigh / argsort ordering, the oracle's SAST assembly
     and 12 oracle mixers at L = 1024 against the device forward.  fp32, 1e-3 on the normalised error."""
-    from compose import nerr, oracle_stack, sast_gather_by_order
+    from compose import oracle_stack, sast_gather_by_order
     from si_mamba_amd.point_mamba import PointMamba, default_config
     torch.manual_seed(0)
     cfg = default_config(drop_path=0.)
     m = PointMamba(cfg).to(device).eval()
-    pts = _clouds(2, npoints, npoints)
+    pts = clouds(2, npoints, npoints)
     with torch.no_grad():
         got = m(pts.to(device)).cpu()
         nb, center, _ = m.group_divider(pts.to(device))
@@ -300,11 +294,10 @@ def test_config3_full_batch_step(device):
       * with frozen statistics the summed loss is additive over samples, so every parameter gradient of the batch of
         128 equals grad(first 64) + grad(last 64) (exercises the backward's batch reductions at two grid sizes);
       * the training-mode step (batch statistics, DropPath, dropout) gives finite gradients for every parameter."""
-    from compose import nerr
     from si_mamba_amd.point_mamba import PointMamba, default_config
     torch.manual_seed(0)
     m = PointMamba(default_config(drop_path=0.)).to(device).eval()
-    pts = _clouds(128, 2048, 33).to(device)
+    pts = clouds(128, 2048, 33).to(device)
     gt = torch.randint(0, 15, (128,), generator=torch.Generator().manual_seed(5)).to(device)
     with torch.no_grad():
         full = m(pts)
@@ -336,7 +329,7 @@ def test_pointmamba_reference_call_surface(device):
     torch.manual_seed(0)
     cfg = default_config(trans_dim=64, encoder_dims=64, depth=2, num_group=32, group_size=16, drop_path=0., knn_graph=8)
     m = PointMamba(cfg).to(device).eval()
-    pts = _clouds(3, 256, 1).to(device)
+    pts = clouds(3, 256, 1).to(device)
     with torch.no_grad():
         a = m(pts)
         b = m(pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=3)
@@ -362,7 +355,6 @@ def test_first_block_on_distinct_tokens_equals_reference_route(device):
     (models/point_mamba.py:889-898, :982-989 then :247-258): outputs, input gradients and every parameter gradient."""
     import copy
     from si_mamba_amd.block import MixerModel
-    from compose import nerr
     torch.manual_seed(0)
     a = MixerModel(d_model=128, n_layer=2, drop_path=0.).to(device)
     b = copy.deepcopy(a)

@@ -4,12 +4,9 @@ models/block.py:72 then :56-58), and against this package's unfused route (libra
 import pytest
 import torch
 
+from helpers import nerr
+
 pytestmark = pytest.mark.gpu
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 def _case(B, C, L, device, seed, residual=True, rowscale=False, beta=True):

@@ -13,15 +13,11 @@ import pytest
 import torch
 
 from conftest import load_golden
+from helpers import nerr
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ["spectral_g64", "spectral_g128", "spectral_g128_surface"]
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -7,7 +7,7 @@ call has to return exactly that, bit for bit."""
 import pytest
 import torch
 
-from compose import clouds
+from helpers import clouds
 
 pytestmark = pytest.mark.gpu
 

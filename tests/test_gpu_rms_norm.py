@@ -9,15 +9,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import clouds, nerr
 from oracle.scan_ref import selective_scan_ref
 from si_mamba_amd import _lib
 
 pytestmark = pytest.mark.gpu
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 def rms_norm_ref(x, weight, residual=None, eps=1e-6, prenorm=False):
@@ -267,33 +263,26 @@ def test_mixer_model_rms_matches_float64_composition(amp, device):
 
 
 # ---- train steps with rms_norm=True --------------------------------------------------------------------------------------
-def _clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
-
-
 def _step(which, device):
     """-> (model, loss_fn) at small sizes with rms_norm=True"""
     torch.manual_seed(0)
     if which == "pointmamba":
         from si_mamba_amd.point_mamba import PointMamba, default_config
         m = PointMamba(default_config(rms_norm=True, depth=4, num_group=64)).to(device).train()
-        pts = _clouds(8, 1024, 1).to(device)
+        pts = clouds(8, 1024, 1).to(device)
         gt = torch.randint(0, 15, (8,), generator=torch.Generator().manual_seed(2)).to(device)
         return m, lambda: m.get_loss_acc(m(pts), gt)[0]
     if which == "mae":
         from si_mamba_amd.mae import Point_MAE_Mamba, default_mae_config
         m = Point_MAE_Mamba(default_mae_config(rms_norm=True, trans_dim=128, encoder_dims=128, depth=2,
                                                decoder_depth=1)).to(device).train()
-        pts = _clouds(4, 1024, 2).to(device)
+        pts = clouds(4, 1024, 2).to(device)
         return m, lambda: m(pts)
     from si_mamba_amd.seg import PartSegMamba, default_seg_config, get_loss
     m = PartSegMamba(50, default_seg_config(rms_norm=True, trans_dim=128, depth=4, fetch_idx=(1, 2, 3))).to(device)
     m.train()
     B, N = 2, 2048
-    pts = _clouds(B, N, 5).transpose(1, 2).contiguous().to(device)
+    pts = clouds(B, N, 5).transpose(1, 2).contiguous().to(device)
     label = F.one_hot(torch.tensor([0, 3]), 16).float().to(device)
     target = torch.randint(0, 50, (B, N), generator=torch.Generator().manual_seed(3)).to(device)
     crit = get_loss()

@@ -9,17 +9,13 @@ import pytest
 import torch
 
 from conftest import load_golden
+from helpers import nerr
 from oracle import scan_ref
 from oracle.gen_golden import scan_inputs
 
 pytestmark = pytest.mark.gpu
 
 TOL = {torch.float32: 1e-3, torch.bfloat16: 1e-2}
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 def run_hip(inp, device, dtype=torch.float32, grads=True):

@@ -9,14 +9,10 @@ its accumulators (float atomics in both paths) to 1e-5.
 import pytest
 import torch
 
+from helpers import nerr
 from oracle import scan_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 def _operands(B, D, L, R, dtype, device, seed=0):

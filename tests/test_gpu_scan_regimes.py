@@ -8,7 +8,7 @@ own scale (scan_regimes.channel_err): a channel whose step is 1e-6 is not hidden
 
 Metric, per tensor: out, last_state, du, ddelta, dz -- max over channels of max |got - want| / max |want| of that
 channel; dA -- the same per row; dD, ddelta_bias -- per element on the tensor's maximum (the worst single-element
-relative error is recorded too); dB, dC -- the tensor's own scale (they are sums over channels).  compose.scaled_err
+relative error is recorded too); dB, dC -- the tensor's own scale (they are sums over channels).  helpers.scaled_err
 (max and RMS over the whole tensor) is bounded the same way, and the suite's nerr bars (1e-3 fp32, 1e-2 bf16) hold too.
 
 Bound, from the reference side only: E_dev <= F * max(E_ref, 2^-23), E_ref being the same metric for the CPU oracle of
@@ -29,7 +29,7 @@ import pytest
 import torch
 
 import scan_regimes as sr
-from compose import nerr
+from helpers import nerr
 from si_mamba_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -61,7 +61,7 @@ def _dump(rows):
     def short(errs):
         return {k: [float(f"{e[w]:.3g}") for w in ("chan", "max", "rms", "elem") if w in e] for k, e in errs.items()}
     head = {"metric": "[chan, max, rms(, elem)] per tensor.  chan: max over channels of max |got - want| / max |want| of "
-                      "the channel (dD, ddelta_bias, dB, dC: on the tensor's maximum); max / rms: compose.scaled_err; elem: "
+                      "the channel (dD, ddelta_bias, dB, dC: on the tensor's maximum); max / rms: helpers.scaled_err; elem: "
                       "worst single-element relative error; all against the float64 selective_scan_ref.  E_ref: the fp32 "
                       "/ bf16 CPU oracle, E_dev: the device"}
     lines = [json.dumps(tag) + ": " + json.dumps({"counters": r["counters"], "E_ref": short(r["E_ref"]),

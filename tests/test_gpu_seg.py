@@ -4,21 +4,10 @@ the oracle composition (CPU mixers + reference-layout head) on the same weights.
 import pytest
 import torch
 
+from helpers import clouds, nerr, peak_err
 from oracle import scan_ref, seg_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def nerr(a, b):
-    a, b = a.detach().float().cpu(), b.detach().float().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
-
-
-def _clouds(B, N, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(B, N, 3, generator=g)
-    p = p - p.mean(1, keepdim=True)
-    return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
 
 
 @pytest.mark.parametrize("B,N,S,C,dtype", [(2, 512, 64, 64, torch.float32), (3, 300, 37, 1152, torch.float32),
@@ -26,7 +15,7 @@ def _clouds(B, N, seed):
                                            (2, 512, 64, 64, torch.bfloat16)])
 def test_three_nn_interpolate_matches_oracle(B, N, S, C, dtype, device):
     from si_mamba_amd.interp import three_interpolate, three_nn
-    pts = _clouds(B, N, N + S)
+    pts = clouds(B, N, N + S)
     g = torch.Generator().manual_seed(C)
     centres = pts[:, torch.randperm(N, generator=g)[:S]].clone()       # centres coincide with points (as after FPS)
     if S >= 8:
@@ -43,11 +32,11 @@ def test_three_nn_interpolate_matches_oracle(B, N, S, C, dtype, device):
         assert bool(same[clear].all())
     f = feats.to(device).to(dtype).requires_grad_(True)
     out = three_interpolate(f, idx, w)
-    assert nerr(out, want) < (2e-4 if dtype == torch.float32 else 2e-2)
+    assert peak_err(out, want) < (2e-4 if dtype == torch.float32 else 2e-2)
     out.backward(dout.to(device).to(dtype))
     fr = feats.to(dtype).float().clone().requires_grad_(True)
     (seg_ref.index_points(fr, idx.cpu().long()) * w.cpu().view(B, N, 3, 1)).sum(2).backward(dout.to(dtype).float())
-    assert nerr(f.grad, fr.grad) < (2e-4 if dtype == torch.float32 else 2e-2)
+    assert peak_err(f.grad, fr.grad) < (2e-4 if dtype == torch.float32 else 2e-2)
 
 
 def test_interp_golden_fixture(device):
@@ -57,7 +46,7 @@ def test_interp_golden_fixture(device):
     z = np.load(os.path.join(os.path.dirname(__file__), "golden", "interp_seg.npz"))
     idx, w = three_nn(torch.from_numpy(z["xyz1"]).to(device), torch.from_numpy(z["xyz2"]).to(device))
     out = three_interpolate(torch.from_numpy(z["feats"]).to(device), idx, w)
-    assert nerr(out, torch.from_numpy(z["out"])) < 2e-4
+    assert peak_err(out, torch.from_numpy(z["out"])) < 2e-4
     assert float((idx.cpu().sort(-1)[0] == torch.from_numpy(z["idx"]).sort(-1)[0]).float().mean()) > 0.99
 
 
@@ -70,7 +59,7 @@ def test_partseg_forward_matches_oracle_composition(method, device):
     m = PartSegMamba(50, cfg).to(device).eval()
     m.hlt_rand = False
     B, N = 2, 512
-    pts = _clouds(B, N, 3).transpose(1, 2).contiguous()                 # (B, 3, N)
+    pts = clouds(B, N, 3).transpose(1, 2).contiguous()                 # (B, 3, N)
     label = torch.zeros(B, 16); label[0, 3] = 1; label[1, 7] = 1
     with torch.no_grad():
         got = m(pts.to(device), label.to(device)).cpu()
@@ -97,7 +86,7 @@ def test_partseg_train_step_reference_sizes(device):
     torch.manual_seed(0)
     m = PartSegMamba(50).to(device).train()
     B, N = 4, 2048
-    pts = _clouds(B, N, 5).transpose(1, 2).contiguous().to(device)
+    pts = clouds(B, N, 5).transpose(1, 2).contiguous().to(device)
     label = torch.nn.functional.one_hot(torch.tensor([0, 3, 7, 15]), 16).float().to(device)
     target = torch.randint(0, 50, (B, N), device=device)
     out = m(pts, label)
@@ -115,14 +104,14 @@ def test_partseg_full_depth_bf16_matches_oracle(method, npts, device):
     of 32; HLT -> L = 256, SAST -> L = 1024) on 2048 points under bf16 autocast, against the oracle restated with the
     autocast roundings (tests/compose.py, oracle/seg_ref.py).  1e-2 on the normalised error of the per-point
     log-probabilities (north_star's bf16 tolerance)."""
-    from compose import nerr as nerr1, oracle_stack
+    from compose import oracle_stack
     from si_mamba_amd.seg import PartSegMamba, default_seg_config
     torch.manual_seed(0)
     cfg = default_seg_config(drop_path=0., drop_path_rate=0., method=method)
     m = PartSegMamba(50, cfg).to(device).eval()
     m.hlt_rand = False
     B, N = 2, npts
-    pts = _clouds(B, N, 3).transpose(1, 2).contiguous()                 # (B, 3, N)
+    pts = clouds(B, N, 3).transpose(1, 2).contiguous()                 # (B, 3, N)
     label = torch.zeros(B, 16); label[0, 3] = 1; label[1, 7] = 1
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         got = m(pts.to(device), label.to(device)).float().cpu()
@@ -135,7 +124,7 @@ def test_partseg_full_depth_bf16_matches_oracle(method, npts, device):
         feats = oracle_stack(cpu.blocks, 384, torch.bfloat16, taps=cpu.blocks.fetch_idx)(x, spos)
         want = seg_ref.seg_head(cpu, pts, label, scenter.float(), feats, io_dtype=torch.bfloat16)
     assert got.shape == (B, N, 50)
-    assert nerr1(got, want) < 1e-2
+    assert nerr(got, want) < 1e-2
     # and the class decisions agree wherever the oracle's top-2 margin is not a near-tie
     top2 = want.topk(2, dim=-1)[0]
     clear = (top2[..., 0] - top2[..., 1]) > 0.1
@@ -149,14 +138,13 @@ def test_config5_full_batch_step(method, device):
     The same size-independent properties as configs 3 and 4: sub-batch log-probabilities equal those of the small run,
     gradient additivity over the batch with frozen statistics, finite training-mode bf16 step; 1e-3 in fp32, 3e-2
     between two bf16 runs through different library GEMM kernels (test_config4_full_batch_step explains)."""
-    from compose import nerr as nerr1
     from si_mamba_amd.seg import PartSegMamba, default_seg_config, get_loss
     torch.manual_seed(0)
     cfg = default_seg_config(method=method)
     m = PartSegMamba(50, cfg).to(device).eval()
     m.hlt_rand = False                                   # the reference's torch.rand tie-break: off for comparisons
     B, N = 16, 2048
-    pts = _clouds(B, N, 9).transpose(1, 2).contiguous().to(device)
+    pts = clouds(B, N, 9).transpose(1, 2).contiguous().to(device)
     label = torch.nn.functional.one_hot(torch.arange(B) % 16, 16).float().to(device)
     target = torch.randint(0, 50, (B, N), generator=torch.Generator().manual_seed(3)).to(device)
     for on, tol in ((False, 1e-3), (True, 3e-2)):
@@ -165,7 +153,7 @@ def test_config5_full_batch_step(method, device):
             full = m(pts, label)
             two = m(pts[:2], label[:2])
         assert full.shape == (B, N, 50)
-        assert nerr1(full[:2].float(), two.float()) < tol, on
+        assert nerr(full[:2].float(), two.float()) < tol, on
 
         def grads(sl):
             m.zero_grad(set_to_none=True)
@@ -177,7 +165,7 @@ def test_config5_full_batch_step(method, device):
         g_all, g_a, g_b = grads(slice(0, 16)), grads(slice(0, 8)), grads(slice(8, 16))
         assert set(g_all) == set(g_a) == set(g_b) and len(g_all) > 100
         for k in g_all:
-            assert nerr1(g_all[k], g_a[k] + g_b[k]) < tol, (on, k)
+            assert nerr(g_all[k], g_a[k] + g_b[k]) < tol, (on, k)
     m.train()
     m.zero_grad(set_to_none=True)
     with torch.autocast("cuda", dtype=torch.bfloat16):

@@ -21,14 +21,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from helpers import peak_err
+
 pytestmark = pytest.mark.gpu
 
 EPS, MOM = 1e-5, 0.1
-
-
-def nerr(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
 def _bounds(shards):
@@ -113,11 +110,11 @@ def test_staged_shards_match_float64(shards, C, group, dtype, device):
     want = oracle(x, gt, group, dy, w, b)
     torch.cuda.synchronize()
     tol, gtol = (1e-4, 5e-4) if dtype == torch.float32 else (2e-2, 1e-1)
-    errs = dict(y=nerr(got["y"], want["y"]), running_mean=nerr(rm, want["rm"]), running_var=nerr(rv, want["rv"]),
-                dx=nerr(got["dx"], want["dx"]), dweight=nerr(got["dweight"], want["dweight"]),
-                dbias=nerr(got["dbias"], want["dbias"]))
+    errs = dict(y=peak_err(got["y"], want["y"]), running_mean=peak_err(rm, want["rm"]), running_var=peak_err(rv, want["rv"]),
+                dx=peak_err(got["dx"], want["dx"]), dweight=peak_err(got["dweight"], want["dweight"]),
+                dbias=peak_err(got["dbias"], want["dbias"]))
     if gt is not None:
-        errs["dgterm"] = nerr(got["dgt"], want["dgt"])
+        errs["dgterm"] = peak_err(got["dgt"], want["dgt"])
     print(shards, C, group, dtype, errs)
     assert float(got["count"]) == sum(shards)
     for k in ("y", "running_mean", "running_var"):
@@ -130,8 +127,8 @@ def test_staged_shards_match_float64(shards, C, group, dtype, device):
     if dtype == torch.float32:
         n0 = shards[0]
         wrong = (1 - MOM) * 1.0 + MOM * want["var"] * n0 / (n0 - 1)
-        assert nerr(wrong, want["rv"]) > tol
-        assert nerr(rv, wrong) > tol
+        assert peak_err(wrong, want["rv"]) > tol
+        assert peak_err(rv, wrong) > tol
 
 
 def test_merge_is_bitwise_repeatable_and_in_rank_order(device):
@@ -152,10 +149,10 @@ def test_merge_is_bitwise_repeatable_and_in_rank_order(device):
     xs = x[a:z].double()
     blk = got["gathered"][2]
     assert torch.equal(blk[0], torch.full((C,), 300.0, device=device, dtype=torch.float64))
-    assert nerr(blk[1], xs.mean(0)) < 1e-6
+    assert peak_err(blk[1], xs.mean(0)) < 1e-6
     # fp32 partial sums: at most ~130 sequential additions per channel (2^-24 each), about a first row that may lie
     # a few standard deviations off the mean (S2 up to ~10x M2)
-    assert nerr(blk[2], ((xs - xs.mean(0)) ** 2).sum(0)) < 1e-4
+    assert peak_err(blk[2], ((xs - xs.mean(0)) ** 2).sum(0)) < 1e-4
 
 
 @pytest.mark.parametrize("rows,C,group", [(300, 8, 0), (1024, 512, 32)])
@@ -178,7 +175,7 @@ def test_one_rank_equals_the_monolithic_forward(rows, C, group, device):
     torch.testing.assert_close(got["invstd"], invstd, rtol=1e-6, atol=0)
     torch.testing.assert_close(rm, rm1, rtol=1e-6, atol=0)
     torch.testing.assert_close(rv, rv1, rtol=1e-6, atol=0)
-    assert nerr(got["y"], y) < 1e-6
+    assert peak_err(got["y"], y) < 1e-6
 
 
 @pytest.mark.parametrize("rows,C,group,ld,dtype", [
@@ -241,7 +238,7 @@ def test_large_mean_is_stable_across_shards(device):
     w, b = torch.ones(64, device=device), torch.zeros(64, device=device)
     got = run_staged(x, None, 0, torch.zeros_like(x), w, b, (4096, 4096))
     ref = torch.relu(F.batch_norm(x.double(), None, None, w.double(), b.double(), True))
-    err = nerr(got["y"], ref)
+    err = peak_err(got["y"], ref)
     print("large mean, two shards:", err)
     assert err < 2e-3
 
@@ -279,14 +276,14 @@ def test_function_at_world_size_one(C, group, momentum, device, one_rank_group):
             y.backward(dy)
         res.append((y, xa.grad, None if ga is None else ga.grad))
     (ya, dxa, dga), (yb, dxb, dgb) = res
-    assert nerr(ya, yb) < 1e-4
-    assert nerr(dxa, dxb) < 5e-4
+    assert peak_err(ya, yb) < 1e-4
+    assert peak_err(dxa, dxb) < 5e-4
     if gt is not None:
-        assert nerr(dga, dgb) < 5e-4
-    assert nerr(bn_a.weight.grad, bn_b.weight.grad) < 5e-4
-    assert nerr(bn_a.bias.grad, bn_b.bias.grad) < 5e-4
-    assert nerr(bn_a.running_mean, bn_b.running_mean) < 1e-4
-    assert nerr(bn_a.running_var, bn_b.running_var) < 1e-4
+        assert peak_err(dga, dgb) < 5e-4
+    assert peak_err(bn_a.weight.grad, bn_b.weight.grad) < 5e-4
+    assert peak_err(bn_a.bias.grad, bn_b.bias.grad) < 5e-4
+    assert peak_err(bn_a.running_mean, bn_b.running_mean) < 1e-4
+    assert peak_err(bn_a.running_var, bn_b.running_var) < 1e-4
     assert int(bn_a.num_batches_tracked) == int(bn_b.num_batches_tracked) == 2
 
 
@@ -313,7 +310,7 @@ def test_dispatch_of_sync_batchnorm(device, one_rank_group, monkeypatch):
     monkeypatch.setattr(eo, "_sync_world", lambda bn: 2)     # what a two-rank group answers
     ya = eo.bn_relu_fn(x, bn_a, gterm=gt, group=group)
     assert called == [1]
-    assert nerr(ya, eo.bn_relu_fn(x, bn_b, gterm=gt, group=group)) < 1e-4
+    assert peak_err(ya, eo.bn_relu_fn(x, bn_b, gterm=gt, group=group)) < 1e-4
 
 
 def test_capture_is_refused(device, one_rank_group, monkeypatch):
@@ -330,17 +327,17 @@ def test_capture_is_refused(device, one_rank_group, monkeypatch):
 
 def _compare_encoders(ya, pa_grad, grads_a, bufs_a, enc_b, yb, pb_grad):
     """The bars of test_encoder_fused_matches_composed."""
-    assert nerr(ya, yb) < 1e-4
-    assert nerr(pa_grad, pb_grad) < 2e-3
+    assert peak_err(ya, yb) < 1e-4
+    assert peak_err(pa_grad, pb_grad) < 2e-3
     for k, b in enc_b.named_parameters():
         a = grads_a[k]
         if k in ("first_conv.0.bias", "first_conv.3.bias", "second_conv.0.bias"):
             # biases in front of a BatchNorm: the gradient is exactly 0, both sides hold rounding noise
             assert float(a.abs().max()) < 1e-4 and float(b.grad.abs().max()) < 1e-4, k
         else:
-            assert nerr(a, b.grad) < 2e-3, k
+            assert peak_err(a, b.grad) < 2e-3, k
     for k, b in enc_b.named_buffers():
-        assert nerr(bufs_a[k], b) < 1e-4, k
+        assert peak_err(bufs_a[k], b) < 1e-4, k
 
 
 def test_encoder_with_sync_batchnorm(device, one_rank_group, monkeypatch):

@@ -4,12 +4,9 @@ north-star bar, the observed error is at the fp32 rounding level), and against t
 import pytest
 import torch
 
+from helpers import nerr
+
 pytestmark = pytest.mark.gpu
-
-
-def nerr(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return ((got - want).abs().max() / max(1.0, want.abs().max().item())).item()
 
 
 # the last four walk several tiles per workgroup (> 512 tiles): D = 64 has two steps per tile (the four-step lookahead

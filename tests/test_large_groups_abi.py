@@ -6,20 +6,16 @@ import re
 
 import pytest
 
+from abi_tables import header_code
 from conftest import ROOT
 from si_mamba_amd import _lib
 
 NEW = ("simamba_laplacian_topk_workspace_bytes", "simamba_laplacian_topk_ex")
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "simamba.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 @pytest.mark.parametrize("name", NEW)
 def test_new_symbols_in_header_binding_and_library(name):
-    assert re.search(r"\b" + name + r"\s*\(", _header()), name
+    assert re.search(r"\b" + name + r"\s*\(", header_code()), name
     assert name in _lib.SIGNATURES
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name)
 

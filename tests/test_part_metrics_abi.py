@@ -9,16 +9,14 @@ import pytest
 import torch
 
 import part_metrics_ref as pr
+from abi_tables import E_DTYPE, E_NULLPTR, E_SHAPE, P, check_rows
 from conftest import GOLDEN
 from si_mamba_amd import _lib
-
-P = 1 << 20   # a non-null address that is never dereferenced: every call below ends in validation
 
 ARGS = dict(scores=P, target=P, part_first=P, part_count=P, lengths=None, pred=None, inter=P, uni=P, shape_iou=P,
             correct=P, seen_class=P, correct_class=P, batch=16, n=2048, c=50, io_dtype=_lib.F32, stream=None)
 REQUIRED = ["scores", "target", "part_first", "part_count", "inter", "uni", "shape_iou", "correct", "seen_class",
             "correct_class"]
-E_NULLPTR, E_SHAPE, E_DTYPE = -1, -2, -3
 
 ROWS = [
     (dict(c=0), E_SHAPE), (dict(c=-1), E_SHAPE), (dict(c=257), E_SHAPE), (dict(n=0), E_SHAPE), (dict(n=-4), E_SHAPE),
@@ -37,15 +35,7 @@ ROWS = [
 
 
 def test_return_codes_without_a_device():
-    fn = _lib.load().simamba_part_seg_eval
-    for change, want in ROWS:
-        assert set(change) <= set(ARGS), change
-        assert fn(*{**ARGS, **change}.values()) == want, change
-
-
-def test_abi_version_unchanged():
-    assert _lib.load().simamba_abi_version() == 9
-    assert _lib.ABI_VERSION == 9
+    check_rows("simamba_part_seg_eval", ARGS, ROWS)
 
 
 def _fixture():

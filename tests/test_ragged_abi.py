@@ -7,10 +7,10 @@ import inspect
 import pytest
 import torch
 
+from abi_tables import E_NULLPTR, E_SHAPE
 from si_mamba_amd import _lib, grouping
 
 NEW = ["simamba_farthest_point_sample_ex", "simamba_knn_group_ex"]
-E_NULLPTR, E_SHAPE = -1, -2
 
 
 def test_symbols_exported_and_bound():

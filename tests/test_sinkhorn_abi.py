@@ -4,11 +4,9 @@ and did not grow a host implementation."""
 import pytest
 import torch
 
+from abi_tables import E_ALIGN, E_NULLPTR, E_SHAPE, E_VARIANT, E_WORKSPACE, OFF, P, check_rows
 from si_mamba_amd import _lib
 
-P = 1 << 20   # a 16-byte aligned, non-null address that is never dereferenced: every call below ends in validation
-OFF = P + 4
-E_NULLPTR, E_SHAPE, E_WORKSPACE, E_ALIGN, E_VARIANT = -1, -2, -6, -8, -9
 BIG = 1 << 40
 
 FWD = dict(x=P, y=P, xlen=None, ylen=None, div=P, ot_xy=P, merr=P, f_xy=P, g_xy=P, g_xx=P, g_yy=P, f_yy=P, pairs=2,
@@ -59,10 +57,7 @@ BWD_ROWS = SHAPE_ROWS + [
 @pytest.mark.parametrize("name,base,rows", [("simamba_sinkhorn_fwd", FWD, FWD_ROWS),
                                             ("simamba_sinkhorn_bwd", BWD, BWD_ROWS)])
 def test_return_codes_without_a_device(name, base, rows):
-    fn = getattr(_lib.load(), name)
-    for change, want in rows:
-        assert set(change) <= set(base), change
-        assert fn(*{**base, **change}.values()) == want, (name, change)
+    check_rows(name, base, rows)
 
 
 def test_workspace_bytes():
@@ -76,17 +71,11 @@ def test_workspace_bytes():
     for bad in [(0, 100, 70, 1), (2, 0, 70, 1), (2, 100, 8193, 1), (2, 100, 70, 2), (1 << 40, 100, 70, 1)]:
         assert q(*bad) == 0, bad
     # the calls compare against the query: one byte short is refused, and the backward needs 4 * pairs bytes
-    fwd, bwd = _lib.load().simamba_sinkhorn_fwd, _lib.load().simamba_sinkhorn_bwd
     need = q(2, 100, 70, 1)
-    assert fwd(*{**FWD, "workspace": P, "workspace_bytes": need - 1}.values()) == E_WORKSPACE
-    assert fwd(*{**FWD, "workspace": OFF, "workspace_bytes": need}.values()) == E_ALIGN
-    assert bwd(*{**BWD, "workspace": P, "workspace_bytes": 7}.values()) == E_WORKSPACE
-    assert bwd(*{**BWD, "workspace": OFF, "workspace_bytes": 8}.values()) == E_ALIGN
-
-
-def test_abi_version_unchanged():
-    assert _lib.load().simamba_abi_version() == 9
-    assert _lib.ABI_VERSION == 9
+    check_rows("simamba_sinkhorn_fwd", FWD, [(dict(workspace=P, workspace_bytes=need - 1), E_WORKSPACE),
+                                             (dict(workspace=OFF, workspace_bytes=need), E_ALIGN)])
+    check_rows("simamba_sinkhorn_bwd", BWD, [(dict(workspace=P, workspace_bytes=7), E_WORKSPACE),
+                                             (dict(workspace=OFF, workspace_bytes=8), E_ALIGN)])
 
 
 def test_python_route_refuses_cpu_tensors():

@@ -1,15 +1,13 @@
 """CPU: the two SVM entry points (csrc/svm.hip) validate their arguments before touching a device -- shape errors in
-front of null pointers -- the ABI version is unchanged, and the Python route checks its arguments first and then refuses
+front of null pointers -- and the Python route checks its arguments first and then refuses
 CPU tensors."""
 import ctypes
 
 import pytest
 import torch
 
-from si_mamba_amd import _lib
+from abi_tables import E_NULLPTR, E_SHAPE, P, check_rows
 
-P = 1 << 20   # a non-null address that is never dereferenced: every call below ends in validation
-E_NULLPTR, E_SHAPE = -1, -2
 NAN = float("nan")
 
 
@@ -69,22 +67,11 @@ VOTE_ROWS = [
 
 
 def test_fit_return_codes_without_a_device():
-    fn = _lib.load().simamba_svm_ovo_fit
-    for change, want in FIT_ROWS:
-        assert set(change) <= set(FIT), change
-        assert fn(*{**FIT, **change}.values()) == want, change
+    check_rows("simamba_svm_ovo_fit", FIT, FIT_ROWS)
 
 
 def test_vote_return_codes_without_a_device():
-    fn = _lib.load().simamba_svm_ovo_vote
-    for change, want in VOTE_ROWS:
-        assert set(change) <= set(VOTE), change
-        assert fn(*{**VOTE, **change}.values()) == want, change
-
-
-def test_abi_version_unchanged():
-    assert _lib.load().simamba_abi_version() == 9
-    assert _lib.ABI_VERSION == 9
+    check_rows("simamba_svm_ovo_vote", VOTE, VOTE_ROWS)
 
 
 def _xy(n=12, d=4, nc=3, dtype=torch.float32):
