@@ -23,6 +23,15 @@ Parity status (see DESIGN.md "Oracle"):
     orders, index maps, block data flow: bit for bit; eigenpairs: bit for bit on the LAPACK configuration that
     generated them, 3e-6 otherwise); tests/test_gpu_pinned.py and tests/test_gpu_spectral.py hold the HIP path to
     the same files.  The mixer INSIDE those blocks is still this package's restatement (previous item).
+  * segmentation head (3-NN interpolation, PointNetFeaturePropagation, MixerModelForSegmentation taps, the per-point
+    head), the patch Encoder, the MAE masking / token layout, the seven point-cloud transforms and part-segmentation
+    scoring: **pinned to the reference's own code** by the same recipe (tests/golden/ref_seg_interp, ref_seg_fp,
+    ref_seg_head, ref_encoder, ref_mae_flow, ref_transforms, ref_part_metrics; each float fixture holds a float32 and
+    a float64 run and the former's error against the latter, which sets the tests' bounds).
+    tests/test_oracle_pinned_heads.py holds seg_ref / mae_ref / tests/augment_ref.py / tests/part_metrics_ref.py to
+    them, tests/test_gpu_pinned.py the HIP path.  Still unpinned: scan and conv arithmetic (first item), FPS and k-NN
+    (pytorch3d), Chamfer (pytorch3d), the bf16 autocast roundings of the head, and the order in which CUDA's sort
+    returns tied centres.
   * state-dict contract: pinned by the parameter table in the reference's
     ``logs/finetuned_hardest.log:100-426`` (tests/golden/param_table_*.json).
 """

@@ -8,7 +8,14 @@ TEST INFRASTRUCTURE (see oracle/__init__.py).  Follows models/point_mamba.py
   pytorch3d.loss.chamfer_distance (absent wheel; published semantics: squared L2 nearest neighbour, mean over
   points, both directions summed, batch_reduction=None)        called at :3203
 with the reference's own tensor operations (matmul with one-hot permutations, x[bool_mask], index assignment in
-Python loops).  The mixers are passed in as callables.  No reference fixtures exist: parity unpinned.
+Python loops).  The mixers are passed in as callables.
+
+Pinned to the reference's own code: oracle/pin_from_reference.py extracts _mask_center_rand / _mask_center_block, the
+``orders`` branch (:2453-2538) and the restore loop with the final mask and the ground-truth selection (:3139-3202) and
+runs them on index-coded tokens; tests/test_oracle_pinned_heads.py holds ``encoder_flow`` / ``restore_tokens`` to the
+resulting index maps bit for bit (tests/golden/ref_mae_flow.npz, k = 4: the reference hard-codes ``cnt = 4`` at :3174
+where ``restore_tokens`` takes the number of orderings).  Not pinned: ``chamfer_distance`` (pytorch3d is absent; the
+published semantics are restated) and the mixers' arithmetic (oracle/scan_ref.py).
 """
 from __future__ import annotations
 

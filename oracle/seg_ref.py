@@ -5,8 +5,16 @@ TEST INFRASTRUCTURE (see oracle/__init__.py).  Follows
                                                PointNetFeaturePropagation.forward :277-311
   part_segmentation/models/pt_mamba.py         MixerModelForSegmentation.forward :390-416,
                                                get_model.forward :631-787 (everything after the token ordering)
-in the reference's own channels-first (B, C, N) layout and op sequence, on plain torch ops.  The reference holds
-no fixtures for these functions: parity unpinned, but every call below is the one the reference itself makes.
+in the reference's own channels-first (B, C, N) layout and op sequence, on plain torch ops.
+
+Pinned to the reference's own code: oracle/pin_from_reference.py runs pointnet2_utils.PointNetFeaturePropagation (imported
+whole), MixerModelForSegmentation over pt_mamba.py's own Block / create_block, and the head statements :768-787, in
+float32 and float64, and tests/test_oracle_pinned_heads.py holds every function below to those runs
+(tests/golden/ref_seg_interp / ref_seg_fp / ref_seg_head): neighbours and fp32 values bit for bit, gradients and
+running statistics within 8 x the reference's own fp32 error.  Not pinned: which copy of a repeated centre the
+reference's ``sort`` returns (implementation-defined; its CPU run on a model sequence does NOT return the lowest index,
+``three_nn_interpolate`` does), the order CUDA's sort would give, and the bf16 roundings of
+``_autocast_ops`` (CUDA autocast cannot run where the fixtures are made).
 """
 from __future__ import annotations
 
@@ -37,8 +45,9 @@ def index_points(points, idx):
 
 def three_nn_interpolate(xyz1, xyz2, points2):
     """:285-297 -- xyz1 (B,N,3), xyz2 (B,S,3), points2 (B,S,D) -> (B,N,D), idx (B,N,3), weight (B,N,3).
-    ``stable=True``: the reference's sort leaves ties (duplicated centres) unspecified; lowest index is the
-    convention of the HIP kernel."""
+    The sort is ``stable=True``: the reference's own ``sort`` leaves ties (the repeated centres of a model sequence)
+    unspecified -- ``sequence.idx32`` of tests/golden/ref_seg_interp.npz shows its CPU run taking other copies than the
+    lowest -- and lowest index is the documented convention of this restatement and of the HIP kernel."""
     B, N, _ = xyz1.shape
     dists = square_distance(xyz1, xyz2)
     dists, idx = dists.sort(dim=-1, stable=True)

@@ -49,6 +49,8 @@ __global__ __launch_bounds__(kNnThreads) void three_nn_kernel(const float* __res
       } else { d2 = d; i2 = s; }
     }
   }
+  // S = 1 is the reference's ``repeat`` branch (pinned: ref_seg_interp.npz, case ``one``).  S = 2 cannot run in the
+  // reference at all (weight.view(B, N, 3, 1) on two columns raises), so that case is this library's own definition.
   if (S < 3) {                                      // fewer than three centres: repeat the last one with weight 0
     if (S < 2) { i1 = i0; d1 = 3.0e38f; }
     i2 = i1; d2 = 3.0e38f;

@@ -180,7 +180,12 @@ class PartSegMamba(nn.Module):
         tokens = self.encoder(neighborhood)
         pos = self.pos_embed(center)
         x, spos, scenter = self.order_tokens(tokens, pos, center, spec())
-        feats = self.blocks(x, spos)
+        return self.head(pts, cls_label, scenter, self.blocks(x, spos))
+
+    def head(self, pts, cls_label, scenter, feats):
+        """reference :768-787, everything after the block stack: pts (B, N, 3), cls_label (B, 16), scenter (B, L, 3) the
+        centres in sequence order, feats the taps (B, L, C) each -> (B, N, cls_dim) log-probabilities."""
+        B, N, _ = pts.shape
         feats = torch.cat([self.norm(f) for f in feats], dim=-1)                # (B, L, 1152)
         x_max = feats.max(dim=1)[0]
         x_avg = feats.mean(dim=1)

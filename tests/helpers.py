@@ -52,6 +52,15 @@ def relerr(got, want):
     return float(((got - want).abs() / want.abs().clamp_min(1e-300)).max())
 
 
+def pinned_bound(ref32_err, cap):
+    """The bound of an assertion against a reference-pinned fixture: 8 x ``ref32_err`` (the reference's own fp32 run
+    against its float64 run under the assertion's metric; three bits for another summation order and split-K partials),
+    never above ``cap`` (what the op's older tests allow).  Floor 8 x 2^-24: a recorded ``ref32_err`` is ONE draw of a
+    rounding error -- for a single number such as a gradient norm it can lie far below fp32's resolution by chance -- and
+    no fp32 result can be held below half an ulp of its peak."""
+    return min(max(8.0 * float(ref32_err), 8.0 * 2.0 ** -24), cap)
+
+
 # ---- point clouds ----------------------------------------------------------------------------------------------------
 def clouds_from(B, N, gen):
     """N(0,1) points from the generator ``gen``, centred and scaled into the unit ball per cloud (a single point
@@ -68,6 +77,56 @@ def clouds(B, N, seed):
     p = torch.randn(B, N, 3, generator=g)
     p = p - p.mean(1, keepdim=True)
     return p / p.norm(dim=-1).max(dim=1)[0][:, None, None]
+
+
+# ---- parameters from an integer formula ------------------------------------------------------------------------------
+def formula_tensor(shape, salt, scale=1.0, offset=0.0, dtype=torch.float32):
+    """offset + scale * v with v in [-1, 1) on a grid of 1/1024, from int64 arithmetic alone: element i (row-major) hashes
+    to h = mix(i * 2654435761 + salt) mod 2^32 and v = ((h >> 21) - 1024) / 1024.  No generator and no platform is
+    involved, so the fixture recipe (oracle/pin_from_reference.py) and a test build the same weights without the fixture
+    carrying them.  The second multiply-xorshift round breaks the period of 2048 the plain product would have."""
+    n = int(np.prod(shape)) if len(shape) else 1
+    m32 = (1 << 32) - 1
+    h = (torch.arange(n, dtype=torch.int64) * 2654435761 + int(salt)) & m32
+    h = ((h ^ (h >> 15)) * 2246822519) & m32
+    h = h ^ (h >> 13)
+    v = ((h >> 21) - 1024).double() / 1024.0
+    return (offset + scale * v).to(dtype).reshape(shape)
+
+
+def formula_parameters(module, salt, running=False):
+    """Fill a module's parameters (and, with ``running``, its BatchNorm running statistics) from ``formula_tensor``, in
+    named_parameters() order: weights of a layer with fan-in f spread over +-2/sqrt(f), biases over +-0.1, BatchNorm
+    scales over 1 +- 0.25; running means over +-0.2 and running variances over 1 +- 0.5."""
+    with torch.no_grad():
+        for k, (name, p) in enumerate(module.named_parameters()):
+            s = salt + 7919 * k
+            if p.dim() >= 2:
+                fan_in = int(np.prod(p.shape[1:]))
+                p.copy_(formula_tensor(p.shape, s, 2.0 / fan_in ** 0.5))
+            elif name.endswith("weight"):
+                p.copy_(formula_tensor(p.shape, s, 0.25, 1.0))
+            else:
+                p.copy_(formula_tensor(p.shape, s, 0.1))
+        if running:
+            for k, (name, b) in enumerate(module.named_buffers()):
+                s = salt + 104729 * (k + 1)
+                if name.endswith("running_mean"):
+                    b.copy_(formula_tensor(b.shape, s, 0.2))
+                elif name.endswith("running_var"):
+                    b.copy_(formula_tensor(b.shape, s, 0.5, 1.0))
+    return module
+
+
+HEAD_PARTS = ("norm", "label_conv", "propagation_0", "convs1", "bns1", "convs2", "bns2", "convs3")
+
+
+def formula_head(model, salt, running=False):
+    """formula_parameters on each module of a segmentation head by NAME (the reference's get_model and PartSegMamba
+    register them in different orders): part i gets salt + 1000 i."""
+    for i, name in enumerate(HEAD_PARTS):
+        formula_parameters(getattr(model, name), salt + 1000 * i, running=running)
+    return model
 
 
 # ---- bit-for-bit comparison of 32-bit tensors ------------------------------------------------------------------------
