@@ -11,8 +11,18 @@
 // thread per (channel, tap) adds a channel's slots in index order, and the workgroup STORES that partial to the
 // workspace, [batch slice][dim][width] (dw) and [batch slice][dim] (dbias); det_reduce.hip sums over the slices.
 // Algorithmic HBM bytes: fwd 2*B*D*L*s, bwd 3*B*D*L*s (+ (W+1)*D*4 parameters).
+//
+// What is stated once: the tap chain (conv_pre) and the backward of a pack (conv_bwd_pack) in conv_device.h -- the
+// forward here, the conv fused into xdt_proj*.hip and the recompute of both backward kernels go through the former, both
+// backward kernels through the latter; a lane's row / pack ownership (conv_lane) for all three kernels; the launch
+// geometry (conv_geom) for both entry points and the workspace query.  A fusion into the backward hooks into
+// conv_bwd_pack.
+#include <algorithm>
+#include <initializer_list>
+
 #include "host_common.h"
 #include "mfma_device.h"
+#include "conv_device.h"
 #include "det_reduce.h"
 
 namespace simamba {
@@ -57,13 +67,32 @@ __device__ __forceinline__ void load_taps(const ConvArgs& p, int d, float (&w4)[
   bias = p.bias ? p.bias[d] : 0.f;
 }
 
+// What a lane owns.  A row of ppr packs takes ppr lanes, so a workgroup holds rows_per_blk channels (lane -> row drow
+// of the workgroup, channel d) and the lanes of a row walk its packs from pk0 in steps of pstride; a row of 256 packs
+// or more takes the whole workgroup.
+struct ConvLane {
+  int ppr, rows_per_blk, drow, d;
+  // (functions, not fields: worked out where the pack loop starts, which the forward's lanes past the last channel
+  // never reach)
+  __device__ __forceinline__ int pk0() const { return ppr >= kConvThreads ? threadIdx.x : threadIdx.x % ppr; }
+  __device__ __forceinline__ int pstride() const { return ppr >= kConvThreads ? kConvThreads : ppr; }
+};
+
+__device__ __forceinline__ ConvLane conv_lane(const ConvArgs& p) {
+  ConvLane l;
+  l.ppr = p.ppr;
+  l.rows_per_blk = p.ppr >= kConvThreads ? 1 : kConvThreads / p.ppr;
+  l.drow = p.ppr >= kConvThreads ? 0 : threadIdx.x / p.ppr;
+  l.d = blockIdx.x * l.rows_per_blk + l.drow;
+  return l;
+}
+
 template <typename T>
 __global__ __launch_bounds__(kConvThreads) void conv1d_fwd_kernel(ConvArgs p) {
-  const int L = p.seqlen, D = p.dim;
-  const int rows_per_blk = p.ppr >= kConvThreads ? 1 : kConvThreads / p.ppr;
-  const int drow = p.ppr >= kConvThreads ? 0 : threadIdx.x / p.ppr;
-  const int d = blockIdx.x * rows_per_blk + drow;
-  if (d >= D) return;
+  const int L = p.seqlen;
+  const ConvLane ln = conv_lane(p);
+  const int d = ln.d;
+  if (d >= p.dim) return;
   float w4[4], bias;
   load_taps(p, d, w4, bias);
   const T* __restrict__ xg = static_cast<const T*>(p.x);
@@ -74,8 +103,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_fwd_kernel(ConvArgs p) {
   for (int b = b0; b < b1; ++b) {
     const T* row = xg + static_cast<size_t>(b) * p.x_bs + static_cast<size_t>(d) * L;
     T* orow = og + static_cast<size_t>(b) * p.o_bs + static_cast<size_t>(d) * L;
-    for (int pk = (p.ppr >= kConvThreads ? threadIdx.x : threadIdx.x % p.ppr); pk * kPack < L;
-         pk += (p.ppr >= kConvThreads ? kConvThreads : p.ppr)) {
+    for (int pk = ln.pk0(); pk * kPack < L; pk += ln.pstride()) {
       const int t0 = pk * kPack;
       float xp[kPack], xc[kPack], o[kPack];
       load_pack<T>(row, t0 - kPack, L, vec, xp);
@@ -83,9 +111,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_fwd_kernel(ConvArgs p) {
       const float win[7] = {xp[1], xp[2], xp[3], xc[0], xc[1], xc[2], xc[3]};
 #pragma unroll
       for (int i = 0; i < kPack; ++i) {
-        float acc = bias;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = fmaf(w4[j], win[i + j], acc);
+        const float acc = conv_pre(w4, win + i, bias);
         o[i] = p.silu ? acc * sigmoid_f(acc) : acc;
       }
       store_items<T, kPack>(orow + t0, L - t0, vec, o);
@@ -146,17 +172,17 @@ __device__ __forceinline__ void conv_bwd_reduce(const ConvArgs& p, float (&sacc)
   }
 }
 
+// Backward.  The two kernels differ only in how a pack's operands reach registers; the pack's arithmetic is
+// conv_bwd_pack (conv_device.h) and the reduction conv_bwd_reduce in both.
 // P: timesteps per lane and step -- one 16-byte access: 4 for fp32, 8 for bf16 (with 4 the bf16 kernel issued twice the
 // loads and recomputed 7 SiLU derivatives per 4 outputs instead of 11 per 8: 120 us where its bytes take 55)
 template <typename T, int P, bool kDet = false>
 __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_kernel(ConvArgs p) {
   __shared__ float sacc[16][5];   // up to 16 channels per workgroup x (4 taps + bias)
   const int L = p.seqlen, D = p.dim;
-  const int rows_per_blk = p.ppr >= kConvThreads ? 1 : kConvThreads / p.ppr;
-  const int drow = p.ppr >= kConvThreads ? 0 : threadIdx.x / p.ppr;
-  const int d = blockIdx.x * rows_per_blk + drow;
-  const bool dvalid = d < D;
-  const int dc = dvalid ? d : D - 1;
+  const ConvLane ln = conv_lane(p);
+  const bool dvalid = ln.d < D;
+  const int dc = dvalid ? ln.d : D - 1;
   if (threadIdx.x < 16 * 5) (&sacc[0][0])[threadIdx.x] = 0.f;
   __syncthreads();
   float w4[4], bias;
@@ -172,8 +198,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_kernel(ConvArgs p) {
     const size_t roff = (static_cast<size_t>(b) * D + dc) * L;                      // dout: contiguous
     const size_t xoff = static_cast<size_t>(b) * p.x_bs + static_cast<size_t>(dc) * L;
     const size_t doff = static_cast<size_t>(b) * p.o_bs + static_cast<size_t>(dc) * L;
-    for (int pk = (p.ppr >= kConvThreads ? threadIdx.x : threadIdx.x % p.ppr); pk * P < L;
-         pk += (p.ppr >= kConvThreads ? kConvThreads : p.ppr)) {
+    for (int pk = ln.pk0(); pk * P < L; pk += ln.pstride()) {
       const int t0 = pk * P;
       float xp[P], xc[P], xn[P], gc[P], gn[P];
       load_pack<T, P>(xg + xoff, t0 - P, L, vec, xp);
@@ -187,34 +212,12 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_kernel(ConvArgs p) {
       for (int i = 0; i < 3; ++i) { xw[i] = xp[P - 3 + i]; xw[P + 3 + i] = xn[i]; gv[P + i] = gn[i]; }
 #pragma unroll
       for (int i = 0; i < P; ++i) { xw[3 + i] = xc[i]; gv[i] = gc[i]; }
-      float dpre[P + 3];
-#pragma unroll
-      for (int i = 0; i < P + 3; ++i) {
-        float g = gv[i];
-        if (p.silu) {
-          float pre = bias;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) pre = fmaf(w4[j], xw[i + j], pre);
-          float sg = sigmoid_f(pre);
-          g = g * sg * (1.f + pre * (1.f - sg));
-        }
-        dpre[i] = (t0 + i < L) ? g : 0.f;
-      }
       float dx[P];
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = fmaf(w4[j], dpre[i + 3 - j], acc);
-        dx[i] = acc;
-        gb += dpre[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gw[j] = fmaf(dpre[i], xw[i + j], gw[j]);
-      }
+      conv_bwd_pack<P, true>(w4, bias, p.silu, xw, gv, L - t0, dx, gw, gb);
       if (dvalid) store_items<T, P>(dxg + doff + t0, L - t0, vec, dx);
     }
   }
-  conv_bwd_reduce<kDet>(p, sacc, gw, gb, drow, rows_per_blk, dvalid);
+  conv_bwd_reduce<kDet>(p, sacc, gw, gb, ln.drow, ln.rows_per_blk, dvalid);
 }
 
 // ---- the aligned case (every pack one whole 16-byte access, L % P == 0): same arithmetic, software-pipelined ----------
@@ -242,11 +245,9 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_fast_kernel(ConvArgs 
   static_assert(sizeof(T) * P == 16, "one 16-byte access per pack");
   __shared__ float sacc[16][5];
   const int L = p.seqlen, D = p.dim;
-  const int rows_per_blk = p.ppr >= kConvThreads ? 1 : kConvThreads / p.ppr;
-  const int drow = p.ppr >= kConvThreads ? 0 : threadIdx.x / p.ppr;
-  const int d = blockIdx.x * rows_per_blk + drow;
-  const bool dvalid = d < D;
-  const int dc = dvalid ? d : D - 1;
+  const ConvLane ln = conv_lane(p);
+  const bool dvalid = ln.d < D;
+  const int dc = dvalid ? ln.d : D - 1;
   if (threadIdx.x < 16 * 5) (&sacc[0][0])[threadIdx.x] = 0.f;
   __syncthreads();
   float w4[4], bias;
@@ -257,8 +258,7 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_fast_kernel(ConvArgs 
   const int b0 = blockIdx.y * p.bchunk;
   const int nb = min(b0 + p.bchunk, p.batch) - b0;
   const int packs = L / P;
-  const int pk0 = p.ppr >= kConvThreads ? threadIdx.x : threadIdx.x % p.ppr;
-  const int pstride = p.ppr >= kConvThreads ? kConvThreads : p.ppr;
+  const int pk0 = ln.pk0(), pstride = ln.pstride();
   const int npk = pk0 < packs ? (packs - pk0 + pstride - 1) / pstride : 0;
   const int n = nb * npk;
 
@@ -300,55 +300,59 @@ __global__ __launch_bounds__(kConvThreads) void conv1d_bwd_fast_kernel(ConvArgs 
       for (int i = 0; i < 3; ++i) {
         xw[i] = first ? 0.f : xp[P - 3 + i];
         xw[P + 3 + i] = last ? 0.f : xn[i];
-        gv[P + i] = last ? 0.f : gn[i];
+        gv[P + i] = last ? 0.f : gn[i];                         // positions >= L carry gv = 0: no guard below
       }
 #pragma unroll
       for (int i = 0; i < P; ++i) { xw[3 + i] = xc[i]; gv[i] = gc[i]; }
-      float dpre[P + 3];
-#pragma unroll
-      for (int i = 0; i < P + 3; ++i) {
-        float g = gv[i];
-        if (p.silu) {
-          float pre = bias;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) pre = fmaf(w4[j], xw[i + j], pre);
-          float sg = sigmoid_f(pre);
-          g = g * sg * (1.f + pre * (1.f - sg));
-        }
-        dpre[i] = g;                                           // (positions >= L carry gv = 0)
-      }
       float dx[P];
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = fmaf(w4[j], dpre[i + 3 - j], acc);
-        dx[i] = acc;
-        gb += dpre[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gw[j] = fmaf(dpre[i], xw[i + j], gw[j]);
-      }
+      conv_bwd_pack<P, false>(w4, bias, p.silu, xw, gv, 0, dx, gw, gb);
       if (dvalid)
         store_items<T, P>(dxg + static_cast<size_t>(b) * p.o_bs + static_cast<size_t>(dc) * L + t0, P, true, dx);
       cur = nxt;
     }
   }
-  conv_bwd_reduce<kDet>(p, sacc, gw, gb, drow, rows_per_blk, dvalid);
+  conv_bwd_reduce<kDet>(p, sacc, gw, gb, ln.drow, ln.rows_per_blk, dvalid);
 }
 
-static int fill_common(ConvArgs& a, int io_dtype, int pack = kPack) {
-  int packs = (a.seqlen + pack - 1) / pack;
-  int ppr = 16;
-  while (ppr < packs && ppr < kConvThreads) ppr <<= 1;
-  a.ppr = ppr;
-  const int rows_per_blk = ppr >= kConvThreads ? 1 : kConvThreads / ppr;
-  const int dblocks = (a.dim + rows_per_blk - 1) / rows_per_blk;
+// Launch geometry of a problem; `pack` = timesteps per lane and step (kPack forward, io_pack backward).  A batch stride
+// of 0 means contiguous; `ptrs` are the activation pointers whose alignment the 16-byte accesses need (the workspace
+// query, which only counts batch slices, passes none).
+struct ConvGeom {
+  int vec, ppr, bchunk;
+  long long x_bs, o_bs;
+  dim3 grid;       // (channel blocks, batch slices)
+};
+
+static ConvGeom conv_geom(int batch, int dim, int seqlen, int io_dtype, int pack, long long x_bs = 0, long long o_bs = 0,
+                          std::initializer_list<const void*> ptrs = {}) {
+  ConvGeom g;
+  const int packs = (seqlen + pack - 1) / pack;
+  g.ppr = 16;
+  while (g.ppr < packs && g.ppr < kConvThreads) g.ppr <<= 1;
+  const int rows_per_blk = g.ppr >= kConvThreads ? 1 : kConvThreads / g.ppr;
+  const int dblocks = (dim + rows_per_blk - 1) / rows_per_blk;
   // enough workgroups to fill 256 CUs several times over, but long batch slices for the reduction
-  int bchunk = a.batch;
-  while (bchunk > 1 && static_cast<long long>(dblocks) * ((a.batch + bchunk - 1) / bchunk) < 2048) bchunk = (bchunk + 1) / 2;
-  a.bchunk = bchunk;
-  a.vec = (a.seqlen * io_esz(io_dtype)) % 16 == 0;
-  return dblocks;
+  g.bchunk = batch;
+  while (g.bchunk > 1 && static_cast<long long>(dblocks) * ((batch + g.bchunk - 1) / g.bchunk) < 2048)
+    g.bchunk = (g.bchunk + 1) / 2;
+  g.grid = dim3(dblocks, (batch + g.bchunk - 1) / g.bchunk);
+  g.x_bs = x_bs ? x_bs : static_cast<long long>(dim) * seqlen;
+  g.o_bs = o_bs ? o_bs : static_cast<long long>(dim) * seqlen;
+  const long long esz = io_esz(io_dtype);
+  g.vec = (seqlen * esz) % 16 == 0 && (g.x_bs * esz) % 16 == 0 && (g.o_bs * esz) % 16 == 0;
+  for (const void* q : ptrs) g.vec = g.vec && aligned16(q);
+  return g;
+}
+
+template <bool kDet>
+static int conv_bwd_launch(const ConvArgs& a, int io_dtype, bool fast, dim3 grid, hipStream_t s) {
+  with_io_type(io_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int kP = 16 / sizeof(T);
+    const auto kernel = fast ? conv1d_bwd_fast_kernel<T, kP, kDet> : conv1d_bwd_kernel<T, kP, kDet>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kConvThreads), 0, s, a);
+  });
+  return static_cast<int>(hipGetLastError());
 }
 
 }  // namespace simamba
@@ -369,29 +373,18 @@ extern "C" int simamba_causal_conv1d_fwd(const void* x, const float* w, const fl
   if (rc) return rc;
   if (!out) return SIMAMBA_E_NULLPTR;
   if (batch == 0 || seqlen == 0) return SIMAMBA_OK;
-  ConvArgs a{};
-  a.x = x; a.w = w; a.bias = bias; a.out = out;
-  a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.width = width; a.silu = silu;
-  const int dblocks = fill_common(a, io_dtype);
-  a.x_bs = x_bstride ? x_bstride : static_cast<long long>(dim) * seqlen;
-  a.o_bs = static_cast<long long>(dim) * seqlen;
-  a.vec = a.vec && aligned16(x) && aligned16(out) && (a.x_bs * io_esz(io_dtype)) % 16 == 0;
-  dim3 grid(dblocks, (batch + a.bchunk - 1) / a.bchunk);
+  const ConvGeom g = conv_geom(batch, dim, seqlen, io_dtype, kPack, x_bstride, 0, {x, out});
+  const ConvArgs a{x, w, bias, out, nullptr, nullptr, nullptr, batch, dim, seqlen, width, silu,
+                   g.vec, g.ppr, g.bchunk, g.x_bs, g.o_bs};
   hipStream_t s = static_cast<hipStream_t>(stream);
   with_io_type(io_dtype, [&](auto tag) {
-    hipLaunchKernelGGL(conv1d_fwd_kernel<decltype(tag)>, grid, dim3(kConvThreads), 0, s, a);
+    hipLaunchKernelGGL(conv1d_fwd_kernel<decltype(tag)>, g.grid, dim3(kConvThreads), 0, s, a);
   });
   return static_cast<int>(hipGetLastError());
 }
 
 // Deterministic form: workspace of the per-batch-slice partials (det_layout), in floats; the slicing depends on the
 // I/O type's pack, the size asked for covers both.
-static long long conv_det_slices(int batch, int dim, int seqlen, int io_dtype) {
-  ConvArgs a{};
-  a.batch = batch; a.dim = dim; a.seqlen = seqlen;
-  fill_common(a, io_dtype, io_pack(io_dtype));
-  return (batch + a.bchunk - 1) / a.bchunk;
-}
 static long long conv_det_dw_floats(long long slices, int dim, int width) {
   return (slices * dim * width + 63) & ~63ll;                 // dbias partials start on a 256-byte boundary
 }
@@ -402,8 +395,9 @@ extern "C" long long simamba_causal_conv1d_bwd_workspace_floats(int batch, int d
   if (batch < 0 || dim <= 0 || seqlen < 0) return SIMAMBA_E_SHAPE;
   if (width < 2 || width > 4) return SIMAMBA_E_WIDTH;
   if (batch == 0 || seqlen == 0) return 0;
-  const long long s4 = conv_det_slices(batch, dim, seqlen, SIMAMBA_F32), s8 = conv_det_slices(batch, dim, seqlen, SIMAMBA_BF16);
-  const long long sl = s4 > s8 ? s4 : s8;
+  long long sl = 0;
+  for (int io_dtype : {SIMAMBA_F32, SIMAMBA_BF16})
+    sl = std::max<long long>(sl, conv_geom(batch, dim, seqlen, io_dtype, io_pack(io_dtype)).grid.y);
   return conv_det_dw_floats(sl, dim, width) + sl * dim;
 }
 
@@ -417,9 +411,8 @@ extern "C" int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const
   int rc = check_conv(x, w, batch, dim, seqlen, width, io_dtype);
   if (rc) return rc;
   if (!dout || !dx || !dw) return SIMAMBA_E_NULLPTR;
-  if (det && simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags) > 0 &&
-      (!workspace || workspace_floats < simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags)))
-    return SIMAMBA_E_WORKSPACE;
+  const long long need = det ? simamba_causal_conv1d_bwd_workspace_floats(batch, dim, seqlen, width, flags) : 0;
+  if (need > 0 && (!workspace || workspace_floats < need)) return SIMAMBA_E_WORKSPACE;
   if (det && !aligned16(workspace)) return SIMAMBA_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the two accumulators are zeroed here; a caller that carves dbias directly behind dw gets one memset node
@@ -434,40 +427,18 @@ extern "C" int simamba_causal_conv1d_bwd_ex(const void* x, const float* w, const
     }
   }
   if (batch == 0 || seqlen == 0) return SIMAMBA_OK;
-  ConvArgs a{};
-  a.x = x; a.w = w; a.bias = bias; a.out = dx; a.dout = dout; a.dw = dw; a.dbias = dbias;
-  a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.width = width; a.silu = silu;
-  const int dblocks = fill_common(a, io_dtype, io_pack(io_dtype));
-  a.x_bs = x_bstride ? x_bstride : static_cast<long long>(dim) * seqlen;
-  a.o_bs = dx_bstride ? dx_bstride : static_cast<long long>(dim) * seqlen;
-  const long long esz = io_esz(io_dtype);
-  a.vec = a.vec && aligned16(x) && aligned16(dx) && aligned16(dout) && (a.x_bs * esz) % 16 == 0 &&
-          (a.o_bs * esz) % 16 == 0;
-  dim3 grid(dblocks, (batch + a.bchunk - 1) / a.bchunk);
-  const bool fast = a.vec && seqlen % io_pack(io_dtype) == 0;
-  if (det) {                                                 // partials in place of the accumulators
-    a.dw = workspace;
-    a.dbias = dbias ? workspace + conv_det_dw_floats(grid.y, dim, width) : nullptr;
-    with_io_type(io_dtype, [&](auto tag) {
-      using T = decltype(tag);
-      constexpr int kP = 16 / sizeof(T);
-      if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<T, kP, true>), grid, dim3(kConvThreads), 0, s, a);
-      else hipLaunchKernelGGL((conv1d_bwd_kernel<T, kP, true>), grid, dim3(kConvThreads), 0, s, a);
-    });
-    const int e = static_cast<int>(hipGetLastError());
-    if (e) return e;
-    DetSumJob jobs[2] = {{a.dw, dw, static_cast<long long>(dim) * width, static_cast<long long>(dim) * width,
-                          static_cast<int>(grid.y)},
-                         {a.dbias, dbias, dim, dim, static_cast<int>(grid.y)}};
-    return det_sum_launch(jobs, dbias ? 2 : 1, s);
-  }
-  with_io_type(io_dtype, [&](auto tag) {
-    using T = decltype(tag);
-    constexpr int kP = 16 / sizeof(T);
-    if (fast) hipLaunchKernelGGL((conv1d_bwd_fast_kernel<T, kP>), grid, dim3(kConvThreads), 0, s, a);
-    else hipLaunchKernelGGL((conv1d_bwd_kernel<T, kP>), grid, dim3(kConvThreads), 0, s, a);
-  });
-  return static_cast<int>(hipGetLastError());
+  const ConvGeom g = conv_geom(batch, dim, seqlen, io_dtype, io_pack(io_dtype), x_bstride, dx_bstride, {x, dx, dout});
+  ConvArgs a{x, w, bias, dx, dout, dw, dbias, batch, dim, seqlen, width, silu, g.vec, g.ppr, g.bchunk, g.x_bs, g.o_bs};
+  const bool fast = g.vec && seqlen % io_pack(io_dtype) == 0;
+  if (!det) return conv_bwd_launch<false>(a, io_dtype, fast, g.grid, s);
+  const int slices = static_cast<int>(g.grid.y);
+  a.dw = workspace;                                            // partials in place of the accumulators
+  a.dbias = dbias ? workspace + conv_det_dw_floats(slices, dim, width) : nullptr;
+  const int e = conv_bwd_launch<true>(a, io_dtype, fast, g.grid, s);
+  if (e) return e;
+  const long long nw = static_cast<long long>(dim) * width;
+  DetSumJob jobs[2] = {{a.dw, dw, nw, nw, slices}, {a.dbias, dbias, dim, dim, slices}};
+  return det_sum_launch(jobs, dbias ? 2 : 1, s);
 }
 
 extern "C" int simamba_causal_conv1d_bwd(const void* x, const float* w, const float* bias, const void* dout,

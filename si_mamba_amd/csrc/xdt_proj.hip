@@ -21,6 +21,7 @@
 //            (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) puts a store instruction on two rows x 128 contiguous bytes.
 // Algorithmic bytes per token: read 4 D, write 4 D + 4 S (6.4 KB; with the conv fused another 4 D written); flops
 // 2 S D + 2 D R = 123 K: close to the ridge of fp32 MFMA (157 TF/s) against HBM.
+#include "conv_device.h"
 #include "xdt_walk.h"
 
 namespace simamba {
@@ -45,7 +46,7 @@ struct XdtArgs {
 };
 
 // kConv: the causal depthwise conv1d (width 4) + SiLU that precedes x_proj in the mixer runs while the x tile is
-// staged -- same arithmetic as conv1d_fwd_kernel (fmaf chain over the taps, x * sigmoid(x)) -- and its result is both
+// staged -- conv1d_fwd_kernel's arithmetic (conv_pre of conv_device.h, then x * sigmoid(x)) -- and its result is both
 // the GEMM operand and, stored once, the conv output the scan and the backward read: the separate conv launch and its
 // re-read of the activation disappear.  A thread's 4-step pack needs the 3 steps before it: the previous pack of the
 // row sits in the neighbouring lane (DPP row_shr:1; a tile row is exactly one 16-lane DPP row) except for the row's
@@ -151,9 +152,7 @@ struct XdtF32 {
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float acc = bias;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc = fmaf(w4[q], win[e + q], acc);
+          const float acc = conv_pre(w4, win + e, bias);
           o[e] = acc * sigmoid_f(acc);
         }
         v = make_float4(o[0], o[1], o[2], o[3]);

@@ -17,6 +17,7 @@
 //   * delta leaves as 2-byte stores, 32 lanes on 64 contiguous bytes of a row (the other half of the line follows from
 //     the unit of the neighbouring token block, two iterations later).
 // A step moves half the bytes of the fp32 form and needs an eighth of its MFMAs; registers allow 3 workgroups per CU.
+#include "conv_device.h"
 #include "xdt_walk.h"
 
 namespace simamba {
@@ -122,9 +123,7 @@ __global__ __launch_bounds__(kHThreads, 3) void xdt_proj_bf16_kernel(XdtHArgs p)
       float o[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float acc = bias;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = fmaf(w4[q], win[e + q], acc);
+        const float acc = conv_pre(w4, win + e, bias);
         o[e] = acc * sigmoid_f(acc);
       }
       v = make_uint4(bf16_pack2(o[0], o[1]), bf16_pack2(o[2], o[3]), bf16_pack2(o[4], o[5]),

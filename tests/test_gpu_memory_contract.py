@@ -82,13 +82,13 @@ def _grads(*ts):
 
 
 # ---- mixer core ------------------------------------------------------------------------------------------------------
-CONV_ATOMIC = "si_mamba_amd/csrc/conv1d.hip:141 (dw) and :143 (dbias)"
+CONV_ATOMIC = "si_mamba_amd/csrc/conv1d.hip: conv_bwd_reduce, the atomicAdd into p.dw and into p.dbias"
 CONV_TOL = ("tests/test_gpu_conv.py: nerr < 1e-3 (fp32), 1e-2 (bf16)", {F32: 1e-3, BF16: 1e-2})
 # the scan backward the row's checkpoint step selects, and the conv1d backward behind it
 SCAN_ATOMIC = {"row": "si_mamba_amd/csrc/scan_bwd.hip:233-235 (dA, dD, ddelta_bias), :270 (dB, dC); "
-                      "conv1d.hip:141, :143",
+                      "conv1d.hip: conv_bwd_reduce (dw, dbias)",
                "seq": "si_mamba_amd/csrc/scan_bwd_seq.hip:521 (ddelta_bias), :558 (dB, dC), :575-576 (dA, dD); "
-                      "conv1d.hip:141, :143"}
+                      "conv1d.hip: conv_bwd_reduce (dw, dbias)"}
 MIXER_TOL = ("tests/test_gpu_mixer_routes.py: NERR = 1e-3 (fp32), 1e-2 (bf16)", {F32: 1e-3, BF16: 1e-2})
 
 

@@ -1,16 +1,18 @@
-"""Causal conv1d + SiLU backward (csrc/conv1d.hip) at the model shape, fp32 and bf16: time and bytes/s."""
+"""Causal conv1d + SiLU backward (csrc/conv1d.hip) at the model shape, fp32 and bf16: time and bytes/s.
+--unaligned: x starts one element into its buffer, so no 16-byte accesses: the generic kernel instead of the pipelined."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from si_mamba_amd import _lib
 if os.environ.get("SIMAMBA_LIB"):
     _lib.LIB_PATH = os.path.abspath(os.environ["SIMAMBA_LIB"])
+unaligned = "--unaligned" in sys.argv[1:]
 dev = torch.device("cuda:0")
 lib = _lib.load()
 B, D, L, W = 64, 768, 1024, 4
 for dt in (torch.float32, torch.bfloat16):
-    xz = torch.randn(B, 2 * D, L, device=dev).to(dt)
-    dxz = torch.empty_like(xz)
+    xz = torch.randn(B * 2 * D * L + 1, device=dev).to(dt)[int(unaligned):][:B * 2 * D * L].view(B, 2 * D, L)
+    dxz = torch.empty(B, 2 * D, L, device=dev, dtype=dt)
     du = torch.randn(B, D, L, device=dev).to(dt)
     cw = torch.randn(D, W, device=dev)
     cb = torch.randn(D, device=dev)
@@ -32,4 +34,5 @@ for dt in (torch.float32, torch.bfloat16):
     torch.cuda.synchronize()
     us = a.elapsed_time(b) * 1e3 / 20
     byt = 3 * B * D * L * xz.element_size()
-    print(f"{str(dt)[6:]:9s} conv1d_bwd {us:7.1f} us   {byt / us / 1e6:6.2f} TB/s of {byt / 1e6:.0f} MB")
+    print(f"{str(dt)[6:]:9s} conv1d_bwd{' (generic)' if unaligned else ''} {us:7.1f} us   {byt / us / 1e6:6.2f} TB/s "
+          f"of {byt / 1e6:.0f} MB")
