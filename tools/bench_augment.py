@@ -21,20 +21,16 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import measure  # noqa: E402
 
 B = 64
 SIZES = {1024: 1200, 2048: 2400, 8192: 8192}         # N -> M (runner_finetune.py:191-203)
-
-
-def stats(v):
-    return [round(sorted(v)[len(v) // 2], 2), round(min(v), 2), round(max(v), 2)]
 
 
 def eager_rotate(pc, rng):
@@ -62,8 +58,7 @@ def main():
     ap.add_argument("--deviations", default=None,
                     help="JSON file with the deviations the GPU tests printed, copied into the result")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_augment.py needs a ROCm device: a time from anything else says nothing")
+    measure.require_gpu("bench_augment.py")
     from si_mamba_amd import _lib, transforms as T
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
@@ -71,14 +66,6 @@ def main():
     ops = {"rotate": (T.PointcloudRotate(), eager_rotate),
            "scale_translate": (T.PointcloudScaleAndTranslate(), eager_scale_translate)}
     g = torch.Generator().manual_seed(0)
-
-    def timed_round(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.calls):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / args.calls * 1e6
 
     rows = []
     for N, M in SIZES.items():
@@ -96,18 +83,17 @@ def main():
             for fn in routes.values():                       # warm-up: every kernel loaded, the allocator settled
                 for _ in range(3):
                     fn()
-            us = {k: [] for k in routes}
-            for _ in range(args.rounds):
-                for k, fn in routes.items():
-                    us[k].append(timed_round(fn))
+            us = measure.rounds({k: (lambda fn=fn: measure.host_clock(fn, steps=args.calls, warmup=0) * 1e3)
+                                 for k, fn in routes.items()}, args.rounds)
             _lib.enable_kernel_timing(True, only=["augment_points"])
             for _ in range(50):
                 routes["gather_fused"]()
             torch.cuda.synchronize()
             launches, kernel_ms = _lib.kernel_times()["augment_points"]
             _lib.enable_kernel_timing(False)
-            rows.append(dict(N=N, M=M, op=name, fused_us=stats(us["fused"]), gather_fused_us=stats(us["gather_fused"]),
-                             eager_loop_us=stats(us["eager_loop"]), kernel_us=round(kernel_ms * 1e3, 2)))
+            rows.append(dict(N=N, M=M, op=name, fused_us=measure.stats(us["fused"], 2),
+                             gather_fused_us=measure.stats(us["gather_fused"], 2),
+                             eager_loop_us=measure.stats(us["eager_loop"], 2), kernel_us=round(kernel_ms * 1e3, 2)))
             print(json.dumps(rows[-1]), flush=True)
 
     deviations = None

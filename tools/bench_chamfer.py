@@ -23,7 +23,6 @@ comparison is reported as not measured.
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 import torch
@@ -33,6 +32,9 @@ if "--child" in sys.argv:                        # a timing process of --ragged:
     ROOT = os.path.abspath(sys.argv[sys.argv.index("--child") + 1])
 sys.path.insert(0, ROOT)
 from si_mamba_amd.mae import chamfer_distance  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # measure: always this tree's
+from tools import measure  # noqa: E402
 
 SHAPES = [(64, 1024, 1024), (64, 2048, 1024), (16, 8192, 8192)]
 PEAK_LANE_OPS = 256 * 4 * 32 * 2.4e9
@@ -47,23 +49,10 @@ def clouds(B, N, seed, dev):
     return (p / p.norm(dim=-1).max(dim=1)[0][:, None, None]).to(dev)
 
 
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def timeit(fn, target_ms=200.0, windows=5):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    reps = max(1, min(2000, int(target_ms / max(window_ms(fn, 3), 1e-3))))
-    ts = sorted(window_ms(fn, reps) for _ in range(windows))
-    return ts[len(ts) // 2], ts[0], ts[-1]
+def timeit(fn):
+    """(median, min, max) ms per call over 5 windows of about 0.2 s, after a warm-up of 3 calls."""
+    ts = measure.alternate({"op": fn}, target_ms=200.0, windows=5, warmup=3)["op"]
+    return measure.median(ts), min(ts), max(ts)
 
 
 def torch_form(x, y):
@@ -109,22 +98,12 @@ def ragged_child():
     print(json.dumps(dict(tree=ROOT, device=torch.cuda.get_device_name(0), rows=rows)))
 
 
-def median(v):
-    v = sorted(v)
-    return v[len(v) // 2]
-
-
 def ragged_main(args):
     """Alternate fresh timing processes of the parent tree and of this one; one JSON line of medians and every run."""
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     trees = ([("parent", os.path.abspath(args.parent))] if args.parent else []) + [("this", here)]
-    runs = {name: [] for name, _ in trees}
-    for r in range(args.runs):
-        for name, tree in trees:
-            print(f"run {r + 1} of {args.runs}: {name}", file=sys.stderr, flush=True)
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", tree], check=True,
-                                 capture_output=True, text=True, timeout=600).stdout
-            runs[name].append(json.loads(out.strip().splitlines()[-1]))
+    runs = measure.fresh_processes([(name, None, [sys.executable, os.path.abspath(__file__), "--child", tree])
+                                    for name, tree in trees], args.runs, timeout_s=600)
     rows = []
     for i, shape in enumerate(SHAPES):
         row = dict(shape=list(shape))
@@ -132,7 +111,7 @@ def ragged_main(args):
             for key in runs[name][0]["rows"][i]:
                 if key.endswith("_ms"):
                     vals = [r["rows"][i][key] for r in runs[name]]
-                    row[f"{name}_{key}"] = dict(median=median(vals), runs=vals)
+                    row[f"{name}_{key}"] = dict(median=measure.median(vals), runs=vals)
                 elif key != "shape":
                     row[key] = runs[name][-1]["rows"][i][key]
         for k in ("fwd_ms", "fwd_bwd_ms"):
@@ -165,8 +144,7 @@ def main():
     args = ap.parse_args()
     if args.ragged and not args.child:
         return ragged_main(args)                 # starts the timing processes; opens no device itself
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_chamfer.py needs a ROCm device: a time from anything else says nothing")
+    measure.require_gpu("bench_chamfer.py")
     if args.child:
         return ragged_child()
     dev = torch.device("cuda:0")

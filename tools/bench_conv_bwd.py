@@ -3,9 +3,9 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from si_mamba_amd import _lib
-if os.environ.get("SIMAMBA_LIB"):
-    _lib.LIB_PATH = os.path.abspath(os.environ["SIMAMBA_LIB"])
+from tools import measure
+measure.require_gpu("bench_conv_bwd.py")
+_lib = measure.use_lib_from_env()
 unaligned = "--unaligned" in sys.argv[1:]
 dev = torch.device("cuda:0")
 lib = _lib.load()
@@ -24,15 +24,7 @@ for dt in (torch.float32, torch.bfloat16):
                                            acc.data_ptr(), acc[D * W:].data_ptr(), B, D, L, W, 1, _lib.dtype_code(dt),
                                            xz.stride(0), dxz.stride(0), st)
         assert rc == 0
-    for _ in range(3):
-        run()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(20):
-        run()
-    b.record()
-    torch.cuda.synchronize()
-    us = a.elapsed_time(b) * 1e3 / 20
+    us = measure.calls(run, warmup=3, reps=20) * 1e3
     byt = 3 * B * D * L * xz.element_size()
     print(f"{str(dt)[6:]:9s} conv1d_bwd{' (generic)' if unaligned else ''} {us:7.1f} us   {byt / us / 1e6:6.2f} TB/s "
           f"of {byt / 1e6:.0f} MB")

@@ -20,7 +20,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -30,10 +29,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from si_mamba_amd import _lib  # noqa: E402
-
-
-def summary(xs):
-    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4), "n": len(xs)}
+from tools import measure  # noqa: E402
 
 
 def scan_case(B, D, L, dtype, ckpt, dev):
@@ -109,7 +105,7 @@ def kernels(args, dev):
                     acc[(m, c)].append(t[c])
         out = {}
         for c in calls:
-            a, d = summary(acc[("atomic", c)]), summary(acc[("deterministic", c)])
+            a, d = measure.summary(acc[("atomic", c)], 4), measure.summary(acc[("deterministic", c)], 4)
             out[c] = {"atomic_us": a, "deterministic_us": d, "ratio_median": round(d["median"] / a["median"], 4)}
         res[name] = out
         del fn
@@ -131,19 +127,15 @@ def train_steps(args, dev):
     fill0 = tud.fill_uninitialized_memory
 
     def run(amp, steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        for _ in range(steps):
+        def step():
             opt.zero_grad(set_to_none=True)
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
                 loss = m.get_loss_acc(m(pts), gt)[0]
             loss.backward()
             torch.nn.utils.clip_grad_norm_(m.parameters(), 10.0)
             opt.step()
-        b.record()
         torch.cuda.synchronize()
-        return 64 * steps / (a.elapsed_time(b) / 1e3)
+        return 64 / (measure.window(step, steps) / 1e3)
 
     modes = [("default", False, True), ("torch_deterministic_fill_on", True, True),
              ("torch_deterministic_fill_off", True, False)]
@@ -161,7 +153,7 @@ def train_steps(args, dev):
                     tud.fill_uninitialized_memory = fill
                     acc[k].append(run(amp, args.steps))
             key = "bf16" if amp else "fp32"
-            res[key] = {k: summary(v) for k, v in acc.items()}
+            res[key] = {k: measure.summary(v, 4) for k, v in acc.items()}
             base = res[key]["default"]["median"]
             for k in acc:
                 res[key][k]["vs_default"] = round(res[key][k]["median"] / base, 4)
@@ -180,6 +172,7 @@ def main():
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    measure.require_gpu("bench_deterministic.py")
     dev = torch.device("cuda:0")
     out = {"device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "reps": args.reps, "steps": args.steps,
            "unit_kernels": "us per library call", "unit_train": "clouds/s", "kernels": kernels(args, dev)}

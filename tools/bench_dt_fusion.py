@@ -4,6 +4,8 @@ mixer launches them, each bracketed by events.  Usage: python tools/bench_dt_fus
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("bench_dt_fusion.py")
 from si_mamba_amd import _lib
 
 dev = torch.device("cuda:0")

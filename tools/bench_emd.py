@@ -13,40 +13,15 @@ alternation: no code on the cdl2 path changes, so the two must agree within thei
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import measure  # noqa: E402
 
 SHAPES = [(39424, 32), (64, 1024)]
-
-
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def alternate(ops, target_ms=200.0, windows=5):
-    """name -> (median, min, max) ms per call; one window of every operation, then the next round of windows."""
-    reps = {}
-    for name, fn in ops.items():
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        reps[name] = max(1, min(2000, int(target_ms / max(window_ms(fn, 2), 1e-3))))
-    ts = {name: [] for name in ops}
-    for _ in range(windows):
-        for name, fn in ops.items():
-            ts[name].append(window_ms(fn, reps[name]))
-    return {name: [round(sorted(v)[len(v) // 2], 4), round(min(v), 4), round(max(v), 4)] for name, v in ts.items()}
 
 
 def kernels():
@@ -68,7 +43,7 @@ def kernels():
         if n <= 64:
             ops["chamfer_patch_fwd"] = lambda: chamfer_distance(x, y)
             ops["chamfer_patch_fwd_bwd"] = lambda: fwd_bwd(chamfer_distance)
-        row = dict(shape=[pairs, n], ms_median_min_max=alternate(ops))
+        row = dict(shape=[pairs, n], ms_median_min_max={k: measure.stats(v, 4) for k, v in measure.alternate(ops).items()})
         dist, assign, rounds, conv = earth_movers_distance(x, y, return_assignment=True)
         row.update(rounds_mean=round(float(rounds.float().mean()), 1), rounds_max=int(rounds.max()),
                    max_rounds=default_max_rounds(n), converged_share=float(conv.float().mean()))
@@ -80,14 +55,11 @@ def steps(parent, runs):
     variants = [("this_cdl2", ROOT, ["--loss", "cdl2"]), ("this_emd", ROOT, ["--loss", "emd"])]
     if parent:
         variants.insert(0, ("parent_cdl2", os.path.abspath(parent), []))
-    out = {name: [] for name, _, _ in variants}
-    for r in range(runs):
-        for name, tree, extra in variants:
-            print(f"run {r + 1} of {runs}: {name}", file=sys.stderr, flush=True)
-            txt = subprocess.run([sys.executable, os.path.join(tree, "tools", "bench_mae.py")] + extra, check=True,
-                                 capture_output=True, text=True, timeout=600, cwd=tree).stdout
-            out[name].append(json.loads(txt.strip().splitlines()[-1])["ms_per_step"])
-    res = {name: dict(median=sorted(v)[len(v) // 2], runs=v) for name, v in out.items()}
+    out = measure.fresh_processes(
+        [(name, tree, [sys.executable, os.path.join(tree, "tools", "bench_mae.py")] + extra)
+         for name, tree, extra in variants], runs, timeout_s=600,
+        parse=lambda txt: measure.last_json_line(txt)["ms_per_step"])
+    res = {name: dict(median=measure.median(v), runs=v) for name, v in out.items()}
     if not parent:
         res["parent_cdl2"] = "not measured (no --parent)"
     return res
@@ -100,8 +72,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3, help="bench_mae.py processes per variant")
     ap.add_argument("--no-steps", action="store_true", help="kernel times only")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_emd.py needs a ROCm device: a time from anything else says nothing")
+    measure.require_gpu("bench_emd.py")
     # the step processes first: this process has not opened the device yet, so they have the GPU to themselves
     step_ms = None if args.no_steps else steps(args.parent, args.runs)
     line = json.dumps(dict(what="earth_movers_distance and the one-wave chamfer_distance, fp32, gaussian clouds, one "

@@ -2,17 +2,14 @@
 layer + max (sparse against dense) at the bench shapes."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import measure
+measure.require_gpu("bench_encoder.py")
 import torch.nn as nn
 from si_mamba_amd.encoder_ops import bn_relu_fn, group_max_fn
 dev = torch.device("cuda:0")
 
-def timeit(fn, n=20):
-    for _ in range(3): fn()
-    ts = []
-    for _ in range(n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(b))
-    ts.sort(); return ts[len(ts) // 2]
+def timeit(fn):
+    return measure.per_call_median(fn, warmup=3, reps=20)
 
 for rows, C, group in [(262144, 128, 0), (262144, 512, 32)]:
     x = torch.randn(rows, C, device=dev, requires_grad=True)

@@ -3,9 +3,9 @@ the library GEMM it replaces."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from si_mamba_amd import _lib
-if os.environ.get("SIMAMBA_LIB"):
-    _lib.LIB_PATH = os.path.abspath(os.environ["SIMAMBA_LIB"])
+from tools import measure
+measure.require_gpu("bench_in_proj.py")
+_lib = measure.use_lib_from_env()
 
 dev = torch.device("cuda:0")
 lib = _lib.load()
@@ -29,15 +29,7 @@ def library():
 
 
 for name, fn in (("hand in_proj kernel", hand), ("library GEMM", library)) * 2:
-    for _ in range(3):
-        fn()
-    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(20):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    us = a.elapsed_time(e) / 20 * 1e3
+    us = measure.calls(fn, warmup=3, reps=20) * 1e3
     byt = (B * L * C + M * C + B * M * L) * x.element_size()
     print(f"{str(dt)[6:]} B={B} L={L} M={M} {name:22s} {us:7.1f} us   {byt / us / 1e6:5.2f} TB/s of {byt / 1e6:.0f} MB   "
           f"{2 * B * L * C * M / us * 1e-6:.0f} TF/s", flush=True)

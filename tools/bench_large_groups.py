@@ -24,22 +24,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from si_mamba_amd import grouping, spectral  # noqa: E402
 from si_mamba_amd.synthetic import unit_ball_centers  # noqa: E402
+from tools import measure  # noqa: E402
 
 
 def median_ms(fn, warmup=3, reps=10):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b))
-    ts.sort()
-    return ts[len(ts) // 2]
+    return measure.per_call_median(fn, warmup=warmup, reps=reps)
 
 
 def householder_bytes(G):
@@ -63,6 +52,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernels-only", action="store_true")
     args = ap.parse_args()
+    measure.require_gpu("bench_large_groups.py")
     dev = torch.device("cuda:0")
     B = 64
     cent = {G: unit_ball_centers(B, G, 0).to(dev) for G in (128, 256, 512)}

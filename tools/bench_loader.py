@@ -25,20 +25,16 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import measure  # noqa: E402
 
 B = 64
 CLASSES = 15          # default_config().cls_dim: a label outside [0, cls_dim) traps in torch's nll_loss kernel
-
-
-def stats(v, nd=2):
-    return [round(sorted(v)[len(v) // 2], nd), round(min(v), nd), round(max(v), nd)]
 
 
 class HostClouds(torch.utils.data.Dataset):
@@ -85,8 +81,7 @@ def main():
         host_iter = iter(host_loader)
         first = next(host_iter)                              # every worker is up
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_loader.py needs a ROCm device: a time from anything else says nothing")
+    measure.require_gpu("bench_loader.py")
     from si_mamba_amd import _lib
     from si_mamba_amd.data import DeviceDataset, DeviceLoader
     dev = torch.device("cuda:0")
@@ -122,15 +117,9 @@ def main():
             outs[name] = loaders[name].fetch()
             for _ in range(3):
                 loaders[name].fetch(out=outs[name])
-        us = {k: [] for k in shapes}
-        for _ in range(args.rounds):
-            for name in shapes:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.calls):
-                    loaders[name].fetch(out=outs[name])
-                torch.cuda.synchronize()
-                us[name].append((time.perf_counter() - t0) / args.calls * 1e6)
+        us = measure.rounds({name: (lambda name=name: measure.host_clock(
+            lambda: loaders[name].fetch(out=outs[name]), steps=args.calls, warmup=0) * 1e3) for name in shapes},
+            args.rounds)
         rows = []
         for name, (store, kw) in shapes.items():
             _lib.enable_kernel_timing(True, only=["dataset_fetch"])
@@ -140,7 +129,7 @@ def main():
             _, kernel_ms = _lib.kernel_times()["dataset_fetch"]
             _lib.enable_kernel_timing(False)
             rows.append(dict(store=name, clouds=len(store), store_GB=round(store.nbytes / 1e9, 3), **kw,
-                             fetch_us=stats(us[name]), kernel_us=round(kernel_ms * 1e3, 2), launches_per_call=2,
+                             fetch_us=measure.stats(us[name], 2), kernel_us=round(kernel_ms * 1e3, 2), launches_per_call=2,
                              h2d_copies_per_call=0, host_reads_per_call=0))
             print(json.dumps(rows[-1]), flush=True)
         res["fetch"] = dict(calls=args.calls, rounds=args.rounds, rows=rows)
@@ -183,21 +172,13 @@ def main():
                 host_iter = iter(host_loader)
         feed = host_batches()
 
+        def host_fed():
+            p, y = next(feed)
+            host_step(p.to(dev, non_blocking=True), y.to(dev, non_blocking=True))
+        one = {"static": static_step, "device": device_step, "host": host_fed, "host_alone": lambda: next(feed)}
+
         def window(kind):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                if kind == "static":
-                    static_step()
-                elif kind == "device":
-                    device_step()
-                elif kind == "host":
-                    p, y = next(feed)
-                    host_step(p.to(dev, non_blocking=True), y.to(dev, non_blocking=True))
-                else:
-                    next(feed)
-            torch.cuda.synchronize()
-            return B * args.steps / (time.perf_counter() - t0)
+            return B / measure.host_clock(one[kind], steps=args.steps, warmup=0) * 1e3
 
         kinds = ["static", "device", "host", "host_alone"]
         for k in kinds:
@@ -209,7 +190,7 @@ def main():
                 print(k, round(rate[k][-1], 1), flush=True)
         res["train"] = dict(steps_per_window=args.steps, rounds=args.rounds, workers=args.workers,
                             cpus=os.cpu_count(), host_clouds=args.host_clouds,
-                            clouds_per_s={k: stats(v, 1) for k, v in rate.items()})
+                            clouds_per_s={k: measure.stats(v, 1) for k, v in rate.items()})
 
     if args.deviations:
         with open(args.deviations) as fh:

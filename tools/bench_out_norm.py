@@ -3,9 +3,9 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from si_mamba_amd import _lib
-if os.environ.get("SIMAMBA_LIB"):
-    _lib.LIB_PATH = os.path.abspath(os.environ["SIMAMBA_LIB"])
+from tools import measure
+measure.require_gpu("bench_out_norm.py")
+measure.use_lib_from_env()
 from si_mamba_amd.add_norm import add_layer_norm_fn
 from si_mamba_amd.out_norm import out_proj_add_ln_fn
 
@@ -35,15 +35,7 @@ def gemm_only():
 
 with torch.no_grad():
     for name, fn in (("fused out_proj+add+LN", fused), ("library GEMM + add_ln kernel", unfused), ("library GEMM alone", gemm_only)) * 2:
-        for _ in range(3):
-            fn()
-        a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(20):
-            fn()
-        e.record()
-        torch.cuda.synchronize()
-        us = a.elapsed_time(e) / 20 * 1e3
+        us = measure.calls(fn, warmup=3, reps=20) * 1e3
         hbm = (B * K * L * 2 + C * K * 2 + 2 * B * L * C * 4 + B * L * C * 2) / 1e6
         print(f"B={B} L={L} {name:32s} {us:7.1f} us   ({hbm:.0f} MB algorithmic for the fused op -> {hbm / us * 1e-3 * 1e3:.0f} GB/s; "
               f"{2 * B * L * C * K / us * 1e-6:.0f} TF/s)", flush=True)

@@ -23,7 +23,6 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -33,13 +32,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from si_mamba_amd import _lib  # noqa: E402
+from tools import measure  # noqa: E402
 
 SHAPES = [(64, 1024, 128, 32), (64, 8192, 512, 32)]
 PLAIN = ("simamba_farthest_point_sample", "simamba_knn_group")
-
-
-def summary(xs):
-    return {"median": round(statistics.median(xs), 2), "min": round(min(xs), 2), "max": round(max(xs), 2), "n": len(xs)}
 
 
 def load_plain(path):
@@ -50,29 +46,12 @@ def load_plain(path):
     return lib
 
 
-def timed(fn, reps, stream):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    for _ in range(reps):
-        fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
-
-
 def compare(variants, rounds, reps, stream):
     """variants: name -> callable; every variant warmed up, then ``rounds`` rounds that run them in turn, in the
-    opposite order every other round."""
-    for fn in variants.values():
-        fn()
-        fn()
-    torch.cuda.synchronize()
-    acc = {k: [] for k in variants}
-    for r in range(rounds):
-        names = list(variants) if r % 2 == 0 else list(variants)[::-1]
-        for k in names:
-            acc[k].append(timed(variants[k], reps, stream))
-    return {k: summary(v) for k, v in acc.items()}
+    opposite order every other round; us per call."""
+    acc = measure.alternate(variants, windows=rounds, reps=reps, warmup=2, reverse_odd=True,
+                            window=lambda fn, n: measure.window(fn, n, stream) * 1e3)
+    return {k: measure.summary(v, 2) for k, v in acc.items()}
 
 
 def checked(rc):
@@ -151,6 +130,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    measure.require_gpu("bench_ragged_clouds.py")
     dev = torch.device("cuda:0")
     new = _lib.load()
     parent = load_plain(args.parent_lib) if args.parent_lib else None

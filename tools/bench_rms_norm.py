@@ -9,37 +9,24 @@ measurement alternates the two modes for 5 rounds and reports the median [min, m
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from si_mamba_amd import _lib  # noqa: E402
+from tools import measure  # noqa: E402
 
 ROUNDS = 5
 
 
-def events_us(fn, iters=50, warm=5):
-    for _ in range(warm):
-        fn()
-    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(e) / iters * 1e3
+def events_us(fn):
+    return measure.calls(fn, warmup=5, reps=50) * 1e3
 
 
 def ab(fns):
     """{name: fn} -> {name: [median, min, max]} over ROUNDS alternating rounds"""
-    got = {k: [] for k in fns}
-    for _ in range(ROUNDS):
-        for k, fn in fns.items():
-            got[k].append(fn())
-    return {k: [round(statistics.median(v), 2), round(min(v), 2), round(max(v), 2)] for k, v in got.items()}
+    return {k: measure.stats(v, 2) for k, v in measure.rounds(fns, ROUNDS).items()}
 
 
 def add_norm_calls(dev, dtype, B=64, L=1024, d=384):
@@ -123,18 +110,13 @@ def train_steps(dev, rms, batch=64, npoints=1024):
         loss.backward()
         torch.nn.utils.clip_grad_norm_(params, 10.0)
         opt.step()
-        return loss
+        last["loss"] = loss
+    last = {}
 
     def timed(steps=10, warm=3):
-        for _ in range(warm):
-            step()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            loss = step()
-        torch.cuda.synchronize()
-        assert torch.isfinite(loss).item()
-        return (time.perf_counter() - t0) / steps * 1e3
+        ms = measure.host_clock(step, steps=steps, warmup=warm)
+        assert torch.isfinite(last["loss"]).item()
+        return ms
     return timed
 
 
@@ -143,6 +125,7 @@ def main():
     ap.add_argument("--out", help="also write the JSON document to this path")
     ap.add_argument("--no-step", action="store_true", help="kernels only")
     args = ap.parse_args()
+    measure.require_gpu("bench_rms_norm.py")
     dev = torch.device("cuda:0")
     doc = {"device": torch.cuda.get_device_name(dev), "rounds": ROUNDS,
            "note": "median [min, max] over alternating rounds; us per call (device events), ms per train step"}

@@ -3,9 +3,9 @@ north-star micro-shape and the model-level shape.  SIMAMBA_LIB=<path> selects an
 import argparse, os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from si_mamba_amd import _lib
-if os.environ.get("SIMAMBA_LIB"):
-    _lib.LIB_PATH = os.environ["SIMAMBA_LIB"]
+from tools import measure
+measure.require_gpu("bench_scan.py")
+_lib = measure.use_lib_from_env()
 from si_mamba_amd import selective_scan_fn
 from si_mamba_amd.synthetic import scan_inputs
 
@@ -29,24 +29,15 @@ for shp in args.shapes.split(","):
         t[k] = t[k].to(dt)
     leaves = [t[k].requires_grad_(True) for k in ("u", "delta", "A", "B", "C", "D", "z", "delta_bias")]
     for mode in args.modes.split(","):
-        times = []
-        for i in range(args.iters + 3):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        def one():                      # ms of one call between its own pair of events; bwd: a fresh forward outside them
             if mode == "fwd":
                 with torch.no_grad():
-                    a.record()
-                    selective_scan_fn(t["u"], t["delta"], t["A"], t["B"], t["C"], t["D"], t["z"], t["delta_bias"], True)
-                    b.record()
-            else:
-                out = selective_scan_fn(*leaves[:6], z=leaves[6], delta_bias=leaves[7], delta_softplus=True)
-                a.record()
-                torch.autograd.grad(out, leaves, t["dout"])
-                b.record()
-            torch.cuda.synchronize()
-            if i >= 3:
-                times.append(a.elapsed_time(b))
-        times.sort()
-        med = times[len(times) // 2]
+                    return measure.window(lambda: selective_scan_fn(t["u"], t["delta"], t["A"], t["B"], t["C"], t["D"],
+                                                                     t["z"], t["delta_bias"], True), 1)
+            out = selective_scan_fn(*leaves[:6], z=leaves[6], delta_bias=leaves[7], delta_softplus=True)
+            return measure.window(lambda: torch.autograd.grad(out, leaves, t["dout"]), 1)
+        times = sorted([one() for _ in range(args.iters + 3)][3:])
+        med = measure.median(times)
         nbytes = (4 * B * D * L * s + 2 * B * N * L * s) if mode == "fwd" else (7 * B * D * L * s + 2 * B * N * L * (s + 4))
         res[f"{shp}:{mode}"] = {"ms": round(med, 4), "min_ms": round(times[0], 4), "GBs": round(nbytes / med / 1e6, 1)}
         print(f"{os.environ.get('SIMAMBA_LIB', 'default'):40s} {shp:16s} {mode}: median {med*1e3:8.1f} us  min {times[0]*1e3:8.1f} us  {nbytes/med/1e6:7.1f} GB/s ({nbytes/med/1e6/80:.1f}% of 8 TB/s)", flush=True)

@@ -2,9 +2,9 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from si_mamba_amd import _lib
-if os.environ.get("SIMAMBA_LIB"):
-    _lib.LIB_PATH = os.environ["SIMAMBA_LIB"]
+from tools import measure
+measure.require_gpu("bench_scan_context.py")
+_lib = measure.use_lib_from_env()
 from si_mamba_amd import selective_scan_fn
 from si_mamba_amd.synthetic import scan_inputs
 

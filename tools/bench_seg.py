@@ -2,9 +2,10 @@
 L=1024), fwd+bwd+AdamW: clouds/s on one GPU (tuning / reporting tool, not the judged bench).  ``--dp``: the data-parallel
 step, one rank by default or one per GPU under torchrun (clouds/s of this rank) -- with ``--graph`` the two-graph
 GraphedTrainStep around one all-reduce, without it DistributedDataParallel (wrap_ddp)."""
-import argparse, os, sys, time, json
+import argparse, os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
 from si_mamba_amd.seg import PartSegMamba, default_seg_config, get_loss
 from si_mamba_amd.synthetic import make_clouds
 
@@ -17,6 +18,7 @@ ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--graph", action="store_true", help="capture the whole step in one hipGraph (GraphedTrainStep)")
 ap.add_argument("--dp", action="store_true", help="data-parallel step over torch.distributed (RCCL)")
 args = ap.parse_args()
+measure.require_gpu("bench_seg.py")
 dev = torch.device("cuda:0")
 rank, world = 0, 1
 if args.dp:
@@ -58,12 +60,10 @@ if args.graph:
 for _ in range(6):                                        # (allocator growth and library one-offs reach into step 3)
     step()
 import gc; gc.collect()     # (a full collection costs ~80 ms here: outside the timed steps)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(args.steps):
+def timed_step():
+    global loss
     loss = step()
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / args.steps
+dt = measure.host_clock(timed_step, steps=args.steps, warmup=0) / 1e3
 if rank == 0:
     print(json.dumps({"workload": f"part segmentation train step, {args.method}, {args.npoints} pts, B={args.batch}, {args.dtype}" + (", hipGraph" if args.graph else "") + (f", data-parallel, {world} rank(s)" if args.dp else ""),
                       "ms_per_step": round(dt * 1e3, 2), "clouds_per_s": round(args.batch / dt, 1), "loss": float(loss)}))

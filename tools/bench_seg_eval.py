@@ -19,7 +19,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -27,13 +26,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from tools import measure  # noqa: E402
 
 B, N, C = 16, 2048, 50
 DISTINCT = 8
-
-
-def stats(v):
-    return [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
 
 
 def main():
@@ -42,8 +38,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seg_eval.json"))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_seg_eval.py needs a ROCm device: a time from anything else says nothing")
+    measure.require_gpu("bench_seg_eval.py")
     import part_metrics_ref as pr
     from si_mamba_amd import SHAPENETPART, PartSegMetrics, part_seg_eval
     dev = torch.device("cuda:0")
@@ -56,24 +51,21 @@ def main():
         target = first[:, None] + (torch.rand(B, N, generator=g) * count[:, None]).long()
         data.append((torch.randn(B, N, C, generator=g).to(dev), target.to(dev)))
 
+    def timed_pass(acc, add, result):
+        """ms from the first batch to the averages on the host (both routes end in a host read), and the averages"""
+        res = []
+
+        def one_pass():
+            for i in range(args.batches):
+                add(acc, *data[i % DISTINCT])
+            res.append(result(acc))
+        return measure.host_clock(one_pass, steps=1, warmup=0), res[0]
+
     def device_round():
-        acc = PartSegMetrics(device=dev)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(args.batches):
-            acc.update(*data[i % DISTINCT])
-        res = acc.compute()
-        return (time.perf_counter() - t0) * 1e3, res
+        return timed_pass(PartSegMetrics(device=dev), lambda a, s, t: a.update(s, t), lambda a: a.compute())
 
     def host_round():
-        ref = pr.Pass(table)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(args.batches):
-            scores, target = data[i % DISTINCT]
-            ref.add(scores.cpu().numpy(), target.cpu().numpy())
-        res = ref.result()
-        return (time.perf_counter() - t0) * 1e3, res
+        return timed_pass(pr.Pass(table), lambda a, s, t: a.add(s.cpu().numpy(), t.cpu().numpy()), lambda a: a.result())
 
     device_round()                                    # warm-up: the table on the device, every kernel loaded
     ms = dict(device=[], host=[])
@@ -86,16 +78,8 @@ def main():
                for k in ("accuracy", "class_avg_accuracy", "class_avg_iou", "inctance_avg_iou"))
 
     scores, target = data[0]
-    reps = 200
-    kernel = []
-    for _ in range(args.rounds):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            part_seg_eval(scores, target, return_pred=False)
-        b.record()
-        torch.cuda.synchronize()
-        kernel.append(a.elapsed_time(b) / reps * 1e3)
+    kernel = [measure.window(lambda: part_seg_eval(scores, target, return_pred=False), 200) * 1e3
+              for _ in range(args.rounds)]
 
     from si_mamba_amd import _lib
     _lib.enable_kernel_timing(True, only=["part_seg_eval"])
@@ -112,9 +96,11 @@ def main():
              "torch operations that prepare its arguments) between device events; kernel_us: the kernel alone, a pair "
              f"of events around each of {launches} launches, mean",
         kernel_us=round(kernel_ms * 1e3, 2),
-        device=torch.cuda.get_device_name(0), batches=args.batches, pass_ms_device=stats(ms["device"]),
-        pass_ms_host=stats(ms["host"]), per_batch_ms_device=round(stats(ms["device"])[0] / args.batches, 4),
-        per_batch_ms_host=round(stats(ms["host"])[0] / args.batches, 4), part_seg_eval_call_us=stats(kernel),
+        device=torch.cuda.get_device_name(0), batches=args.batches, pass_ms_device=measure.stats(ms["device"], 3),
+        pass_ms_host=measure.stats(ms["host"], 3),
+        per_batch_ms_device=round(measure.stats(ms["device"], 3)[0] / args.batches, 4),
+        per_batch_ms_host=round(measure.stats(ms["host"], 3)[0] / args.batches, 4),
+        part_seg_eval_call_us=measure.stats(kernel, 3),
         averages_agree=bool(same), averages=got and {k: got[k] for k in got if k != "category_iou"}))
     print(line)
     if args.out:

@@ -28,7 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tools.bench_emd import alternate  # noqa: E402
+from tools import measure  # noqa: E402
 
 SHAPES = [(64, 1024, 1024), (64, 2048, 1024), (1, 8192, 8192)]
 EPS_REL, ITERS = 2.0 ** -6, 16
@@ -118,7 +118,7 @@ def timings():
             row["composed"] = f"does not fit: {str(err).splitlines()[0]}"
             torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
-        row["ms_median_min_max"] = ms = alternate(ops)
+        row["ms_median_min_max"] = ms = {k: measure.stats(v, 4) for k, v in measure.alternate(ops).items()}
         row["peak_mb_all_ops"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
         row["exp"] = {}
         for name, back in (("sinkhorn_fwd", False), ("sinkhorn_fwd_bwd", True)):
@@ -157,8 +157,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--ratios", action="store_true", help="gpu_error / ref_error for every case of the GPU tests")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_sinkhorn.py needs a ROCm device: a time from anything else says nothing")
+    measure.require_gpu("bench_sinkhorn.py")
     res = dict(what="sinkhorn_divergence (fp32, gaussian sets, defaults: eps_rel 2^-6, 16 iterations, 22 steps) and the "
                     "same procedure composed from torch ops, one MI355X; call times (events around back-to-back calls, "
                     "5 windows of ~0.2 s per operation, the operations alternating): [median, min, max] ms; exp: "

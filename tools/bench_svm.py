@@ -19,6 +19,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import measure  # noqa: E402
 
 
 def make(n_train, n_test, d, nc, spread, seed):
@@ -44,19 +45,16 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-sklearn", action="store_true")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_svm: no ROCm device")
+    measure.require_gpu("bench_svm.py")
     from si_mamba_amd import OvOLinearSVC
     dev = torch.device("cuda:0")
     Xtr, ytr, Xte, yte = make(a.n_train, a.n_test, a.dim, a.classes, a.spread, a.seed)
     X, y, Xt, yt = (torch.from_numpy(v).to(dev) for v in (Xtr, ytr, Xte, yte))
 
     def sync_time(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, time.perf_counter() - t0
+        out = []
+        ms = measure.host_clock(lambda: out.append(fn()), steps=1, warmup=0)
+        return out[0], ms / 1e3
 
     clf = OvOLinearSVC(C=a.C).fit(X, y)          # warm-up: code objects, the GEMM's choice of algorithm
     clf.predict(Xt)

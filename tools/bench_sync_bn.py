@@ -16,10 +16,8 @@ device-synchronised on both sides; peak memory is torch's allocator peak over on
 import argparse
 import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 import torch
 import torch.distributed as dist
@@ -28,6 +26,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from si_mamba_amd import encoder_ops, point_mamba  # noqa: E402
 from si_mamba_amd.point_mamba import Encoder  # noqa: E402
+from tools import measure  # noqa: E402
 
 
 def module_route(x, bn, gterm=None, group=0):
@@ -49,8 +48,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_sync_bn: needs a ROCm device")
+    measure.require_gpu("bench_sync_bn.py")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     store = tempfile.mkdtemp()
@@ -86,18 +84,15 @@ def main():
                     torch.cuda.synchronize()
                     torch.cuda.reset_peak_memory_stats(dev)
                     before = torch.cuda.memory_allocated(dev)
-                    t0 = time.perf_counter()
-                    y = step(name, autocast)
-                    torch.cuda.synchronize()
-                    dt = time.perf_counter() - t0
+                    y = []
+                    ms = measure.host_clock(lambda: y.append(step(name, autocast)), steps=1, warmup=0)
                     if it >= args.warmup:
-                        times[name].append(dt * 1e3)
+                        times[name].append(ms)
                     peaks[name] = (torch.cuda.max_memory_allocated(dev) - before) / 2 ** 20
-                    outs[name] = y.detach().float()
-                    del y
+                    outs[name] = y.pop().detach().float()
             ref = outs["local"]
             result[label] = {
-                name: dict(ms_median=round(statistics.median(times[name]), 3), ms_min=round(min(times[name]), 3),
+                name: dict(ms_median=round(measure.median(times[name]), 3), ms_min=round(min(times[name]), 3),
                            ms_max=round(max(times[name]), 3), peak_mib_above_start=round(peaks[name], 1),
                            max_abs_diff_vs_local=float((outs[name] - ref).abs().max()))
                 for name in ROUTES}

@@ -3,18 +3,15 @@ runs; the tuned table applies) against a split-K batched product + sum (tuning t
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("bench_wgrad_splitk.py")
 from si_mamba_amd.gemm_tuning import enable_tuned_gemms
 
 dev = torch.device("cuda:0")
 enable_tuned_gemms()
 
-def timeit(fn, n=10):
-    for _ in range(3): fn()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
+def timeit(fn):
+    return measure.calls(fn, warmup=3, reps=10) * 1e3
 
 M = 262144
 for dt in (torch.float32, torch.bfloat16):

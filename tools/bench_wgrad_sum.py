@@ -3,22 +3,16 @@ against the alternatives that would drop the (B, M, N) partials and the reduce l
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("bench_wgrad_sum.py")
 from si_mamba_amd.gemm_tuning import enable_tuned_gemms
 
 dev = torch.device("cuda:0")
 enable_tuned_gemms()
 
 
-def timeit(fn, n=10):
-    for _ in range(3):
-        fn()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
+def timeit(fn):
+    return measure.calls(fn, warmup=3, reps=10) * 1e3
 
 
 B, D, L, d = 64, 768, 1024, 384

@@ -3,8 +3,9 @@
 import os, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
-from si_mamba_amd import _lib
-_lib.LIB_PATH = os.path.abspath(sys.argv[1])
+from tools import measure
+os.environ["SIMAMBA_LIB"] = sys.argv[1]
+measure.use_lib_from_env()
 sys.argv = ["bench.py"] + sys.argv[2:]
 import bench
 bench.main()

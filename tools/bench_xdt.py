@@ -2,6 +2,8 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("bench_xdt.py")
 from si_mamba_amd.gemm_tuning import enable_tuned_gemms
 from si_mamba_amd.mamba_inner import _wx, _xw, xdt_proj_fwd
 
@@ -21,15 +23,7 @@ for B, D, L, N, R in [(64, 768, 1024, 16, 24), (128, 768, 1024, 16, 24), (64, 76
         return xdt_proj_fwd(x, wx, wdt)
 
     for name, fn in (("library (2 GEMMs)", lib), ("fused MFMA kernel", fused)):
-        for _ in range(3):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(20):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        us = a.elapsed_time(b) * 1e3 / 20
+        us = measure.calls(fn, warmup=3, reps=20) * 1e3
         flops = 2.0 * B * L * (S * D + D * R)
         nbytes = 4.0 * B * L * (2 * D + S)
         print(f"({B},{D},{L}) {name:20s} {us:8.1f} us  {flops / us * 1e-6:6.1f} TF/s  {nbytes / us * 1e-3:7.1f} GB/s", flush=True)
@@ -48,12 +42,4 @@ for B, D, L in [(64, 768, 1024), (128, 768, 1024)]:
     xc = torch.empty(B, D, L, device=dev)
     for name, fn in (("conv kernel + xdt kernel", lambda: xdt_proj_fwd(causal_conv1d_fn(x_in, cw, cb, "silu"), wx, wdt)),
                      ("conv fused into xdt", lambda: xdt_proj_fwd(x_in, wx, wdt, conv=(cw, cb, xc)))):
-        for _ in range(3):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(20):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        print(f"({B},{D},{L}) {name:26s} {a.elapsed_time(b) * 1e3 / 20:8.1f} us", flush=True)
+        print(f"({B},{D},{L}) {name:26s} {measure.calls(fn, warmup=3, reps=20) * 1e3:8.1f} us", flush=True)

@@ -1,13 +1,11 @@
-import torch, time
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from tools import measure
+measure.require_gpu("bf16x3_probe.py")
 dev = torch.device("cuda:0")
-def timeit(fn, n=20):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
+def timeit(fn):
+    return measure.calls(fn, warmup=3, reps=20) * 1e3
 M, K, N = 65536, 384, 1536
 x = torch.randn(M, K, device=dev); w = torch.randn(N, K, device=dev) / K ** 0.5
 ref = (x.double() @ w.double().t())

@@ -2,6 +2,8 @@
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("cpu_enqueue_time.py")
 from si_mamba_amd import _lib
 from si_mamba_amd.point_mamba import PointMamba, default_config
 from si_mamba_amd.synthetic import make_clouds

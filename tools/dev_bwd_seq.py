@@ -8,10 +8,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from oracle import scan_ref                        # noqa: E402
 from oracle.gen_golden import scan_inputs          # noqa: E402
-from si_mamba_amd import _lib, selective_scan_fn   # noqa: E402
-
-if os.environ.get("SIMAMBA_LIB"):
-    _lib.LIB_PATH = os.path.abspath(os.environ["SIMAMBA_LIB"])
+from tools import measure                          # noqa: E402
+measure.require_gpu("dev_bwd_seq.py")
+_lib = measure.use_lib_from_env()
+from si_mamba_amd import selective_scan_fn         # noqa: E402
 dev = torch.device("cuda:0")
 QUICK = "--quick" in sys.argv          # timing of the model shape only, fp32
 
@@ -111,16 +111,9 @@ if "--time" in sys.argv:
                         acc[0].data_ptr(), acc[1].data_ptr(), acc[2].data_ptr(), acc[3].data_ptr(), dz.data_ptr(), acc[4].data_ptr(),
                         B, D, L, N, code, 1, 0, 0, xdbl.stride(0), 1, xdbl.stride(1), step, st)
                 for name, fn in (("fwd", fwd), ("bwd", bwd)):
-                    for _ in range(3):
-                        rc = fn()
-                        assert rc == 0, (name, step, rc)
-                    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    for _ in range(20):
-                        fn()
-                    e.record()
-                    torch.cuda.synchronize()
-                    res[(name, step)] = a.elapsed_time(e) / 20 * 1e3
+                    rc = fn()
+                    assert rc == 0, (name, step, rc)
+                    res[(name, step)] = measure.calls(fn, warmup=2, reps=20) * 1e3
                 res[("grads", step)] = [x.clone() for x in (du, dd, dz, acc[0], acc[1], acc[2], acc[3], acc[4])]
             diff = max(nerr(a, b) for a, b in zip(res[("grads", 16)], res[("grads", 128)]))
             print(os.environ.get("SIMAMBA_LIB", "default"), (B, D, L), str(dtype)[6:], " ".join(f"{k[0]}@{k[1]}:{v:.0f}us" for k, v in res.items() if k[0] != "grads"),

@@ -7,9 +7,9 @@ run back to back on one stream and of the same work issued on two streams."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from si_mamba_amd import _lib
-if os.environ.get("SIMAMBA_LIB"):                                  # an A/B build from tools/build_alt.sh
-    _lib.LIB_PATH = os.path.abspath(os.environ["SIMAMBA_LIB"])
+from tools import measure
+measure.require_gpu("overlap_probe.py")
+_lib = measure.use_lib_from_env()                                  # an A/B build from tools/build_alt.sh
 from si_mamba_amd.gemm_tuning import enable_tuned_gemms
 from si_mamba_amd.synthetic import scan_inputs
 
@@ -57,17 +57,8 @@ scan_fwd(main.cuda_stream)
 torch.cuda.synchronize()
 
 
-def timeit(fn, n=10):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(main)
-    for _ in range(n):
-        fn()
-    b.record(main)
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
+def timeit(fn):
+    return measure.calls(fn, warmup=2, reps=10, stream=main) * 1e3
 
 
 def seq():

@@ -3,6 +3,8 @@ backward (conv1d backward, add + LayerNorm backward) when issued on a second str
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("overlap_probe2.py")
 from si_mamba_amd import _lib
 from si_mamba_amd.gemm_tuning import enable_tuned_gemms
 
@@ -50,17 +52,8 @@ main = torch.cuda.current_stream(dev)
 side = torch.cuda.Stream(device=dev)
 
 
-def timeit(fn, n=10):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(main)
-    for _ in range(n):
-        fn()
-    b.record(main)
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
+def timeit(fn):
+    return measure.calls(fn, warmup=3, reps=10, stream=main) * 1e3
 
 
 def par(g):

@@ -2,6 +2,8 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("profile_layer.py")
 from torch.profiler import profile, ProfilerActivity
 from si_mamba_amd.block import create_block
 dev = torch.device("cuda:0")

@@ -4,9 +4,11 @@ si_mamba_amd.gemm_tuning.enable_tuned_gemms loads read-only).
 
     python tools/tune_gemm.py gpurun_out/tunableop_results.csv
 """
-import os, sys, time
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from tools import measure
+measure.require_gpu("tune_gemm.py")
 import torch.cuda.tunable as tunable
 from si_mamba_amd.synthetic import make_clouds
 
@@ -68,12 +70,8 @@ def seg(dtype):
     return step
 
 
-def timeit(step, n=5):
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(n):
-        step()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3
+def timeit(step):
+    return measure.host_clock(step, steps=5, warmup=0)
 
 
 tunable.enable(True)
@@ -95,9 +93,7 @@ for name, make, dtype in [(w, table[w], "f32") for w in wanted]:
     base = timeit(step)
     tunable.enable(True)
     tunable.tuning_enable(True)
-    t0 = time.perf_counter()
-    step(); torch.cuda.synchronize()
-    took = time.perf_counter() - t0
+    took = measure.host_clock(step, steps=1, warmup=0) / 1e3
     tunable.tuning_enable(False)
     print(f"{name:10s} {dtype}: default {base:7.2f} ms/step, tuned {timeit(step):7.2f} ms/step (tuning pass {took:.0f} s, "
           f"{len(tunable.get_results())} entries)", flush=True)

@@ -20,6 +20,8 @@ PREFIX = "GemmStridedBatchedTunableOp_float_"
 
 
 def tune(batch, out):
+    from tools import measure
+    measure.require_gpu("tune_gemm_compact.py")
     import torch
     import torch.cuda.tunable as tunable
     from si_mamba_amd.block import MixerModel
