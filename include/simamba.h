@@ -32,6 +32,8 @@
  *                                    part_segmentation/dataset.py: shuffle, per-item sampling, pc_norm, collate.
  *   simamba_svm_ovo_fit/_vote        sklearn.svm.SVC(C=0.01, kernel='linear') (libsvm) of
  *                                    tools/runner_pretrain.py:66-77.
+ *   simamba_tsne_calibrate/_run      sklearn.manifold.TSNE(n_components=2, init='pca') of
+ *                                    tools/runner_finetune.py:605-612, with the exact gradient.
  *
  * Conventions
  *   - Plain pointers and sizes only.  All pointers are DEVICE pointers unless noted.
@@ -46,8 +48,8 @@
  *     (batch, state, time) strides (e.g. straight out of the (batch, seqlen, R+2N) x_proj output).
  *     A stride of 0 means "contiguous default".
  *   - io_dtype: SIMAMBA_F32 or SIMAMBA_BF16 for activation-sized tensors; all state,
- *     accumulation and parameter gradients are fp32.  The one exception is the simamba_svm_ovo_* family, which is
- *     float64 throughout (stated there).
+ *     accumulation and parameter gradients are fp32.  The exceptions are the simamba_svm_ovo_* family, which is
+ *     float64 throughout, and the fp64 sums and outputs of the simamba_tsne_* family (both stated there).
  */
 #ifndef SIMAMBA_H_
 #define SIMAMBA_H_
@@ -764,6 +766,58 @@ int simamba_svm_ovo_fit(const double* gram, const float* x, const int* order, co
                         void* stream);
 int simamba_svm_ovo_vote(const double* dec, const long long* labels, int* pred, long long* matches, long long m, int nc,
                          void* stream);
+
+/*
+ * Exact t-SNE in two dimensions (csrc/tsne.hip): the reference's map of the classifier's pooled features,
+ * tools/runner_finetune.py:605-612, scikit-learn's TSNE with its schedule and its stop rule.  Storage is fp32; the sums
+ * of the perplexity search, Z, the squared gradient norm and KL are fp64.  2 <= n <= 16384 throughout.
+ *
+ * simamba_tsne_calibrate: one workgroup per row i of d2, the (n, n) fp32 squared distances.  It finds beta_i with the
+ * entropy of p_{j|i} ~ exp(-beta_i d2_ij), j != i, equal to log(perplexity): scikit-learn's search (start at 1, double
+ * or halve until bracketed, then bisect, at most 100 steps, stop at |H - log perplexity| <= 1e-5), on the row less its
+ * smallest off-diagonal entry.
+ *   cond : (n, n) fp32, the normalised conditional rows at the beta returned, cond[i][i] = 0.
+ *   beta : (n) fp64.             0 < perplexity < n.
+ * Checks: SIMAMBA_E_SHAPE (n, perplexity), then null pointers.
+ *
+ * simamba_tsne_workspace_floats: host only; the floats of `ws` below for n points, SIMAMBA_E_SHAPE for an n outside the
+ * limits.  ws is device memory, 16-byte aligned (else SIMAMBA_E_ALIGN; NULL: SIMAMBA_E_WORKSPACE); every word a call
+ * reads from it the same call has written.
+ *
+ * simamba_tsne_gradient: one forces pass and the fixed-order sum; nothing moves.
+ *   p         : (n, n) fp32 joint probabilities, SYMMETRIC (the kernel reads column blocks as rows), zero diagonal.
+ *   y         : (n, 2) fp32.
+ *   grad      : (n, 2) fp32 = 4 sum_j (exaggeration p_ij - q_ij) w_ij (y_i - y_j),  w = 1 / (1 + |y_i - y_j|^2),
+ *               q = w / Z,  Z = sum_{i != j} w_ij.
+ *   kl        : (1) fp64 = sum_plogp + sum_ij p_ij log(1 + |y_i - y_j|^2) + log Z  (of p itself, whatever exaggeration).
+ *   sum_plogp : (1) fp64, device: the constant sum_ij p_ij log p_ij.
+ * Checks: SIMAMBA_E_SHAPE (n; exaggeration not finite or <= 0), null pointers, workspace, alignment.
+ *
+ * simamba_tsne_run: enqueues iterations first_iter .. first_iter + n_iter - 1 of scikit-learn's _gradient_descent, two
+ * launches each (forces, update) and a third on the iterations that compute the error: those with (it + 1) % 50 == 0,
+ * the check iterations, and the last of the call.
+ *   y, update, gains : (n, 2) fp32 state, in and out: gains += 0.2 where update * g < 0, else *= 0.8, floor 0.01;
+ *                      update = momentum * update - learning_rate * gains * g;  y += update.
+ *   status           : (8) fp64, in and out: [0] the last error computed (KL of exaggeration * p), [1] the gradient norm
+ *                      at the last check (of gains * g, as scikit-learn takes it), [2] the best error, [3] its
+ *                      iteration, [4] iterations done when [0] was written, [5] stopped, [6..7] unused.  On a check
+ *                      iteration: a lower error becomes the best, otherwise it - best iteration > window stops; a
+ *                      gradient norm <= min_grad_norm stops.  Every launch behind a set `stopped` returns at once.  The
+ *                      caller starts a stage with [2] = DBL_MAX, [3] = first_iter, [5] = 0 (or carries them over).
+ *   params           : a HOST array of four fp64 read during the call, {exaggeration > 0, 0 <= momentum < 1,
+ *                      learning_rate > 0, min_grad_norm >= 0}.
+ *   first_iter, n_iter, window >= 0; n_iter == 0 enqueues nothing.
+ * No float atomics, every sum in a fixed order: the same bits every call.  No grid-wide barrier.
+ * Checks: SIMAMBA_E_SHAPE (n, the iteration counts, then params when not NULL), null pointers, workspace, alignment;
+ * all before any launch.  Still ABI version 9: symbols added, none changed.
+ */
+int simamba_tsne_calibrate(const float* d2, float* cond, double* beta, int n, float perplexity, void* stream);
+long long simamba_tsne_workspace_floats(int n);
+int simamba_tsne_gradient(const float* p, const float* y, float* grad, double* kl, float* ws, const double* sum_plogp,
+                          int n, float exaggeration, void* stream);
+int simamba_tsne_run(const float* p, float* y, float* update, float* gains, double* status, float* ws,
+                     const double* sum_plogp, const double* params, int n, int first_iter, int n_iter, int window,
+                     void* stream);
 
 /*
  * Sampling and augmentation of a batch of clouds in front of a step (csrc/augment.hip; the reference's

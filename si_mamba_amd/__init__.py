@@ -14,6 +14,8 @@ from .emd import earth_movers_distance
 from .sinkhorn import sinkhorn_divergence
 from .seg_metrics import SHAPENETPART, PartSegMetrics, PartTable, part_seg_eval
 from .svm import OvOLinearSVC, evaluate_svm
+from . import manifold
+from .manifold import TSNE
 from . import transforms
 from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRandomInputDropout, PointcloudRotate,
                          PointcloudScale, PointcloudScaleAndTranslate, PointcloudTranslate, RandomHorizontalFlip,
@@ -28,4 +30,5 @@ __all__ = ["data", "Batch", "DeviceDataset", "DeviceLoader", "transforms", "Augm
            "RandomHorizontalFlip", "sample_and_augment", "vote_logits",
 "SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
-           "set_deterministic", "earth_movers_distance", "sinkhorn_divergence", "OvOLinearSVC", "evaluate_svm"]
+           "set_deterministic", "earth_movers_distance", "sinkhorn_divergence", "OvOLinearSVC", "evaluate_svm", "manifold",
+           "TSNE"]

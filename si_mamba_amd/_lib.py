@@ -149,6 +149,10 @@ SIGNATURES = {
     "simamba_part_seg_eval": (c_int, [_P] * 12 + [_LL, c_int, c_int, c_int, _P]),
     "simamba_svm_ovo_fit": (c_int, [_P] * 10 + [c_int, c_int, c_int, c_int, c_int, _P]),
     "simamba_svm_ovo_vote": (c_int, [_P, _P, _P, _P, _LL, c_int, _P]),
+    "simamba_tsne_calibrate": (c_int, [_P, _P, _P, c_int, c_float, _P]),
+    "simamba_tsne_workspace_floats": (_LL, [c_int]),
+    "simamba_tsne_gradient": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_float, _P]),
+    "simamba_tsne_run": (c_int, [_P] * 8 + [c_int, c_int, c_int, c_int, _P]),
     "simamba_augment_points": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_augment_params": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _LL, c_int, _P]),
     "simamba_philox4x32_10": (c_int, [_LL, c_uint, c_uint, c_uint, c_uint, _P]),

@@ -231,7 +231,8 @@ class PointMamba(nn.Module):
         return spectral.order_tokens(self.method, (tokens, pos), center, order, self.k_top_eigenvectors, self.reverse,
                                      self.hlt_rand)
 
-    def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None, *, lengths=None):
+    def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None, *, lengths=None,
+                return_features=False):
         """Reference signature (models/point_mamba.py:843; the runner calls
         ``base_model(points, gt=None, tau=None, use_wavelets=True)``, tools/runner_finetune.py:201).  Built: the
         published spectral route (``tau is None``, ``use_wavelets=False``).  ``gt`` given -> ``(logits, policy)``
@@ -240,7 +241,10 @@ class PointMamba(nn.Module):
         (the wavelet branch calls a function the reference never defines, :879) and are
         refused by name rather than silently replaced.  ``save_pts_dir`` / ``epoch`` only feed the reference's
         point-dump visualisation and are ignored.  ``lengths`` (B,), keyword-only and not in the reference: the point
-        count of every cloud of a padded batch (``Group``); only the tokeniser sees it."""
+        count of every cloud of a padded batch (``Group``); only the tokeniser sees it.  ``return_features``,
+        keyword-only and off by default: also return the pooled (B, trans_dim) vector the head consumes (the
+        ``concat_f`` the reference's t-SNE call site, tools/runner_finetune.py:605, expects): ``(logits, features)``,
+        or ``(logits, policy, features)`` with ``gt``."""
         if tau is not None:
             raise NotImplementedError("PointMamba.forward(tau=...): the learned-permutation branch (reference "
                                       "models/point_mamba.py:902-952) is outside the SI-Mamba hot-path scope")
@@ -296,11 +300,13 @@ class PointMamba(nn.Module):
                                   out_dtype=self.norm.weight.dtype)[0]
         else:
             x = self.norm(x)
-        ret = self.cls_head_finetune(x.mean(1))
+        features = x.mean(1)
+        ret = self.cls_head_finetune(features)
         if not want_policy:
-            return ret
+            return (ret, features) if return_features else ret
         if spec is None:
             spec = self.spectral_eigs(center)
         vals, vecs, _ = spec
         ordered_vecs = torch.sort(vecs.transpose(1, 2), dim=-1)[0]                 # :954
-        return ret, plackett_luce_dist(-ordered_vecs).sum(-1) + plackett_luce_dist(vals)
+        policy = plackett_luce_dist(-ordered_vecs).sum(-1) + plackett_luce_dist(vals)
+        return (ret, policy, features) if return_features else (ret, policy)
