@@ -144,11 +144,18 @@ __global__ __launch_bounds__(kSpecMaxG * kKnnLanes) void knn_graph_kernel(const 
 // ---------------------------------------------------------------------------------------------
 // Laplacian + Jacobi eigensolver + selection + argsort, one sample per workgroup.
 //
-// One-sided (Hestenes) Jacobi on W = S + 2I (S = the mirrored lower triangle of the Laplacian; its
-// spectrum lies in [-1, 3] by Gershgorin, so the shifted matrix is positive definite): column pairs (p,q)
-// of W are rotated until all columns are mutually orthogonal.  Then W = (S + 2I) V with V orthogonal and
+// One-sided (Hestenes) Jacobi on W = S + shift I (S = the mirrored lower triangle of the Laplacian): column pairs
+// (p,q) of W are rotated until all columns are mutually orthogonal.  Then W = (S + shift I) V with V orthogonal and
 // W^T W diagonal, i.e. w_j = lambda'_j v_j: the eigenvector is the normalised column, the eigenvalue its
 // norm minus the shift -- no eigenvector matrix is accumulated, the whole state is ONE G x G LDS image.
+// That reading of the columns needs W positive definite: on an indefinite W the norm is |lambda + shift|, and two
+// eigenvalues with lambda_a + shift = -(lambda_b + shift) share their columns.  The rows of I - D^-1 A have their
+// Gershgorin discs in [-1, 3], but S mixes row i's lower entries with the ROWS j > i's entries of column i, so its
+// discs are not bounded: a star's hub row sums to G - 1 and lambda_min(S) = 1 - sqrt(G - 1) (-10.3 at G = 128), and
+// the kernel returned |lambda + 2| - 2 for it.  So the shift comes from the sample: S = D + E (diagonal + rest),
+// lambda_min(S) >= min D_ii - |E|_2 and |E|_2 <= min(largest absolute row sum, Frobenius norm).  Where that bound
+// already lies above -2 the shift is exactly kEigShift = 2, with the arithmetic the constant had (the k-NN graphs of
+// the model's flag sets: bound -1.27 or above on every fixture of the suite); otherwise 1 - bound: lambda' >= 1.
 // Why one-sided: a 16-lane DPP row owns one pair -- it forms the three inner products (alpha, beta, gamma)
 // with a DPP all-reduce, derives the rotation redundantly in every lane and applies it to its slice of the
 // two columns (16-byte LDS accesses), so a step of G/2 disjoint pairs needs ONE workgroup barrier (the
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(kSpecMaxG * kKnnLanes) void knn_graph_kernel(const 
 
 constexpr int kEigLD = kSpecMaxG + 4;     // row stride of the LDS image (floats), keeps rows 16-B aligned
 constexpr int kEigVec = kSpecMaxG / 64;   // 16-byte chunks of a column per lane (lane l: floats 4l.., 64+4l..)
-constexpr float kEigShift = 2.0f;
+constexpr float kEigShift = 2.0f;              // the shift wherever it provably suffices (see above)
 
 __global__ __launch_bounds__(kEigThreads) void laplacian_eig_kernel(EigArgs p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -171,6 +178,7 @@ __global__ __launch_bounds__(kEigThreads) void laplacian_eig_kernel(EigArgs p) {
   __shared__ int sSel[kSpecMaxG];
   __shared__ float sSign[kSpecMaxG];
   __shared__ int sFlag;
+  __shared__ float sShift;
   const int tid = threadIdx.x;
   const int lane16 = tid & 15;
   const int grp = tid >> 4;               // 64 groups of 16 lanes: one column pair each
@@ -185,11 +193,37 @@ __global__ __launch_bounds__(kEigThreads) void laplacian_eig_kernel(EigArgs p) {
     const int i = e / G, j = e - i * G;
     if (i >= j) {
       const float l = laplacian_entry(sym_adj(A, G, i, j), sDeg[i], sDeg[j], i == j, msym);
-      const float w = l + (i == j ? kEigShift : 0.f);
-      Wt[i * LD + j] = w;
-      Wt[j * LD + i] = w;
+      Wt[i * LD + j] = l;
+      Wt[j * LD + i] = l;
     }
   }
+  __syncthreads();
+  // shift that makes W positive definite (see above): one row of S per lane, reduced once by lane 0.  sEval / sSign
+  // are free until the sweeps are over.
+  if (tid < G) {
+    float rabs = 0.f, rsq = 0.f;
+    for (int j = 0; j < G; ++j) {
+      const float x = j == tid ? 0.f : Wt[tid * LD + j];
+      rabs += fabsf(x);
+      rsq = fmaf(x, x, rsq);
+    }
+    sEval[tid] = rabs;
+    sSign[tid] = rsq;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float rmax = 0.f, fro2 = 0.f, dmin = Wt[0];
+    for (int i = 0; i < G; ++i) {
+      rmax = fmaxf(rmax, sEval[i]);
+      fro2 += sSign[i];
+      dmin = fminf(dmin, Wt[i * LD + i]);
+    }
+    const float bound = dmin - 1.0001f * fminf(rmax, sqrtf(fro2));   // <= lambda_min(S), fp32 rounding included
+    sShift = bound > -kEigShift ? kEigShift : 1.0f - bound;
+  }
+  __syncthreads();
+  const float shift = sShift;
+  if (tid < G) Wt[tid * LD + tid] += shift;      // l + 2.0f where the constant holds: the sum the kernel always formed
   __syncthreads();
 
   // ---- cyclic one-sided Jacobi, tournament ordering: group `grp` owns pair `grp` of each step ---------
@@ -271,7 +305,7 @@ __global__ __launch_bounds__(kEigThreads) void laplacian_eig_kernel(EigArgs p) {
       w[k].x *= inv; w[k].y *= inv; w[k].z *= inv; w[k].w *= inv;
       *reinterpret_cast<float4*>(Wt + col * LD + 64 * k + 4 * lane16) = w[k];
     }
-    if (lane16 == 0) sEval[col] = nrm - kEigShift;
+    if (lane16 == 0) sEval[col] = nrm - shift;
   }
   __syncthreads();
   // ---- sort eigenvalues ascending (rank sort, ties by index) ------------------------------
