@@ -34,6 +34,8 @@
  *                                    tools/runner_pretrain.py:66-77.
  *   simamba_tsne_calibrate/_run      sklearn.manifold.TSNE(n_components=2, init='pca') of
  *                                    tools/runner_finetune.py:605-612, with the exact gradient.
+ *   simamba_optim_adamw_step         clip_grad_norm_ + torch.optim.AdamW.step of tools/runner_finetune.py:200-215 and
+ *                                    timm's per-epoch CosineLRScheduler of tools/builder.py:87-95, three launches.
  *
  * Conventions
  *   - Plain pointers and sizes only.  All pointers are DEVICE pointers unless noted.
@@ -818,6 +820,78 @@ int simamba_tsne_gradient(const float* p, const float* y, float* grad, double* k
 int simamba_tsne_run(const float* p, float* y, float* update, float* gains, double* status, float* ws,
                      const double* sum_plogp, const double* params, int n, int first_iter, int n_iter, int window,
                      void* stream);
+
+/*
+ * The optimizer tail of a training step (csrc/optim.hip): gradient clipping by the global norm
+ * (torch.nn.utils.clip_grad_norm_), decoupled AdamW (torch.optim.AdamW's formulation) and a per-epoch learning-rate
+ * table, for any number of parameter tensors in THREE launches: the squared norm, one workgroup of scalars, the update
+ * (the first is repeated once per 448 tensors beyond the first 448: a launch carries that many gradient addresses).
+ * All tensors fp32.  The caller builds two tables in device memory:
+ *
+ *   segments : (n_segments) simamba_optim_segment, one per parameter tensor, 16-byte aligned.  p, g, exp_avg and
+ *              exp_avg_sq may EACH sit at any 4-byte alignment, independently of one another (a 16-byte aligned one is
+ *              accessed 16 bytes at a time).  g is WRITTEN by the call, from `grads`; the caller's value is not read.
+ *              `step` is the tensor's own count of updates, fp32 as torch keeps it; the call advances it by one for
+ *              every segment with a gradient.
+ *   grads    : a HOST array of n_segments device addresses, read during the call: the gradient of every segment, the
+ *              one column that changes from step to step.  The first kernel takes them by value and leaves them in
+ *              the table, so a captured call replays with the addresses its capture saw.  NULL entry: the parameter
+ *              took no gradient; all three kernels skip the segment (no decay, no step, its step count stays).
+ *   first_chunk : a HOST array of n_segments + 1 ints, read during the call: segment s owns the chunk-table entries
+ *              [first_chunk[s], first_chunk[s + 1]); first_chunk[0] == 0, ascending, first_chunk[n_segments] ==
+ *              n_chunks (else SIMAMBA_E_SHAPE, checked when the array is not NULL).
+ *   chunks   : (n_chunks, 2) int32, {segment, chunk inside the segment}: workgroup k of the first and third launch
+ *              works on elements [chunk * SIMAMBA_OPTIM_CHUNK, ...) of that segment.  Every segment is covered by
+ *              ceil(n / SIMAMBA_OPTIM_CHUNK) entries; 8-byte aligned.
+ *   groups   : (n_groups) simamba_optim_group, 16-byte aligned.  `lr` is the address of the group's DEVICE learning
+ *              rate (one fp32): read as it stands without a schedule, written with one.
+ *   updates  : (1) int64, device: the count of calls so far, advanced by one.
+ *   schedule : (schedule_n) fp64, device, or NULL with schedule_n == 0.  With a schedule every group runs at
+ *              schedule[min(updates / steps_per_epoch, schedule_n - 1)] * lr_scale (updates as the call found it).
+ *   grad_norm: (1) fp32, device, out: the norm of grad_scale * g over every segment with a gradient, before clipping.
+ *   max_norm : the clip.  coef = max_norm / (grad_norm + 1e-6), clamped above at 1 with NaN propagating (a NaN norm
+ *              makes every updated parameter NaN, as torch.clamp does); max_norm < 0: no clipping, coef = 1.
+ *   update   : g' = grad_scale * coef * g;  p *= 1 - lr * weight_decay;  m = beta1 m + (1 - beta1) g';
+ *              v = beta2 v + (1 - beta2) g'^2;  p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+ *              The powers, quotients and 1 - lr * weight_decay are formed in fp64, once per segment.
+ *   flags    : SIMAMBA_OPTIM_ZERO_GRADS: the update also stores 0 into g in the same pass.
+ *   workspace: device memory, 16-byte aligned (else SIMAMBA_E_ALIGN), at least simamba_optim_workspace_bytes() bytes
+ *              (else, or NULL, SIMAMBA_E_WORKSPACE); every word a call reads from it the same call has written.
+ * Limits: 1 <= n_segments <= SIMAMBA_OPTIM_MAX_SEGMENTS, 1 <= n_chunks <= SIMAMBA_OPTIM_MAX_CHUNKS (2^32 elements),
+ * 1 <= n_groups <= SIMAMBA_OPTIM_MAX_GROUPS, 0 <= schedule_n <= 2^20, steps_per_epoch >= 1 with a schedule, max_norm
+ * not NaN, grad_scale finite (else SIMAMBA_E_SHAPE).  The workspace query answers 0 outside [0, limit].
+ * No float atomics, every sum in a fixed order: the same bits every call.
+ * Checks in the order flags (SIMAMBA_E_VARIANT), shape, null pointers, workspace, alignment; all before any launch.
+ * Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_OPTIM_CHUNK 4096
+#define SIMAMBA_OPTIM_MAX_SEGMENTS 65536
+#define SIMAMBA_OPTIM_MAX_CHUNKS 1048576
+#define SIMAMBA_OPTIM_MAX_GROUPS 256
+#define SIMAMBA_OPTIM_ZERO_GRADS 1
+typedef struct simamba_optim_segment {
+  float* p;
+  float* g;
+  float* exp_avg;
+  float* exp_avg_sq;
+  long long n;
+  int group;
+  int reserved0;
+  float step;
+  float reserved1;
+  long long reserved2;
+} simamba_optim_segment;
+typedef struct simamba_optim_group {
+  float* lr;
+  double beta1, beta2, eps, weight_decay, lr_scale;
+  double reserved[2];
+} simamba_optim_group;
+size_t simamba_optim_workspace_bytes(int n_segments, int n_chunks);
+int simamba_optim_adamw_step(void* segments, const int* chunks, const void* groups, long long* updates,
+                             const double* schedule, float* grad_norm, const void* const* grads,
+                             const int* first_chunk, void* workspace, size_t workspace_bytes, int n_segments,
+                             int n_chunks, int n_groups, int schedule_n, int steps_per_epoch, float max_norm,
+                             float grad_scale, int flags, void* stream);
 
 /*
  * Sampling and augmentation of a batch of clouds in front of a step (csrc/augment.hip; the reference's

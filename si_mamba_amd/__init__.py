@@ -22,6 +22,7 @@ from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRand
                          sample_and_augment)
 from .vote import vote_logits
 from . import data
+from . import optim
 from .data import Batch, DeviceDataset, DeviceLoader
 from ._lib import deterministic, deterministic_enabled, set_deterministic
 
@@ -31,4 +32,4 @@ __all__ = ["data", "Batch", "DeviceDataset", "DeviceLoader", "transforms", "Augm
 "SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
            "set_deterministic", "earth_movers_distance", "sinkhorn_divergence", "OvOLinearSVC", "evaluate_svm", "manifold",
-           "TSNE"]
+           "TSNE", "optim"]

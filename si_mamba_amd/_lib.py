@@ -47,6 +47,10 @@ DS_FIRST, DS_PERMUTE, DS_CHOICE = 0, 1, 2
 DS_NONE, DS_UNIT_SPHERE = 0, 1
 DS_STREAM_SHUFFLE, DS_STREAM_ROWS, DS_STREAM_CHOICE = 1, 2, 3
 DS_MAX_POINTS = 8192
+# simamba_optim_adamw_step (optim/adamw.py): elements per chunk-table entry, the table limits, the flag
+OPTIM_CHUNK = 4096
+OPTIM_MAX_SEGMENTS, OPTIM_MAX_CHUNKS, OPTIM_MAX_GROUPS = 65536, 1 << 20, 256
+OPTIM_ZERO_GRADS = 1
 
 # name -> (restype, argtypes); mirrors include/simamba.h one to one
 _P = c_void_p
@@ -153,6 +157,9 @@ SIGNATURES = {
     "simamba_tsne_workspace_floats": (_LL, [c_int]),
     "simamba_tsne_gradient": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_float, _P]),
     "simamba_tsne_run": (c_int, [_P] * 8 + [c_int, c_int, c_int, c_int, _P]),
+    "simamba_optim_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "simamba_optim_adamw_step": (c_int, [_P] * 9 + [c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                         c_int, _P]),
     "simamba_augment_points": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _LL, c_int, c_int, c_int, _P]),
     "simamba_augment_params": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _LL, c_int, _P]),
     "simamba_philox4x32_10": (c_int, [_LL, c_uint, c_uint, c_uint, c_uint, _P]),

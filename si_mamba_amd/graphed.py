@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 
 from .dist import FlatBroadcast, FlatGradients
+from .optim import AdamW as _HipAdamW
 
 
 class GraphedForward:
@@ -90,6 +91,13 @@ class GraphedTrainStep:
 
     With ``process_group=None`` none of this exists: one graph, ``zero_grad(set_to_none=True)`` inside it, whether
     or not torch.distributed is initialised.
+
+    With a ``si_mamba_amd.optim.AdamW`` as ``optimizer`` the clip and the update are its three launches:
+    ``optimizer.step(clip=clip)`` in the single graph, ``optimizer.step(clip=clip, grad_scale=1 / world)`` as graph B
+    (the same arithmetic: scale by 1 / world, norm, scale by the clipped coefficient), and ``self.grad_norm`` is the
+    optimizer's.  One difference: ``.grad`` (the flat buffer) holds the raw gradients afterwards, not the clipped
+    mean.  A schedule attached with ``set_schedule`` changes the learning rate under the replays with no recapture.
+    With any other optimizer nothing changes.
     """
 
     def __init__(self, loss_fn, optimizer, example_inputs, params=None, clip=None, warmup: int = 3, *,
@@ -107,6 +115,7 @@ class GraphedTrainStep:
         if not all(t.is_cuda for t in example_inputs):
             raise RuntimeError("GraphedTrainStep needs CUDA/ROCm tensors")
         self.loss_fn, self.opt, self.clip = loss_fn, optimizer, clip
+        self.hip_tail = isinstance(optimizer, _HipAdamW)
         self.params = [p for g in optimizer.param_groups for p in g["params"]] if params is None else list(params)
         self.static_in = [t.clone() for t in example_inputs]
         self.group = process_group
@@ -117,6 +126,8 @@ class GraphedTrainStep:
             self.sync_buffers = FlatBroadcast(floats, process_group) if floats and broadcast_buffers else None
             self.grad_norm = torch.zeros((), device=self.static_in[0].device) if clip is not None else None
             self.flat = None
+        elif self.hip_tail:
+            self.grad_norm = None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -131,7 +142,7 @@ class GraphedTrainStep:
     def recapture(self):
         """Capture the step again, after a change on the Python side that a graph froze as a constant: BatchNorm
         momentum, drop-path rates, a float learning rate.  (A tensor ``lr`` with a capturable optimizer is read by
-        the graph on every replay and needs no recapture.)"""
+        the graph on every replay and needs no recapture, nor does si_mamba_amd.optim.AdamW with a schedule.)"""
         self.graph = self.graph_a = self.graph_b = None        # the old graphs hand their memory pool back first
         torch.cuda.synchronize()
         if self.group is None:
@@ -165,6 +176,10 @@ class GraphedTrainStep:
         self.opt.zero_grad(set_to_none=True)
         loss = self.loss_fn(*self.static_in)
         loss.backward()
+        if self.hip_tail:
+            self.opt.step(clip=self.clip)
+            self.grad_norm = self.opt.grad_norm
+            return loss.detach()
         if self.clip is not None:
             torch.nn.utils.clip_grad_norm_(self.params, self.clip, foreach=True)
         self.opt.step()
@@ -192,6 +207,10 @@ class GraphedTrainStep:
     @torch.no_grad()
     def _update(self):
         """Graph B: mean over the ranks, clip_grad_norm_'s arithmetic on the flat buffer, optimizer step."""
+        if self.hip_tail:
+            self.opt.step(clip=self.clip, grad_scale=1.0 / self.world)
+            self.grad_norm = self.opt.grad_norm
+            return
         bufs = self.flat.buffers
         for buf in bufs:
             buf.mul_(1.0 / self.world)
