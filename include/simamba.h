@@ -25,6 +25,8 @@
  *                                    (per-sample torch.linalg.eigh loop, cuSOLVER underneath).
  *   simamba_spectral_topk            the two above fused: centres -> top-k eigenpairs + orders.
  *   simamba_argsort_rows             the torch.sort of models/point_mamba.py:820.
+ *   simamba_curve_order              no call site: Hilbert / Z-order serialisations of the centres, the baseline the
+ *                                    reference's method is compared with, as a second producer of (B,k,G) orders.
  *   simamba_farthest_point_sample    pytorch3d.ops.sample_farthest_points, models/point_mamba.py:93.
  *   simamba_augment_points           tools/runner_finetune.py:191-194 (fps_idx[:, choice], gather_operation) and the
  *                                    transforms of datasets/data_transforms.py, one launch per batch.
@@ -1105,6 +1107,36 @@ size_t simamba_spectral_workspace_bytes(int B, int G);
 int simamba_spectral_topk(const float* centers, float* evals, float* evecs, long long* order,
                           void* workspace, size_t ws_bytes, int B, int G, int knn, float alpha,
                           int k, unsigned flags, void* stream);
+
+/*
+ * Space-filling-curve orders of the centres (an extension: the reference has none; the Hilbert / trans-Hilbert and
+ * Z-order serialisations its method is measured against, in the (B,k,G) form of the spectral orders).  One launch,
+ * one workgroup per cloud and curve, 2 <= G <= 8192, 1 <= k <= 8 curves, 1 <= bits <= 16 per axis.
+ *   centers : (B,G,3) fp32
+ *   curves  : k curve ids, on the HOST (read before the launch, never after the call returns)
+ *   order   : (B,k,G) int64: the patches of cloud b along curve c, ascending by (code, patch index)
+ *   codes   : (B,k,G) int64 or NULL: codes[b,c,g] = the code of patch g on curve c (by patch, not in sorted order)
+ *   box     : SIMAMBA_CURVE_BOX_CLOUD: lo_a = the minimum of axis a, ext = the largest of the three extents max_a -
+ *             min_a (fp32), both over the finite coordinates of the cloud (an axis without one: lo_a = 0, extent 0);
+ *             box_lo / box_hi are ignored.  SIMAMBA_CURVE_BOX_FIXED: lo_a = box_lo, ext = box_hi - box_lo (fp32) for
+ *             every cloud and axis.
+ * Cell of a coordinate x on axis a, in float64: q = floor(((double)x - (double)lo_a) / (double)ext * 2^bits), clamped
+ * to [0, 2^bits - 1]; a non-finite x: 2^bits - 1; else ext == 0: 0.  Code of a cell (q_x, q_y, q_z): _Z the bit
+ * interleave (bit i of x, y, z at bits 3i+2, 3i+1, 3i), _HILBERT Skilling's transpose algorithm on (x, y, z) read out
+ * with the same interleave; with _TRANS both run on (y, x, z).
+ * Checks in the order shape (SIMAMBA_E_SHAPE: B < 0, G, k, bits), null pointers (centers, curves, order), box mode and
+ * curve ids (SIMAMBA_E_VARIANT), fixed box (SIMAMBA_E_SHAPE: box_lo or box_hi not finite, box_lo >= box_hi); all
+ * before any launch.  B == 0: SIMAMBA_OK, nothing read.  Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_CURVE_Z             0
+#define SIMAMBA_CURVE_HILBERT       1
+#define SIMAMBA_CURVE_TRANS         2   /* or-ed into _Z / _HILBERT: the curve on (y, x, z) */
+#define SIMAMBA_CURVE_Z_TRANS       2
+#define SIMAMBA_CURVE_HILBERT_TRANS 3
+#define SIMAMBA_CURVE_BOX_CLOUD     0
+#define SIMAMBA_CURVE_BOX_FIXED     1
+int simamba_curve_order(const float* centers, const int* curves, long long* order, long long* codes,
+                        int B, int G, int k, int bits, int box, float box_lo, float box_hi, void* stream);
 
 /*
  * Farthest-point sampling (tokeniser step ahead of the hot path; replaces

@@ -24,6 +24,10 @@ SPEC_SIGMA_MEAN = 0x20
 SPEC_LARGE_G = 0x40          # simamba_laplacian_topk_ex: the large-G kernel at G <= 128 too (parity tests only)
 SPEC_MAX_G = 128             # simamba_laplacian_topk and the full-spectrum outputs
 SPEC_MAX_G_LARGE = 512       # graph, simamba_laplacian_topk_ex and the fused call
+# simamba_curve_order (spectral.curve_order): curve ids, box modes and the limits
+CURVE_Z, CURVE_HILBERT, CURVE_TRANS, CURVE_Z_TRANS, CURVE_HILBERT_TRANS = 0, 1, 2, 2, 3
+CURVE_BOX_CLOUD, CURVE_BOX_FIXED = 0, 1
+CURVE_MAX_G, CURVE_MAX_K, CURVE_MAX_BITS = 8192, 8, 16
 
 # forward-scan kernel selection (include/simamba.h): AUTO in production, the others for benchmarks / parity tests
 SCAN_AUTO, SCAN_ROWSCAN, SCAN_LPC2, SCAN_LPC4, SCAN_MIX = 0, 1, 2, 4, 6
@@ -176,6 +180,7 @@ SIGNATURES = {
     "simamba_spectral_topk": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_float,
                                       c_int, c_uint, _P]),
     "simamba_argsort_rows": (c_int, [_P, _P, c_int, c_int, _P]),
+    "simamba_curve_order": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P]),
     "simamba_farthest_point_sample": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "simamba_farthest_point_sample_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
 }

@@ -35,7 +35,9 @@ def default_mae_config(**over):
     tc = dict(mask_ratio=0.6, mask_type="rand", trans_dim=384, encoder_dims=384, depth=12, drop_path_rate=0.1,
               num_heads=6, decoder_depth=4, decoder_num_heads=6,
               method="smallest_eigenvectors_seperate_learnable_tokens", reverse=True, knn_graph=20,
-              k_top_eigenvectors=4, smallest=True, alpha=10, symmetric=True, self_loop=False, binary=True)
+              k_top_eigenvectors=4, smallest=True, alpha=10, symmetric=True, self_loop=False, binary=True,
+              # not in the reference's config: curve orders in the eigen-orders' place (Point_MAE_Mamba.spectral_orders)
+              ordering="spectral", curves=spectral.DEFAULT_CURVES, curve_bits=10, curve_box="cloud")
     top = dict(group_size=32, num_group=64, loss="cdl2", rms_norm=False, use_cls_token=False, drop_path=0.1,
                drop_out=0.1)
     for k, v in over.items():
@@ -209,6 +211,16 @@ class Point_MAE_Mamba(nn.Module):
         self.symmetric = tc.symmetric
         self.self_loop = tc.self_loop
         self.binary = tc.binary
+        # transformer_config.ordering (not in the reference): "spectral", the eigen-orders, or "curve", the orders of
+        # spectral.curve_order with one ordering per curve in k_top_eigenvectors' place
+        self.ordering = getattr(tc, "ordering", "spectral")
+        if self.ordering not in ("spectral", "curve"):
+            raise NotImplementedError(f"transformer_config.ordering {self.ordering!r}: 'spectral' or 'curve'")
+        self.curves = tuple(getattr(tc, "curves", spectral.DEFAULT_CURVES))
+        self.curve_bits = getattr(tc, "curve_bits", 10)
+        self.curve_box = getattr(tc, "curve_box", "cloud")
+        if self.ordering == "curve":
+            spectral.curve_ids(self.curves)
 
     def patch_loss(self, rebuild, gt):
         """(B * Mtok, M, 3) rebuilt and ground-truth patches -> (B * Mtok,) fp32: the configured loss of every patch."""
@@ -217,7 +229,10 @@ class Point_MAE_Mamba(nn.Module):
         return chamfer_distance(rebuild.float(), gt.float())
 
     def spectral_orders(self, center):
-        """:3097 graph (create_graph_from_centers) -> k smallest eigenvectors -> ascending argsort, (B,k,G)."""
+        """:3097 graph (create_graph_from_centers) -> k smallest eigenvectors -> ascending argsort, (B,k,G); with
+        ``ordering: curve`` the curve orders, (B, len(curves), G)."""
+        if self.ordering == "curve":
+            return spectral.curve_order(center, self.curves, self.curve_bits, self.curve_box)
         adj = spectral.create_graph_from_centers(center, self.knn_graph, self.alpha, self.symmetric, self.self_loop,
                                                  self.binary)
         return spectral._eig(adj, self.k_top_eigenvectors, self.smallest, False, want_all=False, want_order=True)[4]

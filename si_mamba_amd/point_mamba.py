@@ -4,7 +4,8 @@ Mirrors reference models/point_mamba.py ``PointMamba`` (:431-562 constructor, :8
 ``method`` in {"SAST" (canonical), "HLT", "MAMBA"}, ``use_wavelets=False``, ``tau=None``) with the parameter names and shapes of the
 reference's own checkpoint table (logs/finetuned_hardest.log:100-426, 12.29 M parameters), so a
 reference state_dict loads unchanged.  What runs on the HIP kernels: the spectral ordering
-(``spectral.spectral_order``) and every Mamba mixer of ``blocks``.
+(``spectral.spectral_order``) and every Mamba mixer of ``blocks``.  ``method: "CURVE"`` is not in the reference: the
+SAST route on space-filling-curve orders (``spectral.curve_order``), the baseline the method is compared with.
 
 ``Group`` (farthest-point sampling + k-NN grouping) and ``Encoder`` (mini-PointNet) sit BEFORE the
 hot path ("next" row 1).  The reference gets FPS / k-NN from pytorch3d CUDA ops
@@ -176,9 +177,16 @@ class PointMamba(nn.Module):
         self.alpha = config.alpha
         self.binary = config.binary
         self.matrix = config.matrix
-        if self.method not in ("SAST", "HLT", "MAMBA"):
+        if self.method not in ("SAST", "HLT", "MAMBA", "CURVE"):
             raise NotImplementedError(f"ordering method {self.method!r}: SAST (:868), HLT (:1054) and MAMBA (:850) "
                                       "are built; the wavelet / RL research branches are out of scope")
+        # method "CURVE" (not in the reference): the SAST route with space-filling-curve orders in the eigen-orders'
+        # place (spectral.curve_order), one ordering per curve -- k_top_eigenvectors is not consulted
+        self.curves = tuple(getattr(config, "curves", spectral.DEFAULT_CURVES))
+        self.curve_bits = getattr(config, "curve_bits", 10)
+        self.curve_box = getattr(config, "curve_box", "cloud")
+        if self.method == "CURVE":
+            spectral.curve_ids(self.curves)                                     # unknown names are refused here
         self.hlt_rand = True          # the reference's torch.rand tie-break of HLT (:1062); tests switch it off
 
     def get_loss_acc(self, ret, gt):
@@ -194,25 +202,32 @@ class PointMamba(nn.Module):
                                        self_loop=self.self_loop, binary=self.binary, matrix=self.matrix)
 
     def spectral_order(self, center):
+        """The (B, n_orders(), G) orders the sequence is gathered by: the eigen-orders (SAST) or the curve orders."""
+        if self.method == "CURVE":
+            return spectral.curve_order(center, self.curves, self.curve_bits, self.curve_box)
         return self.spectral_eigs(center)[2]
 
+    def n_orders(self):
+        """Orderings in a SAST / CURVE sequence (each once more flipped with ``reverse``)."""
+        return len(self.curves) if self.method == "CURVE" else self.k_top_eigenvectors
+
     def _on_tokens(self):
-        """Is the stack handed the G distinct tokens plus an index map (SAST / MAMBA: the sequence is a pure gather of
-        them), not the assembled sequence?  Not with input dropout, which acts on every position by itself, and not
+        """Is the stack handed the G distinct tokens plus an index map (SAST / CURVE / MAMBA: the sequence is a pure gather
+        of them), not the assembled sequence?  Not with input dropout, which acts on every position by itself, and not
         with add_after_layer, whose stack merges whole sequences."""
-        return (not self.add_after_layer and self.method in ("SAST", "MAMBA")
+        return (not self.add_after_layer and self.method in ("SAST", "CURVE", "MAMBA")
                 and not (self.training and self.drop_out.p > 0))
 
     def seq_len(self):
         """Length of token_index()'s rows, known before the centres are."""
         if self.method == "MAMBA":
             return spectral.XYZ_ORDERS * self.num_group
-        return spectral.sast_len(self.k_top_eigenvectors, self.num_group, self.reverse)
+        return spectral.sast_len(self.n_orders(), self.num_group, self.reverse)
 
     def token_index(self, center, order=None):
         """(B, seq_len()) int64 patch index of every sequence position for the routes that are pure gathers (SAST
         :868-989, MAMBA :850-866); None for HLT, whose assembly also writes zeros (:1075-1112)."""
-        if self.method == "SAST":
+        if self.method in ("SAST", "CURVE"):
             if order is None:
                 order = self.spectral_order(center)
             return spectral.sast_index_map(order, self.reverse)
@@ -222,13 +237,13 @@ class PointMamba(nn.Module):
 
     def order_tokens(self, tokens, pos, center, order=None):
         """Tokens and positions in sequence order for ``self.method`` (reference :850-1112)."""
-        if self.method == "SAST" and order is None:
+        if self.method in ("SAST", "CURVE") and order is None:
             order = self.spectral_order(center)
         elif self.method == "HLT":                                              # :1054-1057: the eigenvectors
             adj = spectral.create_graph_from_centers(center, self.knn_graph, self.alpha, self.symmetric,
                                                      self.self_loop, self.binary)
             order = spectral._eig(adj, self.k_top_eigenvectors, self.smallest, False, want_all=False)[1]
-        return spectral.order_tokens(self.method, (tokens, pos), center, order, self.k_top_eigenvectors, self.reverse,
+        return spectral.order_tokens(self.method, (tokens, pos), center, order, self.n_orders(), self.reverse,
                                      self.hlt_rand)
 
     def forward(self, pts, gt=None, tau=None, use_wavelets=False, save_pts_dir=None, epoch=None, *, lengths=None,
@@ -270,8 +285,11 @@ class PointMamba(nn.Module):
         neighborhood, center, _ = self.group_divider(pts, lengths=lengths)
         # The eigen-ordering depends only on the centres and is latency-bound on B of the 256 CUs: run it
         # on a side HIP stream underneath the (MFMA-bound) patch encoder, join before the gather.
-        join = (spectral.run_on_side_stream(lambda: self.spectral_eigs(center), center)
-                if center.is_cuda and self.method == "SAST" else None)
+        join = None
+        if center.is_cuda and self.method == "SAST":
+            join = spectral.run_on_side_stream(lambda: self.spectral_eigs(center), center)
+        elif center.is_cuda and self.method == "CURVE":                         # the orders alone: no eigenpairs
+            join = spectral.run_on_side_stream(lambda: (None, None, self.spectral_order(center)), center)
         tokens = self.encoder(neighborhood)
         pos = self.pos_embed(center)
         spec = join() if join is not None else None

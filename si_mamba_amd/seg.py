@@ -143,16 +143,25 @@ class PartSegMamba(nn.Module):
         self.self_loop = config.self_loop
         self.alpha = config.alpha
         self.binary = config.binary
-        if self.method not in ("HLT", "SAST", "Point_MAMBA"):
+        if self.method not in ("HLT", "SAST", "Point_MAMBA", "CURVE"):
             raise NotImplementedError(f"ordering method {self.method!r}")
+        # method "CURVE" (not in the reference): the SAST branch on spectral.curve_order's orders, one per curve
+        self.curves = tuple(getattr(config, "curves", spectral.DEFAULT_CURVES))
+        self.curve_bits = getattr(config, "curve_bits", 10)
+        self.curve_box = getattr(config, "curve_box", "cloud")
+        if self.method == "CURVE":
+            spectral.curve_ids(self.curves)
         self.hlt_rand = True          # the reference's torch.rand tie-break (:655); tests switch it off
 
     # ---- token ordering ------------------------------------------------------------------------------------------
     def _spectral(self, center):
-        """What the ordering needs from the eigen-solver: eigenvectors (HLT) or the k argsorts (SAST); None otherwise.
+        """What the ordering needs from the eigen-solver: eigenvectors (HLT) or the k argsorts (SAST); the curve orders
+        in their place (CURVE); None otherwise.
         Depends on the centres only, so forward() runs it on a side stream underneath the patch encoder."""
         if self.method == "Point_MAMBA":
             return None
+        if self.method == "CURVE":
+            return spectral.curve_order(center, self.curves, self.curve_bits, self.curve_box)
         adj = spectral.create_graph_from_centers(center, self.knn_graph, self.alpha, self.symmetric, self.self_loop,
                                                  self.binary)
         if self.method == "HLT":                                                # :667-668
@@ -164,8 +173,8 @@ class PartSegMamba(nn.Module):
         :665-723, SAST :725-759 (the graph is create_graph_from_centers here, not the feature-space variant)."""
         if spec is None:
             spec = self._spectral(center)
-        return spectral.order_tokens(self.method, (tokens, pos, center), center, spec, self.k_top_eigenvectors,
-                                     self.reverse, self.hlt_rand)
+        k = len(self.curves) if self.method == "CURVE" else self.k_top_eigenvectors
+        return spectral.order_tokens(self.method, (tokens, pos, center), center, spec, k, self.reverse, self.hlt_rand)
 
     # ---- forward -------------------------------------------------------------------------------------------------
     def forward(self, pts, cls_label, *, lengths=None):

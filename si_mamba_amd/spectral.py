@@ -154,6 +154,55 @@ def spectral_order(center, knn_graph, alpha, k_top_eigenvectors, smallest=True, 
     return vals, vecs, order
 
 
+# curve name -> id of include/simamba.h (SIMAMBA_CURVE_*)
+CURVES = {"z": _lib.CURVE_Z, "hilbert": _lib.CURVE_HILBERT, "z-trans": _lib.CURVE_Z_TRANS,
+          "hilbert-trans": _lib.CURVE_HILBERT_TRANS}
+DEFAULT_CURVES = ("hilbert", "hilbert-trans", "z", "z-trans")
+
+
+def curve_ids(curves):
+    """The host array of curve ids simamba_curve_order reads for a sequence of curve names; the library reads it inside
+    the call, so it lives as long as the caller's reference."""
+    import ctypes
+    curves = tuple(curves)
+    unknown = [c for c in curves if c not in CURVES]
+    if unknown:
+        raise ValueError(f"curve_order: unknown curves {unknown}; the curves are {sorted(CURVES)}")
+    if not 1 <= len(curves) <= _lib.CURVE_MAX_K:
+        raise ValueError(f"curve_order: 1 to {_lib.CURVE_MAX_K} curves per call, got {len(curves)}")
+    return (ctypes.c_int * len(curves))(*(CURVES[c] for c in curves))
+
+
+def curve_order(center, curves=DEFAULT_CURVES, bits=10, box="cloud", return_codes=False):
+    """Space-filling-curve orders: centres (B,G,3) -> order (B, len(curves), G) int64, each row the patches along one
+    curve (ascending code, ties by patch index), the same contract as spectral_order's orders; 2 <= G <= 8192, one
+    launch.  An extension: the reference has no such orders -- they are the baseline it is compared with.
+
+    ``curves``: names out of CURVES ("z" Morton order, "hilbert", and "-trans" for either on (y, x, z)).  ``bits``:
+    lattice bits per axis, 1..16.  ``box``: "cloud" -- each cloud's own isotropic cube (its per-axis minimum and its
+    largest extent: the order does not change under translation and uniform scaling) -- or ``(lo, hi)``, one fixed cube
+    for every cloud and axis, e.g. (-1, 1) after pc_norm.  ``return_codes``: also the (B, len(curves), G) int64 code of
+    every patch on every curve.  Curve orders are not rotation invariant."""
+    _lib.require_gpu(center, "curve_order")
+    ids = curve_ids(curves)
+    c = center.detach().float().contiguous()
+    if c.dim() != 3 or c.shape[-1] != 3:
+        raise ValueError("curve_order expects (B, G, 3) centres")
+    B, G, _ = c.shape
+    if isinstance(box, str):
+        if box != "cloud":
+            raise ValueError(f"curve_order: box is 'cloud' or a (lo, hi) pair, got {box!r}")
+        mode, lo, hi = _lib.CURVE_BOX_CLOUD, 0.0, 0.0
+    else:
+        lo, hi = (float(v) for v in box)
+        mode = _lib.CURVE_BOX_FIXED
+    k = len(ids)
+    order = torch.empty(B, k, G, device=c.device, dtype=torch.int64)
+    codes = torch.empty(B, k, G, device=c.device, dtype=torch.int64) if return_codes else None
+    _lib.call("simamba_curve_order", c, ids, order, codes, B, G, k, int(bits), mode, lo, hi, device=c.device)
+    return (order, codes) if return_codes else order
+
+
 def sast_len(k, G, reverse=True):
     """Length of sast_index_map's rows for (B,k,G) orders."""
     return k * G * (2 if reverse else 1)
@@ -237,11 +286,12 @@ def order_tokens(method, tensors, center, spec, k, reverse=True, hlt_rand=True):
     """Every (B,G,*) tensor of ``tensors`` in sequence order, for the three orderings the models share.  ``spec``: what
     the eigen-solver gave for the method, from either spectral route -- the (B,k,G) argsorts for "SAST" (:868-989), the
     (B,G,k) eigenvectors for "HLT" (:1054-1112, with the reference's torch.rand tie-break of :1062 drawn here unless
-    ``hlt_rand`` is off); the xyz-sorted copies ("MAMBA" / "Point_MAMBA", :850-866) need none."""
+    ``hlt_rand`` is off); the xyz-sorted copies ("MAMBA" / "Point_MAMBA", :850-866) need none.  "CURVE" (curve_order's
+    (B,k,G) orders as ``spec``) assembles exactly as SAST does."""
     if method == "HLT":
         rand = torch.rand(center.shape[0], center.shape[1], device=center.device) if hlt_rand else None
         return hlt_take(tensors, spec, k, rand)[0]
-    if method == "SAST":
+    if method in ("SAST", "CURVE"):
         idx = sast_index_map(spec, reverse)
     elif method in ("MAMBA", "Point_MAMBA"):
         idx = xyz_sorted_index(center)
