@@ -1032,6 +1032,67 @@ int simamba_dataset_fetch(const float* points, const long long* offsets, const l
 int simamba_keyed_perm(long long seed, long long tweak, long long n, long long first, long long count, long long* out);
 
 /*
+ * Damage to a batch of clouds (csrc/corrupt.hip; the families of ModelNet-C, Ren et al. 2022): one kind per call, one
+ * launch, one workgroup per cloud, followed by a one-lane kernel that adds 1 to the step.
+ *   points      : (B, N, 3) fp32.                                     1 <= N <= K <= 8192 ; 1 <= B < 2^31.
+ *   lengths     : (B) int64, device, or NULL (= N everywhere): cloud b has n = clamp(lengths[b], 1, N) rows; the rows
+ *                 behind them are never read.
+ *   out         : (B, K, 3) fp32; it may not overlap points (SIMAMBA_E_VARIANT).  out_lengths : (B) int64.
+ *   src         : (B, K) int32 or NULL: the input row an output row came from, or a negative code for an added row.
+ *                 Rows of out at and behind out_lengths[b] are written as 0, src there as INT_MIN.
+ *   state       : (2) int64 [seed, step], the layout of simamba_augment_points.  Read by the kernel; step + 1 is written
+ *                 behind it in stream order.  Nothing is read on the host, so the call can be captured.
+ *   kind, flags : HOST integers;  params : HOST array of 4 fp32, read during the call (unused slots are ignored).
+ * Random numbers: Philox4x32-10 with the counter of simamba_augment_points at chain position 0,
+ *     c0 = the block number for a per-cloud draw, the row or the added point's number for a per-point draw
+ *     c1 = the cloud b ;  c2 = step & 0xffffffff ;  c3 = ((step >> 32) & 0x0fffffff) | (per-point ? 1 : 0) << 31
+ *   under the key (seed & 0xffffffff, (seed >> 32) ^ SIMAMBA_CORRUPT_KEY_TWEAK): one state feeds both calls without
+ *   sharing a stream.  u(w) = (w >> 8) * 2^-24; normal(block) = the three Box-Muller normals of simamba_augment_points.
+ *   "cloud block k" below is per-cloud block k, "block t" per-point block t; w0..w3 are a block's words.
+ * Kinds (params):
+ *   DROP_GLOBAL (rho)          m = min((int)(float(n) * rho), n - 1).  Removed: the m rows with the smallest
+ *                              (w0 of block i, i).  Survivors keep their order; out_len = n - m; src = the input row.
+ *   DROP_LOCAL  (T, Cmax)      C = min(1 + (int)(u(cloud block 0, w0) * float(Cmax)), Cmax); T' = min(T, n - 1); cluster
+ *                              j < C removes T' / C + (j < T' % C) rows, the clusters in order, each on the `a` rows
+ *                              still alive: its seed is the alive row of rank min((int)(u(cloud block 1 + j, w0) *
+ *                              float(a)), a - 1) in index order; removed are the alive rows with the smallest (d2, i),
+ *                              d2 = (dx dx + dy dy) + dz dz in fp32 from the seed.  out_len = n - T'.
+ *   ADD_GLOBAL  (A, R)         A_b = min(A, K - n) points behind the cloud's own rows, which are copied bit for bit.
+ *                              Point t from block t: a = 2 u(w1), z = 1 - a, s = sqrt(a (2 - a)), phi = fp32(2 pi) u(w2),
+ *                              r = R cbrt(u(w0)), p = r (s cos phi, s sin phi, z): uniform in the ball.  src = -1.
+ *   ADD_LOCAL   (T, Cmax, lo, hi)  C and the cluster sizes as in DROP_LOCAL over T_b = min(T, K - n).  Cluster j: the
+ *                              seed is input row min((int)(u(cloud block 1 + j, w0) * float(n)), n - 1), sigma_j = lo +
+ *                              u(cloud block 1 + j, w1) * (hi - lo).  Point t belongs to the cluster whose prefix of
+ *                              sizes holds t: p = seed_j + sigma_j * normal(block t).  src = -1 - j.
+ *   ROTATE3     (theta)        angle_a = (2 u(cloud block 0, w_a) - 1) * theta for a = x, y, z; p' = Rz Ry Rx p.
+ *   SCALE_AXES  (s >= 1)       f_a = 1 / s + u(cloud block 0, w_a) * (s - 1 / s); p'_a = p_a f_a.
+ *   JITTER      (sigma)        p' = p + sigma * normal(block i); no clip.
+ *   Every product, sum and quotient named above is one correctly rounded fp32 operation (no contraction) and every (int)
+ *   truncates, so the counts, seeds, clusters, angles and factors can be reproduced bit for bit; cos, sin, cbrt and ln
+ *   are the device library's.  Non-finite coordinates make the choice of rows unspecified and nothing else.
+ * flags: SIMAMBA_CORRUPT_RENORM applies the unit-sphere normalisation of simamba_dataset_fetch to the out_len rows of
+ *   the result (relative to output row 0; the sum runs per lane over its 8 consecutive rows, then as stated there).
+ * The result for (seed, step, b, cloud b's rows, kind, params, N, K) depends on nothing else: not on B or the other clouds.
+ * Checks in the order shape (SIMAMBA_E_SHAPE: B, N, K, K < N), null pointers (points, out, out_lengths, state, params),
+ * SIMAMBA_E_VARIANT for an unknown kind or flag bit, rho outside [0, 1), a negative or NaN count, Cmax not an integer in
+ * [1, 8], s < 1, then for an overlap of out and points; all before any launch.  Counts above 8192 act as 8192.
+ * Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_CORRUPT_DROP_GLOBAL  1
+#define SIMAMBA_CORRUPT_DROP_LOCAL   2
+#define SIMAMBA_CORRUPT_ADD_GLOBAL   3
+#define SIMAMBA_CORRUPT_ADD_LOCAL    4
+#define SIMAMBA_CORRUPT_ROTATE3      5
+#define SIMAMBA_CORRUPT_SCALE_AXES   6
+#define SIMAMBA_CORRUPT_JITTER       7
+#define SIMAMBA_CORRUPT_RENORM       1
+#define SIMAMBA_CORRUPT_MAX_CLUSTERS 8
+#define SIMAMBA_CORRUPT_KEY_TWEAK    0x434F5252u
+int simamba_corrupt_points(const float* points, const long long* lengths, float* out, long long* out_lengths, int* src,
+                           long long* state, int kind, int flags, const float* params, long long B, int N, int K,
+                           void* stream);
+
+/*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,
  * K=group_size, return_sorted=False)): idx[b][g][0..K) = the K points of cloud b nearest to centre g, ascending
  * squared distance (direct differences), ties to the lower point index.

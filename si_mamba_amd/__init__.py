@@ -21,6 +21,8 @@ from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRand
                          PointcloudScale, PointcloudScaleAndTranslate, PointcloudTranslate, RandomHorizontalFlip,
                          sample_and_augment)
 from .vote import vote_logits
+from . import corruptions
+from .corruptions import KINDS, SEVERITY, corrupt, evaluate_robustness
 from . import data
 from . import optim
 from .data import Batch, DeviceDataset, DeviceLoader
@@ -29,6 +31,7 @@ from ._lib import deterministic, deterministic_enabled, set_deterministic
 __all__ = ["data", "Batch", "DeviceDataset", "DeviceLoader", "transforms", "AugmentState", "Compose", "PointcloudJitter", "PointcloudRandomInputDropout",
            "PointcloudRotate", "PointcloudScale", "PointcloudScaleAndTranslate", "PointcloudTranslate",
            "RandomHorizontalFlip", "sample_and_augment", "vote_logits",
+           "corruptions", "KINDS", "SEVERITY", "corrupt", "evaluate_robustness",
 "SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
            "set_deterministic", "earth_movers_distance", "sinkhorn_divergence", "OvOLinearSVC", "evaluate_svm", "manifold",

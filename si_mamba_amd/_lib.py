@@ -51,6 +51,13 @@ DS_FIRST, DS_PERMUTE, DS_CHOICE = 0, 1, 2
 DS_NONE, DS_UNIT_SPHERE = 0, 1
 DS_STREAM_SHUFFLE, DS_STREAM_ROWS, DS_STREAM_CHOICE = 1, 2, 3
 DS_MAX_POINTS = 8192
+# kinds and the flag of simamba_corrupt_points (corruptions.py); the tweak of its Philox key's high word
+(CORRUPT_DROP_GLOBAL, CORRUPT_DROP_LOCAL, CORRUPT_ADD_GLOBAL, CORRUPT_ADD_LOCAL, CORRUPT_ROTATE3, CORRUPT_SCALE_AXES,
+ CORRUPT_JITTER) = 1, 2, 3, 4, 5, 6, 7
+CORRUPT_RENORM = 1
+CORRUPT_MAX_CLUSTERS = 8
+CORRUPT_KEY_TWEAK = 0x434F5252
+CORRUPT_MAX_POINTS = 8192
 # simamba_optim_adamw_step (optim/adamw.py): elements per chunk-table entry, the table limits, the flag
 OPTIM_CHUNK = 4096
 OPTIM_MAX_SEGMENTS, OPTIM_MAX_CHUNKS, OPTIM_MAX_GROUPS = 65536, 1 << 20, 256
@@ -170,6 +177,7 @@ SIGNATURES = {
     "simamba_dataset_fetch": (c_int, [_P] * 10 + [_LL, _LL, _LL, _LL, c_int, c_int, _LL, c_int, c_int, c_int, c_int,
                                       c_int, _P]),
     "simamba_keyed_perm": (c_int, [_LL, _LL, _LL, _LL, _LL, _P]),
+    "simamba_corrupt_points": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _LL, c_int, c_int, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),

@@ -18,7 +18,7 @@
 // __fmul_rn / __fadd_rn, so each is one correctly rounded fp32 operation and a numpy float32 restatement reproduces the
 // drawn parameters and the keep / flip decisions bit for bit.  cos / sin / log are the device library's.
 #include "host_common.h"
-#include "philox.h"
+#include "philox_draws.h"
 #include "pointset.h"
 
 namespace simamba {
@@ -54,25 +54,9 @@ __device__ __forceinline__ Philox4 aug_block(const AugRng& r, int pos, bool per_
   return philox4x32_10(r.k0, r.k1, index, r.cloud, r.step_lo, c3);
 }
 
-__device__ __forceinline__ float aug_uniform(uint32_t w) {           // [0, 1), a multiple of 2^-24: exact
-  return static_cast<float>(w >> 8) * 0x1p-24f;
-}
-
-// Box-Muller: two standard normals from two words; the logarithm's argument is in (0, 1], the angle 2 pi u as 2 u half turns
-__device__ __forceinline__ void aug_normal_pair(uint32_t wa, uint32_t wb, float& n0, float& n1) {
-  const float a = static_cast<float>((wa >> 8) + 1u) * 0x1p-24f;
-  const float r = sqrtf(__fmul_rn(-2.f, logf(a)));
-  float s, c;
-  sincospif(__fmul_rn(2.f, aug_uniform(wb)), &s, &c);
-  n0 = __fmul_rn(r, c);
-  n1 = __fmul_rn(r, s);
-}
-
+// aug_uniform and the Box-Muller normals: philox_draws.h, shared with corrupt.hip
 __device__ __forceinline__ void aug_point_normals(const AugRng& r, int pos, int i, float& n0, float& n1, float& n2) {
-  const Philox4 q = aug_block(r, pos, true, static_cast<uint32_t>(i));
-  float unused;
-  aug_normal_pair(q.w[0], q.w[1], n0, n1);
-  aug_normal_pair(q.w[2], q.w[3], n2, unused);
+  aug_block_normals(aug_block(r, pos, true, static_cast<uint32_t>(i)), n0, n1, n2);
 }
 
 __device__ __forceinline__ float aug_point_uniform(const AugRng& r, int pos, int i) {

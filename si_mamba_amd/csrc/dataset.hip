@@ -20,6 +20,7 @@
 // __fsqrt_rn, one correctly rounded fp32 operation each, in an order the header states.
 #include "host_common.h"
 #include "keyed_perm.h"
+#include "unit_sphere.h"
 
 namespace simamba {
 
@@ -38,27 +39,6 @@ struct DsArgs {                                            // by value in the ke
   long long total, S, stride, steps_per_epoch;
   int K, first, rank, world, order, rows, norm;
 };
-
-// the sum of v over the workgroup in a fixed order (lanes by butterfly, then the waves in ascending order), in every lane
-__device__ __forceinline__ float ds_block_sum(float v, float* s, int lane, int wave, int waves) {
-  v = wave_xor_sum(v);
-  __syncthreads();                                         // the row may still be read from the call before
-  if (lane == 0) s[wave] = v;
-  __syncthreads();
-  float t = s[0];
-  for (int w = 1; w < waves; ++w) t = __fadd_rn(t, s[w]);
-  return t;
-}
-
-__device__ __forceinline__ float ds_block_max(float v, float* s, int lane, int wave, int waves) {
-  v = wave_xor_max(v);
-  __syncthreads();
-  if (lane == 0) s[wave] = v;
-  __syncthreads();
-  float t = s[0];
-  for (int w = 1; w < waves; ++w) t = fmaxf(t, s[w]);
-  return t;
-}
 
 __global__ __launch_bounds__(kDsMaxThreads) void dataset_fetch_kernel(
     const float* __restrict__ points, const long long* __restrict__ offsets, const long long* __restrict__ labels,
@@ -139,40 +119,10 @@ __global__ __launch_bounds__(kDsMaxThreads) void dataset_fetch_kernel(
       sFirst[2] = z[0];
     }
     __syncthreads();
-    const float fx = sFirst[0], fy = sFirst[1], fz = sFirst[2];
-    float sx = 0.f, sy = 0.f, sz = 0.f;
+    unsigned valid = 0;
 #pragma unroll
-    for (int j = 0; j < kDsPerLane; ++j) {
-      if (tid + j * T < len) {
-        x[j] = __fsub_rn(x[j], fx);
-        y[j] = __fsub_rn(y[j], fy);
-        z[j] = __fsub_rn(z[j], fz);
-        sx = __fadd_rn(sx, x[j]);
-        sy = __fadd_rn(sy, y[j]);
-        sz = __fadd_rn(sz, z[j]);
-      }
-    }
-    const float flen = static_cast<float>(len);                      // exact: len <= 8192
-    const float mx = __fdiv_rn(ds_block_sum(sx, sRed, lane, wave, waves), flen);
-    const float my = __fdiv_rn(ds_block_sum(sy, sRed, lane, wave, waves), flen);
-    const float mz = __fdiv_rn(ds_block_sum(sz, sRed, lane, wave, waves), flen);
-    float big = 0.f;                                                 // the largest squared norm; a NaN is passed over
-#pragma unroll
-    for (int j = 0; j < kDsPerLane; ++j) {
-      if (tid + j * T < len) {
-        x[j] = __fsub_rn(x[j], mx);
-        y[j] = __fsub_rn(y[j], my);
-        z[j] = __fsub_rn(z[j], mz);
-        big = fmaxf(big, __fadd_rn(__fadd_rn(__fmul_rn(x[j], x[j]), __fmul_rn(y[j], y[j])), __fmul_rn(z[j], z[j])));
-      }
-    }
-    const float m = __fsqrt_rn(ds_block_max(big, sRed, lane, wave, waves));
-#pragma unroll
-    for (int j = 0; j < kDsPerLane; ++j) {                           // all rows coincide (m == 0): zeros, no 0 / 0
-      x[j] = m > 0.f ? __fdiv_rn(x[j], m) : 0.f;
-      y[j] = m > 0.f ? __fdiv_rn(y[j], m) : 0.f;
-      z[j] = m > 0.f ? __fdiv_rn(z[j], m) : 0.f;
-    }
+    for (int j = 0; j < kDsPerLane; ++j) valid |= (tid + j * T < len ? 1u : 0u) << j;
+    unit_sphere_rows(x, y, z, valid, len, sFirst[0], sFirst[1], sFirst[2], sRed, lane, wave, waves);
   }
 
 #pragma unroll

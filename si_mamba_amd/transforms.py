@@ -289,6 +289,17 @@ def sample_and_augment(points, transforms=None, idx=None, sel=None, lengths=None
     return out
 
 
+def launch_corrupt(points, lengths, out, out_lengths, src, state, kind, flags, params):
+    """The launch of ``corruptions.corrupt`` on checked arguments (csrc/corrupt.hip reads and advances the same
+    ``AugmentState`` as the call above, so the two launches live side by side): ``points`` (B, N, 3) and ``out``
+    (B, K, 3) contiguous float32, ``lengths`` (B,) int64 or None, ``out_lengths`` (B,) int64, ``src`` (B, K) int32 or
+    None, ``kind`` / ``flags`` the ABI's integers, ``params`` its host array of four floats."""
+    B, N, _ = points.shape
+    _lib.count("corrupt_points")
+    _lib.call("simamba_corrupt_points", points, lengths, out, out_lengths, src, state.tensor, kind, flags, params, B, N,
+              out.shape[1], device=points.device, time_as="corrupt_points")
+
+
 def augment_params(transforms, B, K, state=None, lengths=None, noise=False, keep=False, device=None):
     """What the next ``sample_and_augment`` with this chain and state will draw, without touching points or the step:
     ``(cloud_params (B, n_ops, 8) float32, noise (B, K, 3) float32 | None, keep (B, K) bool | None)``; the layout of
