@@ -1093,6 +1093,81 @@ int simamba_corrupt_points(const float* points, const long long* lengths, float*
                            void* stream);
 
 /*
+ * Training-time augmentations the corruption score is lowered with (csrc/mix.hip): PointCutMix-R / -K (Zhang et al.
+ * 2021) and a locally weighted deformation after PointWOLF (Kim et al. 2021).  One launch each, one workgroup per
+ * output cloud, followed by a one-lane kernel that adds 1 to the step.
+ *   state       : (2) int64 [seed, step], the layout of simamba_augment_points.  Read by the kernel; step + 1 is written
+ *                 behind it in stream order.  Nothing is read on the host, so the calls can be captured.
+ * Random numbers: the counter of simamba_corrupt_points (augment's at chain position 0; c1 = the OUTPUT cloud b) under
+ *   the key (seed & 0xffffffff, (seed >> 32) ^ SIMAMBA_MIX_KEY_TWEAK), which differs from corrupt's: one state feeds
+ *   augment, corrupt and mix without sharing a stream.  u(w) = (w >> 8) * 2^-24.  "cloud block k" is per-cloud block k,
+ *   "block i" per-point block i; w0..w3 are a block's words.
+ *   Every product, sum and quotient named below is one correctly rounded fp32 operation (no contraction) and every (int)
+ *   truncates, so every discrete decision can be reproduced bit for bit; cos, sin and exp are the device library's.
+ *   Non-finite coordinates make the choice of rows and anchors unspecified and nothing else.
+ *
+ * simamba_cutmix_points: m rows of cloud b are replaced by m rows of its partner q.
+ *   points      : (B, N, 3) fp32.                                     1 <= N <= 8192 ; 1 <= B < 2^31.
+ *   lengths     : (B) int64, device, or NULL (= N everywhere): cloud b has n_b = clamp(lengths[b], 1, N) rows; the rows
+ *                 behind them are never read.
+ *   partner     : (B) int64, device, or NULL.  Given: q = clamp(partner[b], 0, B - 1), on the device (nothing may be
+ *                 read on the host).  NULL: q = perm(n = B, the key above, stream = step, b), the bijection of
+ *                 csrc/keyed_perm.h: what simamba_keyed_perm(seed ^ (SIMAMBA_MIX_KEY_TWEAK << 32), step, B, b, 1, .)
+ *                 answers on the host.  q == b is allowed: the result is then made of the cloud's own rows.
+ *   lam         : (B) fp32, device, or NULL.  Given: lambda = lam[b] forced into [0, 1] on the device, a NaN becomes 0.
+ *                 NULL: lambda = u(cloud block 0, w0).  A Beta-distributed lambda is the caller's to draw and pass in.
+ *   m = min((int)(float(n_b) * lambda), n_b, n_q).      ratio : (B) fp32 out, ratio[b] = float(m) / float(n_b).
+ *   out         : (B, N, 3) fp32; it may not overlap points at all (SIMAMBA_E_VARIANT): other workgroups read the
+ *                 partner's rows.  Rows [0, n_b - m): the cloud's surviving rows in their input order; rows
+ *                 [n_b - m, n_b): the partner's chosen rows in the partner's input order, where they are (no
+ *                 translation); rows behind n_b: 0.  Copied rows are bit-for-bit copies.
+ *   src         : (B, N) int32 or NULL: the own input row i (>= 0), -1 - i for partner row i, INT_MIN behind n_b.
+ *   mode SIMAMBA_MIX_CUT_R: removed are the m own rows with the smallest (w0 of block i, i), taken the m partner rows
+ *                 with the smallest (w1 of block i, i); both blocks under c1 = b.
+ *   mode SIMAMBA_MIX_CUT_K: the own seed row is min((int)(u(cloud block 1, w0) * float(n_b)), n_b - 1), the partner's
+ *                 min((int)(u(cloud block 1, w1) * float(n_q)), n_q - 1); removed are the m own rows with the smallest
+ *                 (d2, i) from the own seed, taken the m partner rows with the smallest (d2, i) from the partner's seed;
+ *                 d2 = (dx dx + dy dy) + dz dz in fp32 by direct differences, its bits ordered as unsigned (DROP_LOCAL).
+ *   Checks in the order shape (SIMAMBA_E_SHAPE: B, N), null pointers (points, out, ratio, state), an unknown mode
+ *   (SIMAMBA_E_VARIANT), an overlap of out and points (SIMAMBA_E_VARIANT); all before any launch.
+ *
+ * simamba_mix_draw: partner (B) int64 and / or lam (B) fp32 (either may be NULL, not both) as simamba_cutmix_points
+ *   draws them from NULL at the state's present step, for the label arithmetic on top; the step is not advanced.
+ *   Checks: B (SIMAMBA_E_SHAPE), state and both outputs NULL (SIMAMBA_E_NULLPTR).
+ *
+ * simamba_pointwolf_points: written from the paper's description, not a reproduction of its draws.
+ *   points, lengths as above.  out : (B, N, 3) fp32; it may be points itself (the exact alias), any other overlap is
+ *   refused (SIMAMBA_E_VARIANT).  Rows behind the length are written as 0.  1 <= M <= SIMAMBA_WOLF_MAX_ANCHORS anchors.
+ *   params      : HOST array of 4 fp32 {sigma > 0, rot >= 0, scale >= 1, trans >= 0}, all finite, read during the call.
+ *   anchors_out : (B, M) int32 or NULL.  Anchor 0 is row min((int)(u(cloud block 0, w0) * float(n)), n - 1); anchor k is
+ *                 the row with the largest minimum d2 (as above) to anchors 0 .. k - 1, ties to the lower row.
+ *   Anchor j at a_j, a = x, y, z:  angle_a = (2 u(cloud block 1 + j, w_a) - 1) * rot;
+ *                 f_a = 1 + u(cloud block 9 + j, w_a) * (scale - 1), replaced by 1 / f_a when bit 31 of that block's
+ *                 w3 is set (one bit for the three axes);  t_a = (2 u(cloud block 17 + j, w_a) - 1) * trans.
+ *                 q_j(p) = ((Rz Ry Rx ((p - a_j) * f_j)) + a_j) + t_j, the rotation as ROTATE3 of simamba_corrupt_points.
+ *   Blend:        w_j(p) = expf(-((d2(p, a_j) - min_k d2(p, a_k)) * c)), c = fp32(1 / (2 sigma^2)) formed in double on
+ *                 the host and rounded once (SIMAMBA_E_VARIANT when it is not finite);
+ *                 p' = (sum_j w_j q_j) / (sum_j w_j), both sums from 0 in ascending j; the nearest anchor's weight is
+ *                 exp(0) = 1, so the divisor is at least 1 whatever sigma is.
+ *   flags: SIMAMBA_WOLF_RENORM applies the unit-sphere normalisation of simamba_dataset_fetch to the n rows of the result
+ *   (relative to row 0; the sum runs per lane over its 8 consecutive rows, then as stated there).
+ *   Checks in the order shape (SIMAMBA_E_SHAPE: B, N, M), null pointers (points, out, state, params), SIMAMBA_E_VARIANT
+ *   for an unknown flag bit or a parameter outside the ranges above, then for a partial overlap; all before any launch.
+ * Still ABI version 9: symbols added, none changed.
+ */
+#define SIMAMBA_MIX_CUT_R         1
+#define SIMAMBA_MIX_CUT_K         2
+#define SIMAMBA_MIX_KEY_TWEAK     0x4D495847u
+#define SIMAMBA_WOLF_RENORM       1
+#define SIMAMBA_WOLF_MAX_ANCHORS  8
+int simamba_cutmix_points(const float* points, const long long* lengths, const long long* partner, const float* lam,
+                          float* out, float* ratio, int* src, long long* state, int mode, long long B, int N,
+                          void* stream);
+int simamba_mix_draw(long long* partner, float* lam, const long long* state, long long B, void* stream);
+int simamba_pointwolf_points(const float* points, const long long* lengths, float* out, int* anchors_out,
+                             long long* state, int M, const float* params, int flags, long long B, int N, void* stream);
+
+/*
  * k-NN grouping of the tokeniser (reference models/point_mamba.py:96: pytorch3d.ops.knn_points(center, xyz,
  * K=group_size, return_sorted=False)): idx[b][g][0..K) = the K points of cloud b nearest to centre g, ascending
  * squared distance (direct differences), ties to the lower point index.

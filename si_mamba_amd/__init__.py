@@ -23,6 +23,8 @@ from .transforms import (AugmentState, Compose, PointcloudJitter, PointcloudRand
 from .vote import vote_logits
 from . import corruptions
 from .corruptions import KINDS, SEVERITY, corrupt, evaluate_robustness
+from . import mixing
+from .mixing import cutmix, mixed_cross_entropy, mixup, pointwolf
 from . import data
 from . import optim
 from .data import Batch, DeviceDataset, DeviceLoader
@@ -35,4 +37,4 @@ __all__ = ["data", "Batch", "DeviceDataset", "DeviceLoader", "transforms", "Augm
 "SHAPENETPART", "PartSegMetrics", "PartTable", "part_seg_eval","causal_conv1d_fn", "selective_scan_fn", "Mamba", "Block", "MixerModel", "create_block",
            "DropPath", "RMSNorm", "spectral", "install_shim", "deterministic", "deterministic_enabled",
            "set_deterministic", "earth_movers_distance", "sinkhorn_divergence", "OvOLinearSVC", "evaluate_svm", "manifold",
-           "TSNE", "optim"]
+           "TSNE", "optim", "mixing", "cutmix", "pointwolf", "mixup", "mixed_cross_entropy"]

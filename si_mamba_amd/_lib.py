@@ -58,6 +58,12 @@ CORRUPT_RENORM = 1
 CORRUPT_MAX_CLUSTERS = 8
 CORRUPT_KEY_TWEAK = 0x434F5252
 CORRUPT_MAX_POINTS = 8192
+# modes of simamba_cutmix_points, the flag and the anchor limit of simamba_pointwolf_points (mixing/); the tweak of
+# their Philox key's high word, which differs from corrupt's
+MIX_CUT_R, MIX_CUT_K = 1, 2
+MIX_KEY_TWEAK = 0x4D495847
+WOLF_RENORM = 1
+WOLF_MAX_ANCHORS = 8
 # simamba_optim_adamw_step (optim/adamw.py): elements per chunk-table entry, the table limits, the flag
 OPTIM_CHUNK = 4096
 OPTIM_MAX_SEGMENTS, OPTIM_MAX_CHUNKS, OPTIM_MAX_GROUPS = 65536, 1 << 20, 256
@@ -178,6 +184,9 @@ SIGNATURES = {
                                       c_int, _P]),
     "simamba_keyed_perm": (c_int, [_LL, _LL, _LL, _LL, _LL, _P]),
     "simamba_corrupt_points": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _LL, c_int, c_int, _P]),
+    "simamba_cutmix_points": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _LL, c_int, _P]),
+    "simamba_mix_draw": (c_int, [_P, _P, _P, _LL, _P]),
+    "simamba_pointwolf_points": (c_int, [_P, _P, _P, _P, _P, c_int, _P, c_int, _LL, c_int, _P]),
     "simamba_knn_group": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_group_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "simamba_knn_graph": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint, _P]),

@@ -1,6 +1,6 @@
-// The maps from Philox words to the values the point kernels draw (augment.hip, corrupt.hip): one text for both, so the
-// uniform and the Box-Muller normals of one are those of the other bit for bit.  Device only; the translation unit is
-// built with -ffp-contract=off, every product here is one correctly rounded fp32 operation.
+// The maps from Philox words to the values the point kernels draw (augment.hip, corrupt.hip, mix.hip): one text for
+// all, so the uniform and the Box-Muller normals of one are those of the others bit for bit.  Device only; the
+// translation unit is built with -ffp-contract=off, every product here is one correctly rounded fp32 operation.
 #pragma once
 #include "philox.h"
 

@@ -1,5 +1,5 @@
-// pc_norm of a cloud held in the registers of one workgroup (dataset.hip, corrupt.hip): subtract the mean of the valid
-// rows, divide by their largest norm.  One text for both kernels; the arithmetic and its order are stated in
+// pc_norm of a cloud held in the registers of one workgroup (dataset.hip, corrupt.hip, mix.hip): subtract the mean of
+// the valid rows, divide by their largest norm.  One text for both kernels; the arithmetic and its order are stated in
 // include/simamba.h under simamba_dataset_fetch.  The translation unit is built with -ffp-contract=off and every
 // operation is spelled __fadd_rn / __fmul_rn / __fdiv_rn / __fsqrt_rn: one correctly rounded fp32 operation each.
 #pragma once
